@@ -15,6 +15,11 @@ Prints ONE JSON line (rank 0).  N > 1: queries are sharded across ranks with no 
 the path needs no RCCL.  Reported value: weak scaling (every rank aligns its own 10k queries); the same
 line also carries the strong-scaling figure (ONE fixed 10k batch sharded with shard.shard_range) under
 config.strong_scaling (--scaling strong swaps the two).
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
+
+also writes what the last timed step computed (rank 0) as DIR/<name>.npy, float64: the inputs are a function of the
+arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -69,6 +74,58 @@ def _counters(workload, key):
                          f"({workload}/{key}): re-run tools/profile_counters.py\n")
     e["file"] = os.path.relpath(COUNTERS_FILE, ROOT)
     return e
+
+
+DUMP_LIMIT = 60_000_000        # bytes of --dump-outputs' arrays in all (under 64 MB with the .npy headers)
+DUMP_QUERIES = 20000           # queries (block search: records) in the dump at most; beyond, a fixed seeded sample of them
+
+
+def _dump_sample(n, k):
+    """indices of the queries the dump holds: all n, or a sample of k of them that depends on (n, k) alone"""
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(20250523).choice(n, size=k, replace=False))
+
+
+def _save_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def _align_kept(bt, protein=False):
+    """Batch.align / BatchH.align(want=True, convert=False) with the alignments left allocated: the last timed step under
+    --dump-outputs, read (and freed) by _dump_alignments once the clock has stopped.  Returns (alignments, kernel_ms, cells)."""
+    from spaln_amd import abi
+    ms, cells = C.c_float(), C.c_int64()
+    arr = (abi.Alignment * bt.n)()
+    fn = bt.eng.lib.spdp_batch_align_h if protein else bt.eng.lib.spdp_batch_align
+    rc = fn(bt.h, arr, C.byref(ms), C.byref(cells))
+    if not protein or rc not in (0, 1):
+        bt.eng._check(rc, "spdp_batch_align_h" if protein else "spdp_batch_align")
+    return arr, ms.value, cells.value
+
+
+def _dump_alignments(d, lib, arr, n, protein=False):
+    """--dump-outputs of an align step, as Batch.align / BatchH.align(convert=True) hand it to the caller: per query its score
+    (protein: and its status, 0 or the negative n_skl of a refused alignment) and its SKL rows (m, n); the rows of entry j
+    are skl[skl_offset[j]:skl_offset[j + 1]], query[j] is its index in the batch.  Frees `arr`."""
+    try:
+        q = _dump_sample(n, DUMP_QUERIES)
+        k = np.array([max(arr[int(i)].n_skl, 0) for i in q], dtype=np.int64)
+        per = 4 + protein + 2 * k                                   # float64 values per entry (query, score, status, offset, rows)
+        q, k = q[np.cumsum(per) * 8 <= DUMP_LIMIT], k[np.cumsum(per) * 8 <= DUMP_LIMIT]
+        skl = np.zeros((int(k.sum()), 2), dtype=np.int64)
+        off = np.zeros(len(q) + 1, dtype=np.int64)
+        np.cumsum(k, out=off[1:])
+        for j, i in enumerate(q):
+            if k[j]:
+                skl[off[j]:off[j + 1]] = np.ctypeslib.as_array(C.cast(arr[int(i)].skl, C.POINTER(C.c_int32)),
+                                                               shape=(int(k[j]), 2))
+        out = {"query": q, "score": [arr[int(i)].score for i in q], "skl": skl, "skl_offset": off}
+        if protein:
+            out["status"] = [min(arr[int(i)].n_skl, 0) for i in q]
+        _save_outputs(d, out)
+    finally:
+        lib.spdp_free_alignments(arr, n)
 
 
 def _cpu_align_one(item):
@@ -303,14 +360,20 @@ def main_c3(args):
     t0 = time.perf_counter()
     kms = []
     cells = 0
-    for _ in range(args.steps):
-        _, ms, cells = bt.align(want=True, convert=False)
+    kept = None
+    for i in range(args.steps):
+        if args.dump_outputs and rank == 0 and i == args.steps - 1:
+            kept, ms, cells = _align_kept(bt, protein=True)
+        else:
+            _, ms, cells = bt.align(want=True, convert=False)
         kms.append(ms)
     kcells = cells                  # what the launches of the step processed (the exact-model ladders: linear-space passes + slabs)
     if exact or not cells:
         cells = bt.cells()          # the exact-model legs are quoted on BAND cells (m x window band, as round 4's), not on engine cells
     barrier()
     dt = time.perf_counter() - t0
+    if kept is not None:
+        _dump_alignments(args.dump_outputs, eng.lib, kept, bt.n, protein=True)
     if dist is not None:
         t = torch.tensor([dt], device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -541,6 +604,10 @@ def main_blk(args):
     kms = [step() for _ in range(args.steps)]
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the records of the last step (one row of out_cap int32 per EST); a fixed sample of the rows within DUMP_LIMIT
+        q = _dump_sample(n_q, min(DUMP_QUERIES, DUMP_LIMIT // (8 * (out_cap + 1))))
+        _save_outputs(args.dump_outputs, {"query": q, "record": d_out[torch.from_numpy(q).to(dev)].cpu().numpy()})
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -866,7 +933,7 @@ LINE_LIMIT = 4096            # bytes of the one stdout line (the driver keeps th
 
 
 def _leg_short(name, leg):
-    """one leg of the full record -> the few numbers the stdout line carries (the whole leg goes to profiles/)"""
+    """one leg of the full record -> the few numbers the stdout line carries (the whole leg goes to the full record)"""
     if not isinstance(leg, dict):
         return leg
     if leg.get("error"):
@@ -918,7 +985,7 @@ def compact_line(out, limit=LINE_LIMIT):
     line = {k: v for k, v in out.items() if k not in ("config", "roofline", "cpu_baseline")}
     scal = {k: {kk: vv for kk, vv in cfg[k].items() if kk != "sharding"} for k in ("strong_scaling", "weak_scaling") if isinstance(cfg.get(k), dict)}
     line["config"] = {"workload": str(cfg.get("workload", ""))[:200], **{k: cfg[k] for k in keep if cfg.get(k) is not None}, **scal,
-                      "legs": legs, "full_record": f"profiles/{ROUND_TAG}_bench_legs.json"}
+                      "legs": legs, "full_record": FULL_RECORD}
     line["roofline"] = rf
     line["cpu_baseline"] = cb
     s = json.dumps(line, separators=(",", ":"))
@@ -933,16 +1000,18 @@ def compact_line(out, limit=LINE_LIMIT):
     return s
 
 
+FULL_RECORD = os.path.join("bench_out", f"{ROUND_TAG}_bench_legs.json")
+
+
 def _write_full_record(out):
-    """the full record (every leg with its prose) as a file: profiles/ is what the judge reads, gpurun_out/ is what travels back"""
-    for d, name in ((os.path.join(ROOT, "profiles"), f"{ROUND_TAG}_bench_legs.json"),
-                    (os.path.join(ROOT, "gpurun_out"), f"{ROUND_TAG}_bench_legs.json")):
-        try:
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, name), "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError:
-            pass
+    """the full record (every leg with its prose) as a file in the ignored output directory; a record worth keeping is copied
+    to profiles/ by hand (a run never rewrites a committed file)"""
+    try:
+        os.makedirs(os.path.join(ROOT, os.path.dirname(FULL_RECORD)), exist_ok=True)
+        with open(os.path.join(ROOT, FULL_RECORD), "w") as f:
+            json.dump(out, f, indent=1)
+    except OSError:
+        pass
 
 
 def _parity_note(args):
@@ -991,7 +1060,13 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = every rank its own batch of --queries (the reported value), strong = one "
                          "batch of --queries sharded over the ranks; the other one is reported under config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float64, at most "
+                         "64 MB in all: alignments as score, skl, skl_offset and query (a fixed, seeded sample of at most "
+                         f"{DUMP_QUERIES} queries of a larger batch); --workload blk: the vote's records")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.queries:
         args.queries = ({"c5": 32, "blk": 200000}.get(args.workload, 10000)) if args.engines == "wip" else 1000
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1104,14 +1179,20 @@ def main():
         t0 = time.perf_counter()
         stats = []
         step_cells = 0
-        for _ in range(args.steps):
-            _, ms, kc = bt.align(want=True, convert=False)
+        kept = None
+        for i in range(args.steps):
+            if args.dump_outputs and rank == 0 and mode == args.scaling and i == args.steps - 1:
+                kept, ms, kc = _align_kept(bt)
+            else:
+                _, ms, kc = bt.align(want=True, convert=False)
             stats.append(bt.stats())
             step_cells = kc
         torch.cuda.synchronize()
         busy = time.perf_counter() - t0                              # this rank's own time, before it waits for the others
         barrier()
         dt = time.perf_counter() - t0
+        if kept is not None:
+            _dump_alignments(args.dump_outputs, eng.lib, kept, bt.n)
         tot_cells, tot_q = float(step_cells), float(len(batch))
         rank_busy, rank_cells = [busy], [float(step_cells)]
         if dist is not None:

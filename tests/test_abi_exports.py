@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -39,8 +40,11 @@ def test_struct_layout_matches_header(tmp_path):
 
 
 def test_no_gpu_means_loud_failure():
-    import torch
-    if torch.cuda.is_available():
+    # torch is asked in a child process: its wheel carries a HIP runtime of its own, and loaded here after the library it
+    # would start a second runtime in this process, which takes the device from the library's for every later test
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                           capture_output=True, text=True, check=True)
+    if probe.stdout.split()[-1] == "1":
         pytest.skip("GPU present")
     with pytest.raises(RuntimeError):
         engine.Engine(0)

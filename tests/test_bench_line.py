@@ -59,3 +59,41 @@ def test_the_round_record_is_within_the_limit():
         assert d["config"]["legs"][leg]["same"] == d["config"]["legs"][leg]["of"], leg
     kept = open(os.path.join(ROOT, "profiles", "r06_bench_line.json")).read().strip()
     assert len(kept) <= b.LINE_LIMIT and json.loads(kept)["value"] == full["value"]
+
+
+def test_dump_outputs_of_an_align_step(tmp_path):
+    """--dump-outputs: every query's score and SKL rows as the caller receives them, float64, within the size limit, the
+    sample of a large batch fixed by its size alone, the library's arrays freed"""
+    import ctypes as C
+    import numpy as np
+    from spaln_amd import abi
+    b = _bench()
+    rng = np.random.default_rng(3)
+    for n, protein, rows_hi in ((40, False, 30), (b.DUMP_QUERIES + 5, True, 30), (30, False, 400000)):
+        arr, keep = (abi.Alignment * n)(), []
+        for i in range(n):
+            k = int(rng.integers(-2, rows_hi))
+            arr[i].score, arr[i].n_skl = 7 * i - 50, k
+            if k > 0:
+                s = (abi.Skl * k)()
+                s_np = np.ctypeslib.as_array(C.cast(s, C.POINTER(C.c_int32)), shape=(k, 2))
+                s_np[:, 0], s_np[:, 1] = i, np.arange(k)
+                keep.append(s)
+                arr[i].skl = C.cast(s, C.POINTER(abi.Skl))
+        freed = []
+        d = tmp_path / f"d{n}"
+        b._dump_alignments(str(d), type("Lib", (), {"spdp_free_alignments": lambda self, a, m: freed.append(m)})(), arr, n, protein)
+        assert freed == [n]
+        out = {p.stem: np.load(p) for p in d.iterdir()}
+        assert set(out) == {"query", "score", "skl", "skl_offset"} | ({"status"} if protein else set())
+        assert all(a.dtype == np.float64 for a in out.values())
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        q = out["query"].astype(np.int64)
+        assert len(q) == min(n, b.DUMP_QUERIES) or rows_hi > 1000                  # (huge rows: a prefix of the sample)
+        assert np.array_equal(q, b._dump_sample(n, b.DUMP_QUERIES)[:len(q)])
+        for j, i in enumerate(q):
+            k = max(arr[i].n_skl, 0)
+            rows = out["skl"][int(out["skl_offset"][j]):int(out["skl_offset"][j + 1])]
+            assert out["score"][j] == 7 * i - 50 and rows.shape == (k, 2)
+            assert (rows[:, 0] == i).all() and np.array_equal(rows[:, 1], np.arange(k))
+            assert not protein or out["status"][j] == min(arr[i].n_skl, 0)
