@@ -12,9 +12,17 @@ the hot path over the whole batch, inputs resident in HBM.
 
 Prints ONE JSON line (rank 0).  N > 1: queries are sharded across ranks with no data-path collective
 (SURVEY.md 8e); the ranks only meet at the timing barriers and the reduction of the timer, over gloo --
-the path needs no RCCL.  Reported value: weak scaling (every rank aligns its own 10k queries); the same
-line also carries the strong-scaling figure (ONE fixed 10k batch sharded with shard.shard_range) under
-config.strong_scaling (--scaling strong swaps the two).
+the path needs no RCCL.  Reported value: weak scaling (every rank aligns its own 10k queries; --scaling strong:
+ONE fixed 10k batch sharded with shard.shard_range).
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the steps, writes the dump
+below if asked, and prints the line.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+
+also measures and checks everything else: the CPU baseline (the compiled reference, or the oracle port), the
+upload-inclusive and streamed figures, at N > 1 the other scaling mode, the seeded-path leg, the other workloads and
+engines as legs (--legs), each a run of its own, and the full record of them all under bench_out/.
 
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
 
@@ -392,8 +400,8 @@ def main_c3(args):
         import multiprocessing as mp
         ncores = _host_cores()
         ns = max(1, min(args.cpu_sample if args.cpu_sample > 0 else 2 * ncores, len(batch)))
-        if world > 1:
-            cpu_base = None                                   # timed at N = 1 only
+        if world > 1 or not args.full:
+            cpu_base = None                                   # timed at N = 1 only, under --full
         elif _ref_available() and not args.cpu_port:
             from oracle import oracle
             ns = max(1, min(args.cpu_sample if args.cpu_sample > 0 else 64 * ncores, len(batch)))
@@ -539,8 +547,9 @@ def main_blk(args):
     eng = engine.Engine(local_rank)
     # the index builder (fourth slice): the same genome's index made by the library on the device, compared with
     # the tables of the reference's file and timed beside the reference's formatter (which also writes the sequence files)
+    # under --full; without the reference's file it is the index the vote searches
     index_build = None
-    if rank == 0 or not have_ref:
+    if not have_ref or (rank == 0 and args.full):
         t_b = time.perf_counter()
         with open(os.path.join(td, "gnm.mfa"), "rb") as f:
             raw = np.frombuffer(f.read(), dtype=np.uint8)
@@ -560,7 +569,8 @@ def main_blk(args):
         goff = np.array([0] + list(np.cumsum(chr_len_seen)), dtype=np.int64)
         parse_s = time.perf_counter() - t_b
         bp = blocks.build_params_default(eng.lib, os.path.getsize(os.path.join(td, "gnm.mfa")), 1, threaded=1)
-        blocks.build_index(eng, gcodes[:1 << 20], np.array([0, 1 << 20], dtype=np.int64), bp)          # (code objects loaded, pools sized)
+        if args.full:
+            blocks.build_index(eng, gcodes[:1 << 20], np.array([0, 1 << 20], dtype=np.int64), bp)      # (code objects loaded, pools sized)
         t_b = time.perf_counter()
         built, bsec = blocks.build_index(eng, gcodes, goff, bp, max_intron_len=13000)
         build_s = time.perf_counter() - t_b
@@ -568,15 +578,16 @@ def main_blk(args):
                                            for k in ("blk_nblk", "blk_wscr", "blk_blkp", "blk_blkb", "blk_chr", "blk_bitpat", "blk_rscrtab", "blk_pb2c"))
         if fx is None:
             fx = built
-        index_build = {"what": "spdp_blk_index_build on the same residues (inputs in host memory; the upload is inside), its tables against "
-                               "those of the reference's file", "identical_tables": same if same is None else bool(same), "genome_nt": int(gcodes.size),
-                       "ktuple": int(bp.ktuple), "blklen": int(bp.blklen), "postings": int(np.asarray(built["blk_blkb"]).size),
-                       "library_s": round(build_s, 3), "library_device_s": round(bsec[0], 3), "library_host_s": round(bsec[1], 3),
-                       "residues_per_s": round(gcodes.size / build_s, 0),
-                       "reference_format_s": None if ref_format_s is None else round(ref_format_s, 2), "reference_threads": _host_cores(),
-                       "note": "reference = `spaln -W -KD -t<cores>` on the FASTA file: it parses the file and writes the .seq / .idx / "
-                               ".ent files as well as the index; the library starts from residue codes (FASTA -> codes here: "
-                               f"{parse_s:.2f} s of numpy)"}
+        if args.full:
+            index_build = {"what": "spdp_blk_index_build on the same residues (inputs in host memory; the upload is inside), its tables against "
+                                   "those of the reference's file", "identical_tables": same if same is None else bool(same), "genome_nt": int(gcodes.size),
+                           "ktuple": int(bp.ktuple), "blklen": int(bp.blklen), "postings": int(np.asarray(built["blk_blkb"]).size),
+                           "library_s": round(build_s, 3), "library_device_s": round(bsec[0], 3), "library_host_s": round(bsec[1], 3),
+                           "residues_per_s": round(gcodes.size / build_s, 0),
+                           "reference_format_s": None if ref_format_s is None else round(ref_format_s, 2), "reference_threads": _host_cores(),
+                           "note": "reference = `spaln -W -KD -t<cores>` on the FASTA file: it parses the file and writes the .seq / .idx / "
+                                   ".ent files as well as the index; the library starts from residue codes (FASTA -> codes here: "
+                                   f"{parse_s:.2f} s of numpy)"}
         del raw, keep
     dix = blocks.BlockIndex(eng, fx)
     out_cap = 768
@@ -640,7 +651,7 @@ def main_blk(args):
                     "queries": nf, "with_a_locus": with_locus, "loci": n_loc, "first_locus_covers_the_planted_gene_on_its_strand": int(ok),
                     "seconds": round(find_s, 2), "queries_per_s": round(nf / find_s, 0)}
     ref_blk = None
-    if rank == 0 and have_ref and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "spaln_blktime")):
+    if rank == 0 and args.full and have_ref and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "spaln_blktime")):
         # the reference's own block search on the same index and queries: its program with a stop watch around SrchBlk::findblock
         # (oracle/_ref/spaln_blktime: the reference's object code, one symbol renamed) on a sample, all host cores
         import re as _re
@@ -670,47 +681,54 @@ def main_blk(args):
         rec = d_out.cpu().numpy()
         reached = (rec[:, 2] & blocks.REACHED) != 0
         flagged = int(((rec[:, 2] & (blocks.CUT | blocks.TABLE)) != 0).sum())
-        # mapping accuracy: the best candidate pair covers the planted locus, on the right strand
         prm = fx["blk_prm"]
         blklen = int(prm[6])
-        chr_first = np.asarray(fx["blk_chr"]).reshape(-1, 2)[:, 1]
-        hit = hit_any = 0
-        sample = np.arange(0, n_q, max(1, n_q // 20000))
-        for i in sample:
-            r = blocks.split_record(rec[i])
-            if not r.get("reached") or "pairs" not in r or not len(r["pairs"]):
-                continue
-            bscr, c, lb, rb, ub, db, zl, zr, rvs = (int(x) for x in r["pairs"][0])
-            lo, hi = (lb - zl) * blklen if zl else 0, ((rb - zl if zl else 0) + 1) * blklen
-            covers = c == truth[i, 0] and lo <= truth[i, 1] + 60000 and truth[i, 1] <= hi
-            hit += covers and rvs == int(rc[i])
-            hit_any += covers
-        # parity on a sample against the oracle (the pinned restatement), in the same run
-        from oracle import blk as oblk
-        ix, _keep = oblk.index_of(fx)
-        ix.extblockl = int(prm[27])
-        same = 0
-        chk = sample[:300]
-        for i in chk:
-            want = oblk.vote(ix, codes[i], 0, frag, 0)
-            got = blocks.split_record(rec[i])
-            if want is None:
-                same += not got.get("reached")
-                continue
-            w = oblk.split_recorded(want[0], want[1])
-            same += bool(got.get("reached") and "head" in got and np.array_equal(got["head"], w["head"]) and
-                         np.array_equal(got["pairs"], want[1][2:].reshape(-1, 9)) and
-                         got["runs"] == [sorted(x) for x in oblk.runs_near_pairs(ix, w["runs"], got["pairs"])])
-        # CPU baseline: the oracle's vote, one process per host core
-        import multiprocessing as mp
-        ncores = _host_cores()
-        ns = min(n_q, args.cpu_sample if args.cpu_sample > 0 else 400 * ncores)
-        as_file = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}      # (the container knows the signed types)
-        spdg.save(fx_path, {k: np.asarray(v).view(as_file.get(np.asarray(v).dtype, np.asarray(v).dtype)) for k, v in fx.items() if k.startswith("blk_")})
-        jobs = [(fx_path, [codes[i] for i in range(c, ns, ncores)]) for c in range(ncores)]
-        with mp.get_context("fork").Pool(ncores) as pool:
-            busy = pool.map(_blk_oracle_chunk, jobs)
-        cpu_qps = ns / max(busy)
+        checks = {}
+        cpu_base = None
+        if args.full:
+            # mapping accuracy: the best candidate pair covers the planted locus, on the right strand
+            chr_first = np.asarray(fx["blk_chr"]).reshape(-1, 2)[:, 1]
+            hit = hit_any = 0
+            sample = np.arange(0, n_q, max(1, n_q // 20000))
+            for i in sample:
+                r = blocks.split_record(rec[i])
+                if not r.get("reached") or "pairs" not in r or not len(r["pairs"]):
+                    continue
+                bscr, c, lb, rb, ub, db, zl, zr, rvs = (int(x) for x in r["pairs"][0])
+                lo, hi = (lb - zl) * blklen if zl else 0, ((rb - zl if zl else 0) + 1) * blklen
+                covers = c == truth[i, 0] and lo <= truth[i, 1] + 60000 and truth[i, 1] <= hi
+                hit += covers and rvs == int(rc[i])
+                hit_any += covers
+            # parity on a sample against the oracle (the pinned restatement), in the same run
+            from oracle import blk as oblk
+            ix, _keep = oblk.index_of(fx)
+            ix.extblockl = int(prm[27])
+            same = 0
+            chk = sample[:300]
+            for i in chk:
+                want = oblk.vote(ix, codes[i], 0, frag, 0)
+                got = blocks.split_record(rec[i])
+                if want is None:
+                    same += not got.get("reached")
+                    continue
+                w = oblk.split_recorded(want[0], want[1])
+                same += bool(got.get("reached") and "head" in got and np.array_equal(got["head"], w["head"]) and
+                             np.array_equal(got["pairs"], want[1][2:].reshape(-1, 9)) and
+                             got["runs"] == [sorted(x) for x in oblk.runs_near_pairs(ix, w["runs"], got["pairs"])])
+            # CPU baseline: the oracle's vote, one process per host core
+            import multiprocessing as mp
+            ncores = _host_cores()
+            ns = min(n_q, args.cpu_sample if args.cpu_sample > 0 else 400 * ncores)
+            as_file = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}      # (the container knows the signed types)
+            spdg.save(fx_path, {k: np.asarray(v).view(as_file.get(np.asarray(v).dtype, np.asarray(v).dtype)) for k, v in fx.items() if k.startswith("blk_")})
+            jobs = [(fx_path, [codes[i] for i in range(c, ns, ncores)]) for c in range(ncores)]
+            with mp.get_context("fork").Pool(ncores) as pool:
+                busy = pool.map(_blk_oracle_chunk, jobs)
+            cpu_qps = ns / max(busy)
+            checks = {"best_pair_covers_planted_locus": f"{hit_any} / {len(sample)} ({hit} with the strand as planted)",
+                      "identical_to_oracle_on_sample": f"{same} / {len(chk)}"}
+            cpu_base = ref_blk or {"value": round(cpu_qps, 1), "unit": "queries/s", "cores": ncores, "kind": "port",
+                                   "sample": f"first {ns} ESTs through the oracle's vote (oracle/spdp_oracle_blk.c), one process per host core"}
         k_ms = float(np.mean(kms))
         words = int(np.asarray(fx["blk_blkb"]).size)
         # algorithmic bytes per query: its codes once, per looked-up word the two table entries (Nblk 2 B, wscr 2 B, blkp 4 B) and
@@ -732,11 +750,9 @@ def main_blk(args):
                        "cells_per_gpu_per_step": 0,
                        "index": {"ktuple": int(prm[28]) // 8, "tabsize": int(prm[3]), "nshift": int(prm[5]), "blklen": blklen, "nseg": int(prm[19]),
                                  "words": words, "patterns": int(prm[8])},
-                       "reached_first_call": int(reached.sum()), "flagged": flagged,
-                       "best_pair_covers_planted_locus": f"{hit_any} / {len(sample)} ({hit} with the strand as planted)",
-                       "identical_to_oracle_on_sample": f"{same} / {len(chk)}",
+                       "reached_first_call": int(reached.sum()), "flagged": flagged, **checks,
                        "words_looked_up_per_query": round(float(tw), 1),
-                       "input_generation_s": round(input_s, 1), "index_build": index_build, "find": find_leg,
+                       "input_generation_s": round(input_s, 1), **({"index_build": index_build, "find": find_leg} if args.full else {}),
                        "reference_parity": "the vote's state at every TestOutput call, the block pairs, and every candidate locus FindHsp makes of them "
                                            "(HSPs included): bit-identical to the compiled reference's recorded runs (tests/golden/blk_*.spdg: "
                                            "tests/test_gpu_blk.py, test_gpu_blk_find.py)"},
@@ -747,8 +763,7 @@ def main_blk(args):
                                  "slots in the wave's slab of HBM (random 8-byte accesses): bound by memory latency per word, hidden by 16 waves per "
                                  "CU; algorithmic bytes = codes + per word its table entries and posting list + two score slots per listed block + "
                                  "the record"},
-            "cpu_baseline": ref_blk or {"value": round(cpu_qps, 1), "unit": "queries/s", "cores": ncores, "kind": "port",
-                                        "sample": f"first {ns} ESTs through the oracle's vote (oracle/spdp_oracle_blk.c), one process per host core"},
+            "cpu_baseline": cpu_base,
         }
         if ref_blk:
             out["config"]["vote_port_baseline"] = {"value": round(cpu_qps, 1), "unit": "queries/s", "cores": ncores, "kind": "port",
@@ -902,7 +917,7 @@ def _run_leg(name):
         d.update(what=what, args=" ".join(argv), wall_s=round(time.perf_counter() - t0, 1))
         return d
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--legs", "none", "--seeded-pairs", "0"],
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--legs", "none", "--seeded-pairs", "0"],
                            env=env, capture_output=True, text=True, timeout=900)
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     except Exception as e:                                       # noqa: BLE001 -- a leg must not cost the line
@@ -930,6 +945,7 @@ def _run_leg(name):
 
 ROUND_TAG = "r06"
 LINE_LIMIT = 4096            # bytes of the one stdout line (the driver keeps the tail of stdout: round 5's 22 KB line did not parse)
+FULL_RECORD = os.path.join("bench_out", f"{ROUND_TAG}_bench_legs.json")
 
 
 def _leg_short(name, leg):
@@ -964,9 +980,10 @@ def _leg_short(name, leg):
     return o
 
 
-def compact_line(out, limit=LINE_LIMIT):
+def compact_line(out, limit=LINE_LIMIT, record=FULL_RECORD):
     """the ONE stdout line: the contract's keys + roofline + cpu_baseline + one short record per leg, at most `limit` bytes; the
-    prose (what each leg is, which reference output it is pinned to, the sources of the counters) stays in the full record"""
+    prose (what each leg is, which reference output it is pinned to, the sources of the counters) stays in the full record
+    `record` (None: a plain run, which writes none and has no legs)"""
     cfg = out.get("config", {})
     legs = {k: _leg_short(k, v) for k, v in cfg.items() if isinstance(v, dict) and k not in ("with_h2d",)
             and not k.endswith("_scaling")}
@@ -985,7 +1002,7 @@ def compact_line(out, limit=LINE_LIMIT):
     line = {k: v for k, v in out.items() if k not in ("config", "roofline", "cpu_baseline")}
     scal = {k: {kk: vv for kk, vv in cfg[k].items() if kk != "sharding"} for k in ("strong_scaling", "weak_scaling") if isinstance(cfg.get(k), dict)}
     line["config"] = {"workload": str(cfg.get("workload", ""))[:200], **{k: cfg[k] for k in keep if cfg.get(k) is not None}, **scal,
-                      "legs": legs, "full_record": FULL_RECORD}
+                      **({"legs": legs, "full_record": record} if record else {})}
     line["roofline"] = rf
     line["cpu_baseline"] = cb
     s = json.dumps(line, separators=(",", ":"))
@@ -998,9 +1015,6 @@ def compact_line(out, limit=LINE_LIMIT):
         line["config"]["legs"] = {"dropped": "see full_record"}
         s = json.dumps(line, separators=(",", ":"))
     return s
-
-
-FULL_RECORD = os.path.join("bench_out", f"{ROUND_TAG}_bench_legs.json")
 
 
 def _write_full_record(out):
@@ -1036,30 +1050,35 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks: the CPU baseline, the "
+                         "upload-inclusive and streamed figures, the other scaling mode at N > 1, the seeded-path leg, the "
+                         "legs (--legs) and the full record; off: setup, warm-up, the timed steps, --dump-outputs and the line")
     ap.add_argument("--seeded-pairs", type=int, default=10000,
-                    help="pairs of the seeded-path (-Q7) leg reported in config.seeded_q7 (c2, N = 1; 0: skip)")
+                    help="--full: pairs of the seeded-path (-Q7) leg reported in config.seeded_q7 (c2, N = 1; 0: skip)")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5", "blk"], default="c2",
                     help="c2: cDNA x genome (the headline); c3: protein x genome (Fwd2h1 path); "
                          "c4: 500-nt ESTs (traceback branch of the ladder only); c5: 50 kb cDNAs with 25 exons "
                          "(recursive linear-space branch all the way down)")
     ap.add_argument("--legs", default="auto",
-                    help="the other BASELINE configs and engines as legs of the default line (config.c3 / c4 / c5 / a0 / a1 / "
-                         "c3_a0 / c3_a1), each a run of this script: auto = all of them with the default workload at N = 1, "
+                    help="--full: the other BASELINE configs and engines as legs of the default line (config.c3 / c4 / c5 / a0 / "
+                         "a1 / c3_a0 / c3_a1 ...), each a run of its own: auto = all of them with the default workload at N = 1, "
                          "none, or a comma-separated subset")
     ap.add_argument("--engines", choices=["wip", "a0", "a1"], default="wip",
                     help="wip = the -A2 `_wip` engines (the headline); a0 = the exact-intron-length engines "
                          "(algmode.alg 0: forwardS_ng / hirschbergS_ng, spdp_rowwave.hip); a1 = the -A1 engines (spdp_exact.hip)")
     ap.add_argument("--queries", type=int, default=0, help="queries per GPU (default 10000; 1000 with --engines a0 / a1)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="queries timed on the CPU oracle (0 = 2 per host core)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: queries timed on the CPU baseline (0 = its default)")
     ap.add_argument("--intron-hi", type=int, default=20000, help="upper clip of planted intron lengths")
     ap.add_argument("--cpu-port", action="store_true",
-                    help="time the oracle port as the CPU baseline even when oracle/_ref/spaln is present")
+                    help="--full: time the oracle port as the CPU baseline even when oracle/_ref/spaln is present")
     ap.add_argument("--plain", action="store_true",
-                    help="nothing but --warmup + --steps aligns of the batch (no upload-inclusive / streamed figures): what "
-                         "tools/profile_counters.py runs under rocprofv3, so that counter totals divide by the number of steps")
+                    help="nothing but --warmup + --steps aligns of the batch (no upload-inclusive / streamed figures, no "
+                         "untimed first align): what tools/profile_counters.py runs under rocprofv3, so that counter totals "
+                         "divide by the number of steps")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = every rank its own batch of --queries (the reported value), strong = one "
-                         "batch of --queries sharded over the ranks; the other one is reported under config")
+                         "batch of --queries sharded over the ranks; --full: the other one is reported under config")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float64, at most "
                          "64 MB in all: alignments as score, skl, skl_offset and query (a fixed, seeded sample of at most "
@@ -1067,6 +1086,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.legs not in ("auto", "none") and not args.full:
+        ap.error("--legs runs with --full only")
     if not args.queries:
         args.queries = ({"c5": 32, "blk": 200000}.get(args.workload, 10000)) if args.engines == "wip" else 1000
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1127,7 +1148,7 @@ def main():
         for w, q, s5, s3, _ in batch:
             ps.add(q, w, s5, s3, **(synth.exact_inputs(w) if exact else {}))
         h2d = None
-        if mode == args.scaling and not args.plain:
+        if mode == args.scaling and args.full and not args.plain:
             # the same step with the batch coming over PCIe first (upload + align): reported beside the headline, which
             # counts inputs resident in HBM (the bench contract); full column records, ~95 B per genomic position
             tb0 = time.perf_counter()
@@ -1173,6 +1194,10 @@ def main():
                 h2d["streamed_step_ms"] = None
                 h2d["streamed_error"] = str(e)[:120]
         bt = eng.upload(sc, ps)
+        if mode == args.scaling and h2d is None and not args.plain:
+            # one untimed align first, as --full's upload-inclusive figures leave the context: its first align loads the
+            # code objects and sizes the pools, which the timed steps never included, --warmup 0 or not
+            bt.align(want=True, convert=False)
         for _ in range(args.warmup):
             bt.align(want=True, convert=False)
         barrier()
@@ -1214,7 +1239,7 @@ def main():
 
     prim = measure(args.scaling)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         om = "strong" if args.scaling == "weak" else "weak"
         o = measure(om)
         other = {"scaling": om, "value": round(o["total_cells"] * args.steps / o["dt"] / 1e9, 3), "unit": "GCUPS",
@@ -1243,8 +1268,8 @@ def main():
         import multiprocessing as mp
         ncores = _host_cores()
         ns = max(1, min(args.cpu_sample if args.cpu_sample > 0 else 2 * ncores, len(batch)))
-        if world > 1:
-            cpu_base = None                                   # timed at N = 1 only
+        if world > 1 or not args.full:
+            cpu_base = None                                   # timed at N = 1 only, under --full
         elif exact and not _ref_available():
             cpu_base = None                                   # (the port's ladder is the -A2 one)
         elif _ref_available() and not args.cpu_port:
@@ -1326,14 +1351,16 @@ def main():
                                  "VALU-issue bound recurrence (integer scores carried as exact fp32); HBM fraction reported as asked; kernel_ms = mean duration per step summed over the step's launches of this kernel (one per pipelined chunk)"},
             "cpu_baseline": cpu_base,
         }
-        if world == 1 and args.workload == "c2" and not exact and args.seeded_pairs > 0:
+        if args.full and world == 1 and args.workload == "c2" and not exact and args.seeded_pairs > 0:
             leg = _seeded_leg(args.seeded_pairs)
             if leg:
                 out["config"]["seeded_q7"] = leg
     eng.close()
     if dist is not None:
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(compact_line(out, record=None), flush=True)
+    elif rank == 0:
         # the other BASELINE configs and engines, each a run of this script on the now idle GPU (N = 1, default workload)
         want = args.legs
         if want == "auto":

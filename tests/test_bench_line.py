@@ -2,6 +2,10 @@
 import importlib.util
 import json
 import os
+import subprocess
+import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,6 +63,44 @@ def test_the_round_record_is_within_the_limit():
         assert d["config"]["legs"][leg]["same"] == d["config"]["legs"][leg]["of"], leg
     kept = open(os.path.join(ROOT, "profiles", "r06_bench_line.json")).read().strip()
     assert len(kept) <= b.LINE_LIMIT and json.loads(kept)["value"] == full["value"]
+
+
+def test_a_plain_line_names_no_legs_and_no_record():
+    """a run without --full has no legs and writes no full record: its line says neither, and keeps the contract's keys"""
+    b = _bench()
+    full = json.load(open(os.path.join(ROOT, "profiles", "r05_bench_line_with_legs.json")))
+    for k in list(full["config"]):
+        if isinstance(full["config"][k], dict) and k != "with_h2d":
+            del full["config"][k]
+    full["cpu_baseline"] = None
+    d = json.loads(b.compact_line(full, record=None))
+    assert "legs" not in d["config"] and "full_record" not in d["config"]
+    assert d["value"] == full["value"] and d["ms_per_step"] == full["ms_per_step"] and d["cpu_baseline"] is None
+    assert json.loads(b.compact_line(full))["config"]["full_record"] == b.FULL_RECORD
+
+
+def test_legs_need_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "c3"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_a_plain_run_times_the_steps_and_nothing_else():
+    """without --full: no CPU baseline, no upload-inclusive figures, no seeded leg, no legs, no full record written"""
+    rec_path = os.path.join(ROOT, "bench_out", "r06_bench_legs.json")
+    before = os.stat(rec_path).st_mtime_ns if os.path.exists(rec_path) else None
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--queries", "300"], capture_output=True, text=True, env=env, timeout=550)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and d["config"]["queries_per_gpu"] == 300
+    assert not {"legs", "full_record", "queries_per_s_incl_upload", "seeded_q7"} & set(d["config"])
+    assert (os.stat(rec_path).st_mtime_ns if os.path.exists(rec_path) else None) == before
 
 
 def test_dump_outputs_of_an_align_step(tmp_path):

@@ -1,6 +1,6 @@
 """The N > 1 paths with the real engine, on one card: (a) a device group whose members are two contexts on GPU 0
 shards a batch and returns exactly what one context returns, in query order; (b) bench.py --gpus 2 spawns two ranks
-(BENCH_SHARE_GPU=1: both on GPU 0), reports n_gpus = 2 and both scaling modes."""
+(BENCH_SHARE_GPU=1: both on GPU 0), reports n_gpus = 2 and, with --full, both scaling modes."""
 import json
 import os
 import subprocess
@@ -51,7 +51,7 @@ def test_bench_two_ranks_on_one_card():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--queries", "600", "--cpu-sample", "4"], capture_output=True, text=True, env=env, timeout=850)
+                          "--queries", "600", "--cpu-sample", "4", "--full"], capture_output=True, text=True, env=env, timeout=850)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
