@@ -192,6 +192,77 @@ void* SpdpContext::staging(int k, size_t bytes)
     return stage_ptr[k];
 }
 
+// the staging ring of spdp_internal.h.  The calling thread issues the copies and never packs: a packer may wait on `copied`, which
+// only the calling thread advances
+int spdp_upload_ring(SpdpContext* ctx, const std::vector<int64_t>& off, int64_t tot, int64_t grp_positions,
+                     std::vector<StagedStream>& st, const std::function<void(int i, int64_t at)>& pack)
+{
+    const int n = (int) off.size(), ring = 4;
+    std::vector<int> grp_first, grp_of(n);
+    int64_t slot_cap = 1, acc = 0;
+    for (int i = 0; i < n; ++i) {
+        if (i == 0 || acc >= grp_positions) { grp_first.push_back(i); acc = 0; }
+        grp_of[i] = (int) grp_first.size() - 1;
+        acc += (i + 1 < n ? off[i + 1] : tot) - off[i];
+        slot_cap = std::max(slot_cap, acc);
+    }
+    for (StagedStream& s : st)
+        if (!(s.host = ctx->staging(s.slot, (size_t) slot_cap * ring * s.bytes))) { ctx->err = "out of pinned host memory"; return -1; }
+    const int n_grp = (int) grp_first.size();
+    std::atomic<int> copied{0};                         // groups whose copy has left the staging
+    std::vector<std::atomic<int>> grp_done(n_grp);      // problems packed, per group
+    for (auto& g : grp_done) g.store(0);
+    std::atomic<int> next_prob{0};
+    auto packer = [&] {
+        for (int i; (i = next_prob.fetch_add(1)) < n; ) {
+            const int g = grp_of[i];
+            while (copied.load(std::memory_order_acquire) < g - ring + 1) std::this_thread::yield();
+            pack(i, (int64_t) (g % ring) * slot_cap + (off[i] - off[grp_first[g]]));
+            grp_done[g].fetch_add(1, std::memory_order_release);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0, nt = std::max(1, std::min(spdp_host_cpus(), n)); t < nt; ++t) th.emplace_back(packer);
+    hipError_t ce = hipSuccess;
+    std::vector<hipEvent_t> left((size_t) ring, nullptr);
+    for (int k = 0; k < ring && ce == hipSuccess && n_grp > ring; ++k) ce = hipEventCreateWithFlags(&left[k], hipEventDisableTiming);
+    for (int g = 0; g < n_grp && ce == hipSuccess; ++g) {
+        const int first = grp_first[g], last = g + 1 < n_grp ? grp_first[g + 1] : n;
+        while (grp_done[g].load(std::memory_order_acquire) < last - first) std::this_thread::yield();
+        const int64_t c0 = off[first], c1 = last < n ? off[last] : tot, s0 = (int64_t) (g % ring) * slot_cap;
+        for (const StagedStream& s : st)
+            if (ce == hipSuccess)
+                ce = hipMemcpyAsync((char*) s.dev + c0 * s.bytes, (char*) s.host + s0 * s.bytes, (size_t) (c1 - c0) * s.bytes,
+                                    hipMemcpyHostToDevice, ctx->stream);
+        if (n_grp > ring) {                             // (a call of up to four groups never waits: every group has its slot)
+            if (ce == hipSuccess) ce = hipEventRecord(left[g % ring], ctx->stream);
+            if (ce == hipSuccess && g >= 1) { ce = hipEventSynchronize(left[(g - 1) % ring]); copied.store(g, std::memory_order_release); }
+        }
+    }
+    copied.store(INT32_MAX, std::memory_order_release);                   // (on an error too: no packer may wait for ever)
+    for (std::thread& t : th) t.join();
+    const hipError_t se = hipStreamSynchronize(ctx->stream);              // the staging is the context's: one upload at a time
+    for (hipEvent_t e : left) if (e) (void) hipEventDestroy(e);
+    if (ce == hipSuccess) ce = se;
+    if (ce != hipSuccess) { ctx->err = std::string("column record upload: ") + hipGetErrorString(ce); return -1; }
+    return 0;
+}
+
+int spdp_upload_cip(SpdpContext* ctx, int n, const std::function<const int32_t*(int i, size_t& len)>& row, std::vector<int32_t>& off,
+                    void** d)
+{
+    off.assign(n, -1);
+    std::vector<int32_t> h;
+    for (int i = 0; i < n; ++i) {
+        size_t len = 0;
+        if (const int32_t* r = row(i, len)) { off[i] = (int32_t) h.size(); h.insert(h.end(), r, r + len); }
+    }
+    if (h.empty()) return 0;
+    HIPCHK(hipMalloc(d, h.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
 const char* spdp_last_error(const SpdpContext* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int spdp_device_name(const SpdpContext* ctx, char* buf, int buflen)
@@ -306,53 +377,25 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
         (void) hipFree(d_b);
         if (rc) return -1;
     } else {
-        // column records (8 B per genomic position) and class bytes, packed by all host cores into pinned staging
-        // memory the context keeps (a 10 k batch is ~1 GB: one thread and pageable memory took 430 ms, 40 % of a step)
-        int n_thr = spdp_host_cpus();
-        if (const char* e = getenv("SPDP_UPLOAD_THREADS")) n_thr = atoi(e);
-        n_thr = std::max(1, std::min(std::min(n_thr, 32), n));
-        std::vector<int> t_s5(n_thr, INT32_MIN), t_s3(n_thr, INT32_MIN);
-        // the copy of a group of problems (~8 M positions) starts as soon as the group is packed, under the packing of the next ones;
-        // the groups go through a ring of four slots of the staging memory (a slot is packed again once its copy has left): a map +
-        // align call holds 5 * 10^8 positions, which was 5 GB of pinned memory when every group had a place of its own
-        std::vector<int> grp_first, grp_of(n);
-        int64_t slot_cap = 1;
-        {
-            int64_t acc = 0;
-            for (int i = 0; i < n; ++i) {
-                if (i == 0 || acc >= (8 << 20)) { grp_first.push_back(i); acc = 0; }
-                grp_of[i] = (int) grp_first.size() - 1;
-                acc += (int64_t) probs[i].b_len + 1 + SPDP_COL_PAD;
-                slot_cap = std::max(slot_cap, acc);
-            }
-        }
-        const int n_grp = (int) grp_first.size();
-        const int ring = (getenv("SPDP_UPLOAD_RING") && atoi(getenv("SPDP_UPLOAD_RING")) == 0) ? std::max(1, n_grp) : 4;     // (0: a place per group)
-        const size_t nc = 2 * (size_t) slot_cap * (size_t) ring;
-        int32_t* hc = (int32_t*) ctx->staging(0, nc * sizeof(int32_t));
-        uint8_t* hx = has_exact ? (uint8_t*) ctx->staging(1, nc) : nullptr;
-        if (!hc || (has_exact && !hx)) { ctx->err = "out of pinned host memory"; return -1; }
-        auto stage_of = [&](int i) -> int64_t { const int g = grp_of[i]; return (int64_t) (g % ring) * slot_cap + (col_off[i] - col_off[grp_first[g]]); };
-        std::atomic<int> copied{0};                     // groups whose copy has left the staging
-        std::vector<std::atomic<int>> grp_done(n_grp);
-        for (auto& g : grp_done) g.store(0);
-        std::atomic<int> next_prob{0};
-        auto pack = [&](int t) {
-            int m5 = INT32_MIN, m3 = INT32_MIN;
-            for (;;) {
-                const int i = next_prob.fetch_add(1);
-                if (i >= n) break;
+        // column records (8 B per genomic position) and class bytes, packed by all host cores into pinned staging memory the context
+        // keeps (a 10 k batch is ~1 GB: one thread and pageable memory took 430 ms, 40 % of a step) and copied in groups of ~8 M
+        // positions under the packing of the next ones (a map + align call holds 5 * 10^8 positions: 5 GB of pinned memory when
+        // every group had a place of its own)
+        std::vector<StagedStream> st = {{0, d_cols, 2 * sizeof(int32_t)}};
+        if (has_exact) st.push_back({1, d_aux, 2});
+        std::vector<int> p_s5(n, INT32_MIN), p_s3(n, INT32_MIN);
+        if (spdp_upload_ring(ctx, col_off, col_tot, 8 << 20, st, [&](int i, int64_t at) {
                 const SpdpProblem& p = probs[i];
-                while (copied.load(std::memory_order_acquire) < grp_of[i] - ring + 1) std::this_thread::yield();
                 if (has_exact) {
-                    uint8_t* x = hx + 2 * stage_of(i);
+                    uint8_t* x = (uint8_t*) st[1].host + 2 * at;
                     for (int nn = 0; nn <= p.b_len; ++nn, x += 2) {
                         x[0] = (p.cano5[nn] ? 1 : 0) | (p.cano3[nn] ? 2 : 0);
                         x[1] = p.dinc[nn];
                     }
                     memset(x, 0, 2 * SPDP_COL_PAD);
                 }
-                int32_t* cr = hc + 2 * stage_of(i);
+                int32_t* cr = (int32_t*) st[0].host + 2 * at;
+                int m5 = INT32_MIN, m3 = INT32_MIN;
                 for (int nn = 0; nn <= p.b_len; ++nn, cr += 2) {
                     const uint16_t s5 = (uint16_t) (int16_t) (p.sig5[nn] + sc.ipen);
                     const uint16_t s3 = (uint16_t) p.sig3[nn];
@@ -361,37 +404,9 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
                     cr[1] = nn > 0 ? p.b[nn - 1] : 0;
                 }
                 memset(cr, 0, 2 * SPDP_COL_PAD * sizeof(int32_t));
-                grp_done[grp_of[i]].fetch_add(1, std::memory_order_release);
-            }
-            t_s5[t] = m5; t_s3[t] = m3;
-        };
-        {
-            std::vector<std::thread> th;
-            for (int t = 0; t < n_thr; ++t) th.emplace_back(pack, t);
-            hipError_t ce = hipSuccess;
-            std::vector<hipEvent_t> left((size_t) ring, nullptr);
-            for (int k = 0; k < ring && ce == hipSuccess && n_grp > ring; ++k) ce = hipEventCreateWithFlags(&left[k], hipEventDisableTiming);
-            for (int g = 0; g < n_grp && ce == hipSuccess; ++g) {
-                const int first = grp_first[g], last = g + 1 < n_grp ? grp_first[g + 1] : n;
-                while (grp_done[g].load(std::memory_order_acquire) < last - first) std::this_thread::yield();
-                const int64_t c0 = col_off[first], c1 = last < n ? col_off[last] : col_tot;
-                const int64_t s0 = (int64_t) (g % ring) * slot_cap;
-                ce = hipMemcpyAsync((int32_t*) d_cols + 2 * c0, hc + 2 * s0, (size_t) (c1 - c0) * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-                if (ce == hipSuccess && has_exact)
-                    ce = hipMemcpyAsync((uint8_t*) d_aux + 2 * c0, hx + 2 * s0, (size_t) (c1 - c0) * 2, hipMemcpyHostToDevice, ctx->stream);
-                if (n_grp > ring) {                     // (a call of up to four groups never waits: every group has its slot)
-                    if (ce == hipSuccess) ce = hipEventRecord(left[g % ring], ctx->stream);
-                    if (ce == hipSuccess && g >= 1) { ce = hipEventSynchronize(left[(g - 1) % ring]); copied.store(g, std::memory_order_release); }
-                }
-            }
-            copied.store(INT32_MAX, std::memory_order_release);               // (on an error too: no packer may wait for ever)
-            for (std::thread& t : th) t.join();
-            if (ce != hipSuccess) (void) hipStreamSynchronize(ctx->stream);   // copies already issued still read the staging
-            for (hipEvent_t e : left) if (e) (void) hipEventDestroy(e);
-            HIPCHK(ce);
-        }
-        for (int t = 0; t < n_thr; ++t) { max_s5 = std::max(max_s5, t_s5[t]); max_s3 = std::max(max_s3, t_s3[t]); }
-        HIPCHK(hipStreamSynchronize(ctx->stream));          // the staging buffers are the context's: one upload at a time
+                p_s5[i] = m5; p_s3[i] = m3;
+            })) return -1;
+        for (int i = 0; i < n; ++i) { max_s5 = std::max(max_s5, p_s5[i]); max_s3 = std::max(max_s3, p_s3[i]); }
     }
     sc.sigmodel = nullptr;                                   // the caller's model is not ours to keep
     // bounds for the fp32 sweeps (DevRun::build): best substitution score, best net gain of one intron
@@ -403,19 +418,7 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
         fp_gain = (sc.spj && max_s5 > INT32_MIN) ? std::max(0, max_s5 + max_s3 + max_pen) : 0;
     }
     // conserved-intron bonuses of the queries that carry them (SpdpProblem::cip), one row of a_len + 1 ints each
-    cip_off.assign(n, -1);
-    {
-        std::vector<int32_t> hcip;
-        for (int i = 0; i < n; ++i)
-            if (probs[i].cip) {
-                cip_off[i] = (int32_t) hcip.size();
-                hcip.insert(hcip.end(), probs[i].cip, probs[i].cip + probs[i].a_len + 1);
-            }
-        if (!hcip.empty()) {
-            HIPCHK(hipMalloc(&d_cip, hcip.size() * sizeof(int32_t)));
-            HIPCHK(hipMemcpy(d_cip, hcip.data(), hcip.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
+    if (spdp_upload_cip(ctx, n, [&](int i, size_t& len) { len = (size_t) probs[i].a_len + 1; return probs[i].cip; }, cip_off, &d_cip)) return -1;
     DevScoring hsc;
     to_dev_scoring(&sc, &hsc);
     HIPCHK(hipMalloc(&d_sc, sizeof(DevScoring)));

@@ -7,9 +7,7 @@
 #include "spdp_hsp_host.h"
 #include "spdp_region.h"
 #include "spdp_hostcpus.h"
-#include <atomic>
 #include <chrono>
-#include <thread>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -274,19 +272,6 @@ extern "C" int spdp_blk_vote(SpdpContext* ctx, const SpdpBlkIndex* ix, const uin
 // host threads (spdp_hsp_chain.h), the machines advance.
 namespace {
 
-template <class F> void on_threads(int n, F f)
-{
-    std::atomic<int> next{0};
-    std::atomic<bool> failed{false};
-    auto work = [&] { try { for (int k; (k = next++) < n; ) f(k); } catch (...) { failed = true; } };
-    const int nt = std::max(1, std::min(spdp_host_cpus(), n));
-    std::vector<std::thread> th;
-    try { for (int t = 1; t < nt; ++t) th.emplace_back(work); } catch (...) {}      // (fewer threads: the caller's does the rest)
-    work();
-    for (std::thread& t : th) t.join();
-    if (failed) throw std::bad_alloc();
-}
-
 struct SearchTask { int machine, pair; spdp_loci::Region r; std::vector<spdp_hsp::Unit> units; };
 
 struct HspBatch {                                       // what a call's searches share
@@ -378,7 +363,7 @@ struct HspBatch {                                       // what a call's searche
         HIPCHK(hipMemcpyAsync(counts.data(), d_counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(out.data(), d_out.p, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        on_threads(n, [&](int k) {
+        on_host_threads(n, [&](int k) {
             SearchTask& t = tasks[k];
             const int q = query_of[t.machine];
             if (counts[2 * k + 1]) { on_host(t, q); return; }
@@ -445,7 +430,7 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
         std::vector<spdp_loci::Call> mach(m);
         std::vector<int> verdict(m, 0);                 // > 0 loci, 0 go on, -1 ended, -2 record cut / table full
         std::vector<char> live(m, 0);
-        on_threads(m, [&](int k) {
+        on_host_threads(m, [&](int k) {
             const int32_t* rc = rec.data() + (size_t) k * out_cap;
             if (!(rc[2] & SPDP_BLK_REACHED)) { verdict[k] = -1; return; }            // findblock ended before this call
             if (rc[2] & (SPDP_BLK_CUT | SPDP_BLK_TABLE)) { verdict[k] = -2; return; }
@@ -487,7 +472,7 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
             tasks.clear();
             std::vector<SearchTask> more(m);
             std::vector<char> asks(m, 0);
-            on_threads(m, [&](int k) {
+            on_host_threads(m, [&](int k) {
                 if (!live[k] || mach[k].done) return;
                 spdp_loci::Call& c = mach[k];
                 int pi; spdp_loci::Region rg;

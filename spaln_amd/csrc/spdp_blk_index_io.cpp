@@ -195,12 +195,19 @@ extern "C" void spdp_blk_index_host_free(SpdpBlkIndexHost* h) { delete (HostInde
 #include "spdp_internal.h"
 #include "spdp_blk_build.h"
 #include "spdp_hostcpus.h"
-#include <atomic>
 #include <chrono>
 #include <memory>
-#include <thread>
 
 namespace {
+// f(t, lo, hi) for t = 0 .. nt - 1: the words [lo, hi) of slice t of 0 .. n.  Callers keep a partial result per t and reduce them
+// in t order, so their totals do not depend on which thread ran which slice
+template <class F> void on_ranges(int nt, uint32_t n, F f)
+{
+    const uint32_t step = (n + nt - 1) / nt;
+    auto lo = [&](int t) { return (uint32_t) std::min<uint64_t>(n, (uint64_t) t * step); };
+    on_host_threads(nt, [&](int t) { f(t, lo(t), lo(t + 1)); });
+}
+
 // DefBitPat (src/bitpat.cc:47-56): the pairs of spaced patterns `spaln -W -XC<n>` uses for a k-mer weight, leftmost position first
 const char* const kDefBitPat[16] = {
     "", "1", "101", "1011,10011", "101011,1000111", "10100111,100101101", "1010011011,1010100111",
@@ -321,14 +328,8 @@ static SpdpBlkIndexHost* blk_index_build(SpdpContext* ctx, const SpdpGenome* gen
     const uint32_t segn = (uint32_t) blocks, blksz = (uint32_t) G / segn;
     try { h->nblk.assign(tabsize, 0); h->blkp.assign(tabsize, 0); h->wscr.assign(tabsize, 0); } catch (const std::bad_alloc&) { return fail("out of memory for the index tables"); }
     const int nt = std::max(1, std::min(spdp_host_cpus(), (int) (tabsize >> 14)));
-    auto on_ranges = [&](auto f) {
-        std::vector<std::thread> th;
-        const uint32_t step = (tabsize + nt - 1) / nt;
-        for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { f(t, (uint32_t) std::min<uint64_t>(tabsize, (uint64_t) t * step), (uint32_t) std::min<uint64_t>(tabsize, (uint64_t) (t + 1) * step)); });
-        for (std::thread& x : th) x.join();
-    };
     std::vector<uint64_t> part_m(nt, 0);
-    on_ranges([&](int t, uint32_t a, uint32_t b) { uint64_t m = 0; for (uint32_t w = a; w < b; ++w) if (tcount[w]) ++m; part_m[t] = m; });
+    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) { uint64_t m = 0; for (uint32_t w = a; w < b; ++w) if (tcount[w]) ++m; part_m[t] = m; });
     uint64_t m_seen = 0;
     for (uint64_t x : part_m) m_seen += x;
     if (!m_seen) { return fail("no word in the genome"); }
@@ -337,7 +338,7 @@ static SpdpBlkIndexHost* blk_index_build(SpdpContext* ctx, const SpdpGenome* gen
     if (min_scr < 0) min_scr = 0;
     std::vector<double> part_avr(nt, 0.);
     std::vector<uint64_t> part_kept(nt, 0), part_words(nt, 0), part_max(nt, 0), part_over(nt, 0);
-    on_ranges([&](int t, uint32_t a, uint32_t b) {
+    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) {
         double avr = 0.; uint64_t kept = 0, words = 0, mx = 0, over = 0;
         for (uint32_t w = a; w < b; ++w) {
             if (!cnt[w]) { h->wscr[w] = -1; continue; }
@@ -510,15 +511,9 @@ static SpdpBlkIndexHost* blk_index_build_p(SpdpContext* ctx, const SpdpGenome* g
         }
     }
     const int nt = std::max(1, std::min(spdp_host_cpus(), (int) (tabsize >> 14)));
-    auto on_ranges = [&](auto f) {
-        std::vector<std::thread> th;
-        const uint32_t step = (tabsize + nt - 1) / nt;
-        for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { f(t, (uint32_t) std::min<uint64_t>(tabsize, (uint64_t) t * step), (uint32_t) std::min<uint64_t>(tabsize, (uint64_t) (t + 1) * step)); });
-        for (std::thread& x : th) x.join();
-    };
     std::vector<int64_t> part_sum(nt, 0);
     std::vector<uint64_t> part_m(nt, 0);
-    on_ranges([&](int t, uint32_t lo, uint32_t hi) {
+    on_ranges(nt, tabsize, [&](int t, uint32_t lo, uint32_t hi) {
         int64_t sum = 0; uint64_t m = 0;
         for (uint32_t w = lo; w < hi; ++w) {
             if (!tcount[w]) continue;
@@ -538,7 +533,7 @@ static SpdpBlkIndexHost* blk_index_build_p(SpdpContext* ctx, const SpdpGenome* g
     short min_scr = (short) (avr - 100 * (1 + p->aaafact) * log((double) p->b.afact));
     if (min_scr < 0) min_scr = 0;
     std::vector<uint64_t> part_words(nt, 0), part_over(nt, 0);
-    on_ranges([&](int t, uint32_t lo, uint32_t hi) {
+    on_ranges(nt, tabsize, [&](int t, uint32_t lo, uint32_t hi) {
         uint64_t words = 0, ov = 0;
         for (uint32_t w = lo; w < hi; ++w) {
             if (!cnt[w]) { h->wscr[w] = -1; continue; }

@@ -13,8 +13,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "../../include/spdp.h"
@@ -161,39 +159,25 @@ int HStore::upload(SpdpContext* c, const SpdpScoringH* scp, const SpdpProblemH* 
         col_off[i] = c_tot; col_len[i] = probs[i].b_len + 3 + SPDH_COL_PAD; c_tot += col_len[i];
     }
     std::vector<uint8_t> a_all((size_t) a_tot, 0);      // (the byte behind a query reads 0 in the reference process: row a_len, see bad_range)
-    // column records, packed by the host's cores into pinned staging memory the context keeps (one thread and pageable
-    // vectors took 0.18 ms per protein window -- longer than the reference takes to ALIGN the pair on its seeded path)
-    // ... through a ring of four groups' worth of it: a group's slot is packed again once its copy has left (a map + align call of
-    // 20 000 protein loci holds 5 * 10^8 positions -- 12 GB of pinned memory when every group had its own place, two seconds of a
-    // context's first call to allocate)
-    std::vector<int> grp_first, grp_of(n);
-    int64_t slot_cap = 1;
-    {
-        int64_t acc = 0;
-        for (int i = 0; i < n; ++i) {
-            if (i == 0 || acc >= (4 << 20)) { grp_first.push_back(i); acc = 0; }
-            grp_of[i] = (int) grp_first.size() - 1;
-            acc += col_len[i];
-            slot_cap = std::max(slot_cap, acc);
-        }
+    for (int i = 0; i < n; ++i) memcpy(a_all.data() + a_off[i], probs[i].a, probs[i].a_len);
+    if (n) {
+        d_cols = pool.get(HP_COLS, (size_t) c_tot * sizeof(int4));
+        d_aux = pool.get(HP_AUX, (size_t) c_tot * sizeof(short4));
+        if (!d_cols || !d_aux) { ctx->err = "device allocation failed (aa x genome inputs)"; return -1; }
     }
-    const int RING_SLOTS = (getenv("SPDP_UPLOAD_RING") && atoi(getenv("SPDP_UPLOAD_RING")) == 0) ? std::max<int>(1, (int) grp_first.size()) : 4;     // (0: every group its own place, as before round 6)
-    int4* cols = dev_sig ? nullptr : (int4*) ctx->staging(0, (size_t) slot_cap * RING_SLOTS * sizeof(int4));
-    short4* aux = dev_sig ? nullptr : (short4*) ctx->staging(1, (size_t) slot_cap * RING_SLOTS * sizeof(short4));
-    if (!dev_sig && (!cols || !aux)) { ctx->err = "out of pinned host memory"; return -1; }
-    auto stage_of = [&](int i) -> int64_t {             // where problem i's records lie in the staging ring
-        const int g = grp_of[i];
-        return (int64_t) (g % RING_SLOTS) * slot_cap + (col_off[i] - col_off[grp_first[g]]);
-    };
-    auto pack_one = [&](int i) {
+    // column records (layout: spdp_h_dev.h), packed by the host's cores into pinned staging memory the context keeps (one thread and
+    // pageable vectors took 0.18 ms per protein window -- longer than the reference takes to ALIGN the pair on its seeded path), and
+    // copied in groups of ~4 M positions (a map + align call of 20 000 protein loci holds 5 * 10^8 positions: 12 GB of pinned memory
+    // when every group had its own place, two seconds of a context's first call to allocate)
+    std::vector<StagedStream> st = {{0, d_cols, sizeof(int4)}, {1, d_aux, sizeof(short4)}};
+    auto pack_one = [&](int i, int64_t at) {
         const SpdpProblemH& p = probs[i];
-        memcpy(a_all.data() + a_off[i], p.a, p.a_len);
-        if (dev_sig) return;
-        // column records (layout: spdp_h_dev.h); positions beyond the inputs read as zero
+        int4* cols = (int4*) st[0].host + at;
+        short4* aux = (short4*) st[1].host + at;
+        // positions beyond the inputs read as zero
         const int N = p.b_len + 3;
         auto good = [&](int x) { return p.exin_left - 1 <= x && x < p.exin_right; };
         auto s16at = [&](const int16_t* v, int x) -> int { return (x >= 0 && x < N) ? v[x] : 0; };
-        const size_t c0 = (size_t) stage_of(i);
         for (int x = 0; x < N; ++x) {
             const int cp = (x - 2 >= 0 && good(x - 2)) ? p.sigE[x - 2] : 0;
             const int tron = (x - 2 >= 0 && x - 2 <= p.b_len) ? p.b[x - 2] : 0;
@@ -218,61 +202,12 @@ int HStore::upload(SpdpContext* c, const SpdpScoringH* scp, const SpdpProblemH* 
             rec.y = (int) ((unsigned) (uint16_t) (int16_t) s3_0 | ((unsigned) (uint16_t) (int16_t) s3_1 << 16));
             rec.z = (int) ((unsigned) (uint16_t) (int16_t) s5_0 | ((unsigned) (uint16_t) (int16_t) s5_1 << 16));
             rec.w = (p.dinc && x <= p.b_len) ? (int) p.dinc[x] : 0;     // b_len + 1 entries
-            cols[c0 + x] = rec;
-            aux[c0 + x] = make_short4(p.sigS[x], p.sigT[x], p.sigE[x], p.sig5[x]);
+            cols[x] = rec;
+            aux[x] = make_short4(p.sigS[x], p.sigT[x], p.sigE[x], p.sig5[x]);
         }
-        for (int x = N; x < col_len[i]; ++x) { cols[c0 + x] = make_int4(0, 0, 0, 0); aux[c0 + x] = make_short4(0, 0, 0, 0); }
+        for (int x = N; x < col_len[i]; ++x) { cols[x] = make_int4(0, 0, 0, 0); aux[x] = make_short4(0, 0, 0, 0); }
     };
-    if (n && !dev_sig) {
-        d_cols = pool.get(HP_COLS, (size_t) c_tot * sizeof(int4));
-        d_aux = pool.get(HP_AUX, (size_t) c_tot * sizeof(short4));
-        if (!d_cols || !d_aux) { ctx->err = "device allocation failed (aa x genome inputs)"; return -1; }
-    }
-    {
-        int n_thr = spdp_host_cpus();
-        if (const char* e = getenv("SPDP_UPLOAD_THREADS")) n_thr = atoi(e);
-        n_thr = std::max(1, std::min(std::min(n_thr, 32), n));
-        // the copy of a group of problems (~4 M positions) starts as soon as the group is packed, under the packing of the next ones;
-        // a packer that reaches a group whose slot still holds an earlier group waits for that group's copy
-        const int n_grp = (int) grp_first.size();
-        std::vector<std::atomic<int>> grp_done(std::max(1, n_grp));
-        for (auto& g : grp_done) g.store(0);
-        std::atomic<int> next_prob{0};
-        std::atomic<int> copied{0};                     // groups whose copy has left the staging (or: give up, INT_MAX)
-        auto pack = [&]() {
-            for (;;) {
-                const int i = next_prob.fetch_add(1);
-                if (i >= n) break;
-                if (!dev_sig) while (copied.load(std::memory_order_acquire) < grp_of[i] - RING_SLOTS + 1) std::this_thread::yield();
-                pack_one(i);
-                grp_done[grp_of[i]].fetch_add(1, std::memory_order_release);
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_thr; ++t) th.emplace_back(pack);
-        hipError_t ce = hipSuccess;
-        std::vector<hipEvent_t> left((size_t) RING_SLOTS, nullptr);
-        for (int k = 0; k < RING_SLOTS && !dev_sig && ce == hipSuccess; ++k) ce = hipEventCreateWithFlags(&left[k], hipEventDisableTiming);
-        int synced = 0;                                 // groups known to have left
-        for (int g = 0; g < n_grp && !dev_sig && ce == hipSuccess; ++g) {
-            const int first = grp_first[g], last = g + 1 < n_grp ? grp_first[g + 1] : n;
-            while (grp_done[g].load(std::memory_order_acquire) < last - first) std::this_thread::yield();
-            const int64_t c0 = col_off[first], c1 = last < n ? col_off[last] : c_tot;
-            const int64_t s0 = (int64_t) (g % RING_SLOTS) * slot_cap;
-            ce = hipMemcpyAsync((int4*) d_cols + c0, cols + s0, (size_t) (c1 - c0) * sizeof(int4), hipMemcpyHostToDevice, ctx->stream);
-            if (ce == hipSuccess)
-                ce = hipMemcpyAsync((short4*) d_aux + c0, aux + s0, (size_t) (c1 - c0) * sizeof(short4), hipMemcpyHostToDevice, ctx->stream);
-            if (ce == hipSuccess) ce = hipEventRecord(left[g % RING_SLOTS], ctx->stream);
-            // the packers may be two groups ahead of the copies: the group before this one has to have left before the next is issued
-            if (ce == hipSuccess && g >= 1) { ce = hipEventSynchronize(left[(g - 1) % RING_SLOTS]); synced = g; copied.store(g, std::memory_order_release); }
-        }
-        (void) synced;
-        copied.store(INT32_MAX, std::memory_order_release);                  // (on an error too: no packer may wait for ever)
-        for (std::thread& t : th) t.join();
-        if (!dev_sig) (void) hipStreamSynchronize(ctx->stream);              // the last copies still read the staging
-        for (int k = 0; k < RING_SLOTS; ++k) if (left[k]) (void) hipEventDestroy(left[k]);
-        HIPCHK(ce);
-    }
+    if (!dev_sig && spdp_upload_ring(ctx, col_off, c_tot, 4 << 20, st, pack_one)) return -1;
     scalar_ok = sc.intpen && sc.intpen_len > 0;
     for (int i = 0; i < n && !dev_sig; ++i) if (!probs[i].dinc) scalar_ok = false;      // (device-made signals bring dinc along)
     // double affine gaps (PwdB::Noll = 3, -yl3): built for the -A0 engines (forwardH_ng / hirschbergH_ng, spdh_rowwave<., ., ., true>);
@@ -292,25 +227,9 @@ int HStore::upload(SpdpContext* c, const SpdpScoringH* scp, const SpdpProblemH* 
         if (ipen_runs_ok)
             HIPCHK(hipMemcpy((int16_t*) d_intpen + sc.intpen_len, runs.data(), runs.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     }
-    cip_off.assign(n, -1);
-    {
-        std::vector<int32_t> hcip;
-        for (int i = 0; i < n; ++i)
-            if (probs[i].cip) {
-                cip_off[i] = (int32_t) hcip.size();
-                hcip.insert(hcip.end(), probs[i].cip, probs[i].cip + 3 * probs[i].a_len + 2);
-            }
-        if (!hcip.empty()) {
-            HIPCHK(hipMalloc(&d_cip, hcip.size() * sizeof(int32_t)));
-            HIPCHK(hipMemcpy(d_cip, hcip.data(), hcip.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
+    if (spdp_upload_cip(ctx, n, [&](int i, size_t& len) { len = 3 * (size_t) probs[i].a_len + 2; return probs[i].cip; }, cip_off, &d_cip)) return -1;
     d_sc = pool.get(HP_SC, sizeof ds);
     d_a = pool.get(HP_A, a_all.size() + 16);
-    if (dev_sig) {
-        d_cols = pool.get(HP_COLS, (size_t) c_tot * sizeof(int4));
-        d_aux = pool.get(HP_AUX, (size_t) c_tot * sizeof(short4));
-    }
     if (!d_sc || !d_a || !d_cols || !d_aux) { ctx->err = "device allocation failed (aa x genome inputs)"; return -1; }
     HIPCHK(hipMemcpyAsync(d_sc, &ds, sizeof ds, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_a, a_all.data(), a_all.size(), hipMemcpyHostToDevice, ctx->stream));

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include "../../include/spdp.h"
@@ -267,6 +268,25 @@ struct SpdpContext {
     void*  staging(int k, size_t bytes);
 };
 SpdpContext* spdp_lane(SpdpContext* ctx, int i);
+
+// Column records of problems 0 .. off.size() - 1 to the device through the context's pinned staging (spdp_api.cpp).  Problem i
+// holds positions off[i] .. off[i + 1] (tot after the last) of every stream.  The problems are cut into groups of at least
+// grp_positions positions, and the groups go through a ring of four slots of the staging: a group is copied as soon as its problems
+// are packed, and its slot is packed again once that copy has left.  pack(i, at) fills problem i's records at position `at` of every
+// stream's staging (StagedStream::host); it runs once per problem, on threads the function starts.  Returns once the copies are
+// done (the staging is the context's): 0, or -1 with ctx->err set.
+struct StagedStream {
+    int    slot;                // SpdpContext::staging slot
+    void*  dev;                 // position p's record at dev + p * bytes
+    size_t bytes;               // per position
+    void*  host = nullptr;      // set before the first pack(): the slot's memory
+};
+int spdp_upload_ring(SpdpContext* ctx, const std::vector<int64_t>& off, int64_t tot, int64_t grp_positions,
+                     std::vector<StagedStream>& st, const std::function<void(int i, int64_t at)>& pack);
+// conserved-intron bonus rows (SpdpProblem::cip, SpdpProblemH::cip) to one device array *d (hipMalloc, the caller frees it):
+// row(i, len) is problem i's row of len ints, or null; off[i] = where it starts in *d, -1 = none.  Returns 0, or -1 with ctx->err set
+int spdp_upload_cip(SpdpContext* ctx, int n, const std::function<const int32_t*(int i, size_t& len)>& row, std::vector<int32_t>& off,
+                    void** d);
 
 // Resident inputs of a set of parent problems: residues, per-position column
 // records and the scoring bundle.  Sub-problems (UDH slabs, engine calls on

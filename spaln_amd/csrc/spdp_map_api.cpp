@@ -8,13 +8,11 @@
 #include "spdp_region.h"
 #include "spdp_hostcpus.h"
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <thread>
 #include <vector>
 
 int spdh_signals_run(SpdpContext* ctx, const SpdpSignalModelH* m, const std::vector<SigJobH>& jobs, SignalArgsH args, int pack);   // spdp_signals_api.cpp
@@ -36,17 +34,6 @@ inline uint8_t other_strand(uint8_t c)   // A 2 <-> T 9, C 3 <-> G 5; ambiguity 
 double since(std::chrono::steady_clock::time_point t)
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
-
-template <class F> void on_host_threads(int n, F f)
-{
-    std::atomic<int> next{0};
-    auto work = [&] { for (int k; (k = next++) < n; ) f(k); };
-    const int nt = std::max(1, std::min(spdp_host_cpus(), n));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(work);
-    work();
-    for (std::thread& t : th) t.join();
 }
 
 }  // namespace

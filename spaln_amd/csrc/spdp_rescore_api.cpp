@@ -12,8 +12,6 @@
 #include "spdp_dev.h"
 #include "spdp_internal.h"
 #include "spdp_hostcpus.h"
-#include <thread>
-#include <atomic>
 #include "spdp_gencode.h"
 
 #define HIPCHK(call)                                                                     \
@@ -261,31 +259,21 @@ static int rescore_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpRescore
     uint8_t* const b_p = misc_p ? misc_p : b_all.data();
     int8_t* const phs_p = misc_p ? (int8_t*) (misc_p + b_tot) : phs.data();
     uint8_t* const dinc_p = misc_p ? misc_p + b_tot + 2 * col_tot : dinc.data();
-    {
-        std::atomic<int> next{0};
-        auto work = [&] {
-            for (int s; (s = next++) < (int) idx.size(); ) {
-                const SpdpProblemH& p = probs[idx[s]];
-                const HRescoreProb& d = descs[s];
-                memcpy(a_all.data() + d.a_off, p.a, (size_t) p.a_len);
-                uint8_t* bb = b_p + d.b_off;
-                short* sg = sig_p + 5 * d.col_off; int8_t* ph = phs_p + 2 * d.col_off; uint8_t* dc = dinc_p + d.col_off;
-                for (int x = d.w_lo; x < d.w_hi; ++x) {
-                    const int o = x - d.w_lo;
-                    bb[o] = x <= p.b_len ? p.b[x] : 0;
-                    sg[5 * o] = p.sig5[x]; sg[5 * o + 1] = p.sig3[x]; sg[5 * o + 2] = p.sigS[x]; sg[5 * o + 3] = p.sigT[x]; sg[5 * o + 4] = p.sigE[x];
-                    ph[2 * o] = p.phs5[x]; ph[2 * o + 1] = p.phs3[x];
-                    dc[o] = x <= p.b_len ? p.dinc[x] : 0;
-                }
-                memcpy(skl.data() + soff[s], aln[idx[s]].skl + 1, sizeof(SpdpSkl) * (size_t) scnt[s]);
-            }
-        };
-        const int nt = std::max(1, std::min(spdp_host_cpus(), (int) idx.size()));
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(work);
-        work();
-        for (std::thread& t : th) t.join();
-    }
+    on_host_threads((int) idx.size(), [&](int s) {
+        const SpdpProblemH& p = probs[idx[s]];
+        const HRescoreProb& d = descs[s];
+        memcpy(a_all.data() + d.a_off, p.a, (size_t) p.a_len);
+        uint8_t* bb = b_p + d.b_off;
+        short* sg = sig_p + 5 * d.col_off; int8_t* ph = phs_p + 2 * d.col_off; uint8_t* dc = dinc_p + d.col_off;
+        for (int x = d.w_lo; x < d.w_hi; ++x) {
+            const int o = x - d.w_lo;
+            bb[o] = x <= p.b_len ? p.b[x] : 0;
+            sg[5 * o] = p.sig5[x]; sg[5 * o + 1] = p.sig3[x]; sg[5 * o + 2] = p.sigS[x]; sg[5 * o + 3] = p.sigT[x]; sg[5 * o + 4] = p.sigE[x];
+            ph[2 * o] = p.phs5[x]; ph[2 * o + 1] = p.phs3[x];
+            dc[o] = x <= p.b_len ? p.dinc[x] : 0;
+        }
+        memcpy(skl.data() + soff[s], aln[idx[s]].skl + 1, sizeof(SpdpSkl) * (size_t) scnt[s]);
+    });
     const int nr = (int) idx.size();
     if (!nr) return 0;
     std::vector<int> mtx(32 * 32, 0);

@@ -23,7 +23,7 @@ def _oracle_align(item):
 
 def test_c2_fullsize_batch():
     from spaln_amd import abi, defaults, engine, synth
-    n_q = 1500
+    n_q = 4000                                       # ~4000 x 12.4 kb = 49 M positions: 6 upload groups of 8 Mi, slots reused
     batch = synth.make_batch(n_q, seed=synth.SEED + 77)
     sc = defaults.scoring()
     ps = abi.ProblemSet()

@@ -28,7 +28,7 @@ def _oracle_align_h(item):
 
 def test_c3_fullsize_batch():
     from spaln_amd import abi, defaults, engine, synth
-    n_q = 768
+    n_q = 2500                                       # ~2500 x 8.2 kb = 20.5 M positions: 5 upload groups of 4 Mi, a slot reused
     batch = synth.make_protein_batch(n_q, seed=synth.SEED + 4077)
     sc = defaults.scoring_h()
     ps = abi.ProblemSetH()
