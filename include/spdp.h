@@ -961,6 +961,41 @@ int spdp_map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkInde
                      const uint8_t* codes, const int64_t* offs, int32_t n,
                      SpdpMapGene* genes, SpdpMapExon** exons, double* seconds);
 
+/* Every locus `spaln -M N[.M]` prints of a query, not only the best one: paralogs, multi-copy families, segmental duplications.
+ * The same chain as spdp_map_align_s / _h (the same device work: the loci aligned are the same ones, at most max_out2 per query),
+ * then blkaln's selection (src/spaln.cc:913-976) in place of the best locus:
+ *   - a locus is dropped (not counted) when its walk gave no alignment, or -- unless all_out (-pw, OutPrm.all_out) -- when its
+ *     score (skl_rng's return value, SpdpMapGene.score) is <= sp->vthr (PwdB::Vthr, what -H sets);
+ *   - ALL loci of the query, the dropped ones too, are ordered by fstat.val, highest first, ties in the block search's order
+ *     (the reference's insertion sort; a locus without an alignment counts as val 0);
+ *   - the first min(n_out, max_out) positions of that order are reported, n_out = the loci not dropped, and of those the ones
+ *     without an alignment are skipped.  A locus dropped by the threshold thus keeps its place: it is reported when it lands in
+ *     one of those positions, and it can take the place of a kept one; its SpdpMapGene.score is then SPDP_NEVSEL (blkaln
+ *     has set Gsinfo::scr so; -O4 prints it in the summary line).
+ * MaxOut = fprm->max_out (>= 1; fprm->max_out2 >= max_out: spaln -M N.M sets MaxOut = N, MaxOut2 = max(M, N), M = 4 when not
+ * given, and -M alone is -M4.4).  The index must have been made for the same MaxOut: its queues hold Ncand = max_out + 10
+ * candidates (SpdpBlkSearchOpts.max_out; src/blksrc.cc:2220); hix->ncand != fprm->max_out + 10 is refused, as are max_out < 1
+ * and max_out2 < max_out.  The vote keeps those queues in LDS, about 100 B per candidate (the queue and its position hash of
+ * dhash_size(2 Ncand) slots: 4 (2 (Ncand + 1) + 2 dhash_size(2 Ncand)) words; spdp_blk_index_create refuses more than 64 KB a query): with the default Nascr (2) max_out <= 423 fits any index (499 when the run hash lies in HBM, as it does beyond 8 KB;
+ * SPDP_BLK_HH_LDS moving a larger one into LDS lowers the bound).
+ * Out: gene_off[n + 1] (the caller's; query i reports (*genes)[gene_off[i] .. gene_off[i + 1]), in print order), *genes and
+ * *exons malloc'ed (free() both; SpdpMapGene.exon_off indexes *exons; n_loci = the query's loci that were aligned).  The return
+ * value as spdp_map_align_s.  ori = 3: every locus picks its orientation on its own, as in spdp_map_align_s.  The program
+ * differs there: when a locus aligned with the query reverse-complemented, alignS_ng leaves the query so (src/fwd2s1.cc:2766-2777)
+ * and the query's further loci are aligned in that state with the HSPs found for the other one; their alignments (mostly poor
+ * ones) are not reproduced.  algmode.mlt = 2, which -M N > 1 also sets, changes nothing else on this path: its readers are the
+ * unspliced aligner, Wilip outside algmode.lsg and the gene-range sort of -O12. */
+int spdp_map_align_s_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                           const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, int32_t all_out,
+                           int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds);
+int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                           const struct SpdpScoringH* sc, const SpdpSeedParams* sp, const struct SpdpSignalModelH* sigmodel,
+                           const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
+                           const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                           int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds);
+
 /* ---- device groups, continued ------------------------------------------------------------------------------------------ */
 /* the same sharding for the calls of the seeded path, rescoring and the block vote (rounds 3 / 4).  The HSP source of a
  * seeded call is asked with the CALLER's query numbers, from the worker threads of every member.  spdp_group_blk_vote takes
@@ -985,6 +1020,23 @@ int spdp_group_map_align_s(SpdpGroup* g, const SpdpBlkIndex* const* ix, const Sp
                            const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
                            const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
                            SpdpMapGene* genes, SpdpMapExon** exons);
+/* the same for protein queries (spdp_map_align_h; one translated index per member) */
+int spdp_group_map_align_h(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                           const struct SpdpScoringH* sc, const SpdpSeedParams* sp, const struct SpdpSignalModelH* sigmodel,
+                           const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
+                           const uint8_t* codes, const int64_t* offs, int32_t n,
+                           SpdpMapGene* genes, SpdpMapExon** exons);
+/* spdp_map_align_s_multi / _h_multi, sharded the same way; gene_off, *genes and *exons in the caller's query order */
+int spdp_group_map_align_s_multi(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                 const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                 const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, int32_t all_out,
+                                 int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons);
+int spdp_group_map_align_h_multi(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                 const struct SpdpScoringH* sc, const SpdpSeedParams* sp, const struct SpdpSignalModelH* sigmodel,
+                                 const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
+                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                                 int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons);
 
 #ifdef __cplusplus
 }

@@ -414,3 +414,62 @@ def map_align_h(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, pr
     libc.free.argtypes = [C.c_void_p]
     libc.free(exons)
     return out, list(sec), rc
+
+
+def _multi_call(index: "BlockIndex", fn: str, genome_codes, chr_off, args_before, queries, args_after):
+    """the call of a _multi entry and its lists: (per query a list of dicts shaped as map_align's, in print order), seconds, rc"""
+    lib, eng = index.lib, index.eng
+    n = len(queries)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([len(q) for q in queries])
+    codes = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
+    g = Genome()
+    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+    go = np.ascontiguousarray(chr_off, dtype=np.int64)
+    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
+    gene_off = np.zeros(n + 1, dtype=np.int64)
+    genes = C.POINTER(MapGene)()
+    exons = C.POINTER(MapExon)()
+    sec = (C.c_double * 4)()
+    f = getattr(lib, fn)
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] * 11 + [C.c_int32] * (1 + len(args_after)) + [C.c_void_p] * 4
+    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), *args_before, codes.ctypes.data, offs.ctypes.data, n, *args_after,
+           gene_off.ctypes.data, C.byref(genes), C.byref(exons), sec)
+    if rc < 0:
+        eng._check(rc, fn)
+    out = []
+    for i in range(n):
+        lst = []
+        for k in range(int(gene_off[i]), int(gene_off[i + 1])):
+            G = genes[k]
+            ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
+                  for j in range(G.n_exons)]
+            lst.append(dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex))
+        out.append(lst)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(genes)
+    libc.free(exons)
+    return out, list(sec), rc
+
+
+def map_align_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1,
+                    all_out: bool = False):
+    """spdp_map_align_s_multi: what `spaln -M N` prints of every query -- up to prm.max_out loci, highest fstat.val first, the
+    threshold sp.vthr applied unless all_out (-pw); a locus printed though the threshold dropped it has score abi.NEVSEL.  The
+    index must have been made for prm.max_out (ncand = max_out + 10).  ori = 3: every locus picks its orientation on its own; the
+    program aligns a query's further loci with the query left reverse-complemented after a locus that took that orientation, so
+    such a query's later loci can differ from spaln's (include/spdp.h).
+    Returns (per query a list of dicts shaped as map_align's, in print order; seconds; return code)."""
+    from . import abi
+    rp = abi.RescoreParams(*(int(x) for x in rescore))
+    return _multi_call(index, "spdp_map_align_s_multi", genome_codes, chr_off,
+                       (C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp)), queries, (int(ori), int(bool(all_out))))
+
+
+def map_align_h_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries,
+                      all_out: bool = False):
+    """spdp_map_align_h_multi: the same for protein queries against the translated index (arguments as map_align_h's)"""
+    return _multi_call(index, "spdp_map_align_h_multi", genome_codes, chr_off,
+                       (C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rescore)), queries, (int(bool(all_out)),))

@@ -291,30 +291,49 @@ int spdp_group_blk_vote(SpdpGroup* g, const SpdpBlkIndex* const* ix, const uint8
     });
 }
 
-int spdp_group_map_align_s(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                           const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                           SpdpMapGene* genes, SpdpMapExon** exons)
+// map + align with the queries sharded over the members by length.  call(ctx, member, codes, offs, cnt, ...) runs one member's
+// shard: its queries' codes gathered in caller order, renumbered 0 .. cnt - 1
+extern "C++" {
+namespace {
+struct Shard {                          // a member's queries, gathered
+    std::vector<int64_t> offs;
+    std::vector<uint8_t> codes;
+    Shard(const std::vector<int>& idx, const uint8_t* codes_, const int64_t* offs_) : offs(idx.size() + 1, 0)
+    {
+        const size_t cnt = idx.size();
+        for (size_t k = 0; k < cnt; ++k) offs[k + 1] = offs[k] + (offs_[idx[k] + 1] - offs_[idx[k]]);
+        codes.resize((size_t) offs[cnt]);
+        for (size_t k = 0; k < cnt; ++k) memcpy(codes.data() + offs[k], codes_ + offs_[idx[k]], (size_t) (offs[k + 1] - offs[k]));
+    }
+};
+int member_of(const SpdpGroup* g, const SpdpContext* c)
 {
-    if (!ix || !codes || !offs || !genes || !exons) { if (g) g->err = "spdp_group_map_align_s: null argument"; return -1; }
-    *exons = nullptr;
+    int member = 0;
+    while (g->ctx[member] != c) ++member;
+    return member;
+}
+std::vector<int64_t> query_costs(const int64_t* offs, int n)
+{
     std::vector<int64_t> cost(std::max(n, 0));
     for (int i = 0; i < n; ++i) cost[i] = 1 + offs[i + 1] - offs[i];
+    return cost;
+}
+
+// one gene per query (spdp_map_align_s / _h): genes[n] of the caller; *exons malloc'ed, a member's exons in one run
+template <typename CALL>
+int group_map_best(SpdpGroup* g, const char* who, const uint8_t* codes, const int64_t* offs, int32_t n,
+                   SpdpMapGene* genes, SpdpMapExon** exons, CALL&& call)
+{
     const int w = g ? (int) g->ctx.size() : 0;
     std::vector<std::vector<SpdpMapExon>> part(std::max(w, 1));        // a member's exons, its genes' exon_off relative to them
     std::vector<std::vector<int>> whose(std::max(w, 1));
-    const int rc = fan_out_idx(g, n, cost, [&](SpdpContext* c, const std::vector<int>& idx) {
-        int member = 0;
-        while (g->ctx[member] != c) ++member;
+    const int rc = fan_out_idx(g, n, query_costs(offs, n), [&](SpdpContext* c, const std::vector<int>& idx) {
+        const int member = member_of(g, c);
         const int cnt = (int) idx.size();
-        std::vector<int64_t> o2(cnt + 1, 0);
-        for (int k = 0; k < cnt; ++k) o2[k + 1] = o2[k] + (offs[idx[k] + 1] - offs[idx[k]]);
-        std::vector<uint8_t> cd((size_t) o2[cnt]);
-        for (int k = 0; k < cnt; ++k) memcpy(cd.data() + o2[k], codes + offs[idx[k]], (size_t) (o2[k + 1] - o2[k]));
+        Shard sh(idx, codes, offs);
         std::vector<SpdpMapGene> gn(cnt);
         SpdpMapExon* ex = nullptr;
-        const int r = spdp_map_align_s(c, ix[member], hix, genome, sc, sp, sigmodel, fprm, rp, cd.data(), o2.data(), cnt, ori, gn.data(), &ex, nullptr);
+        const int r = call(c, member, sh.codes.data(), sh.offs.data(), cnt, gn.data(), &ex);
         if (r >= 0) {
             size_t ne = 0;
             for (int k = 0; k < cnt; ++k) { genes[idx[k]] = gn[k]; ne = std::max<size_t>(ne, (size_t) gn[k].exon_off + gn[k].n_exons); }
@@ -328,7 +347,7 @@ int spdp_group_map_align_s(SpdpGroup* g, const SpdpBlkIndex* const* ix, const Sp
     size_t total = 0;
     for (int r = 0; r < w; ++r) total += part[r].size();
     *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(total, 1));
-    if (!*exons) { g->err = "spdp_group_map_align_s: out of memory"; return -1; }
+    if (!*exons) { g->err = std::string(who) + ": out of memory"; return -1; }
     size_t base = 0;
     for (int r = 0; r < w; ++r) {
         if (!part[r].empty()) memcpy(*exons + base, part[r].data(), sizeof(SpdpMapExon) * part[r].size());
@@ -336,6 +355,120 @@ int spdp_group_map_align_s(SpdpGroup* g, const SpdpBlkIndex* const* ix, const Sp
         base += part[r].size();
     }
     return rc;
+}
+
+// lists of genes per query (the _multi entries): gene_off[n + 1] of the caller, *genes and *exons malloc'ed, both in the
+// caller's query order
+template <typename CALL>
+int group_map_multi(SpdpGroup* g, const char* who, const uint8_t* codes, const int64_t* offs, int32_t n,
+                    int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, CALL&& call)
+{
+    const int w = g ? (int) g->ctx.size() : 0;
+    struct Part { std::vector<int64_t> off; std::vector<SpdpMapGene> gn; std::vector<SpdpMapExon> ex; };
+    std::vector<Part> part(std::max(w, 1));
+    std::vector<std::pair<int, int>> at(std::max(n, 0), {-1, 0});     // query -> (member, its number there)
+    const int rc = fan_out_idx(g, n, query_costs(offs, n), [&](SpdpContext* c, const std::vector<int>& idx) {
+        const int member = member_of(g, c);
+        const int cnt = (int) idx.size();
+        Shard sh(idx, codes, offs);
+        Part& P = part[member];
+        P.off.assign(cnt + 1, 0);
+        SpdpMapGene* gn = nullptr;
+        SpdpMapExon* ex = nullptr;
+        const int r = call(c, member, sh.codes.data(), sh.offs.data(), cnt, P.off.data(), &gn, &ex);
+        if (r >= 0) {
+            size_t ne = 0;
+            for (int64_t j = 0; j < P.off[cnt]; ++j) ne = std::max<size_t>(ne, (size_t) gn[j].exon_off + gn[j].n_exons);
+            P.gn.assign(gn, gn + P.off[cnt]);
+            P.ex.assign(ex, ex + ne);
+            for (int k = 0; k < cnt; ++k) at[idx[k]] = {member, k};
+        }
+        free(gn); free(ex);
+        return r;
+    });
+    if (rc < 0) return rc;
+    size_t ng = 0, ne = 0;
+    for (int r = 0; r < w; ++r) { ng += part[r].gn.size(); ne += part[r].ex.size(); }
+    *genes = (SpdpMapGene*) malloc(sizeof(SpdpMapGene) * std::max<size_t>(ng, 1));
+    *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
+    if (!*genes || !*exons) {
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
+        g->err = std::string(who) + ": out of memory"; return -1;
+    }
+    int64_t k = 0, o = 0;
+    gene_off[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        if (at[i].first >= 0) {
+            const Part& P = part[at[i].first];
+            for (int64_t j = P.off[at[i].second]; j < P.off[at[i].second + 1]; ++j, ++k) {
+                SpdpMapGene G = P.gn[j];
+                if (G.n_exons > 0) memcpy(*exons + o, P.ex.data() + G.exon_off, sizeof(SpdpMapExon) * G.n_exons);
+                G.exon_off = o;
+                o += G.n_exons;
+                (*genes)[k] = G;
+            }
+        }
+        gene_off[i + 1] = k;
+    }
+    return rc;
+}
+}   // namespace
+}   // extern "C++"
+
+int spdp_group_map_align_s(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                           const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
+                           SpdpMapGene* genes, SpdpMapExon** exons)
+{
+    if (!ix || !codes || !offs || !genes || !exons) { if (g) g->err = "spdp_group_map_align_s: null argument"; return -1; }
+    *exons = nullptr;
+    return group_map_best(g, "spdp_group_map_align_s", codes, offs, n, genes, exons,
+                          [&](SpdpContext* c, int member, const uint8_t* cd, const int64_t* o2, int cnt, SpdpMapGene* gn, SpdpMapExon** ex) {
+        return spdp_map_align_s(c, ix[member], hix, genome, sc, sp, sigmodel, fprm, rp, cd, o2, cnt, ori, gn, ex, nullptr);
+    });
+}
+
+int spdp_group_map_align_h(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                           const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
+                           const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+                           const uint8_t* codes, const int64_t* offs, int32_t n,
+                           SpdpMapGene* genes, SpdpMapExon** exons)
+{
+    if (!ix || !codes || !offs || !genes || !exons) { if (g) g->err = "spdp_group_map_align_h: null argument"; return -1; }
+    *exons = nullptr;
+    return group_map_best(g, "spdp_group_map_align_h", codes, offs, n, genes, exons,
+                          [&](SpdpContext* c, int member, const uint8_t* cd, const int64_t* o2, int cnt, SpdpMapGene* gn, SpdpMapExon** ex) {
+        return spdp_map_align_h(c, ix[member], hix, genome, sc, sp, sigmodel, fprm, rp, cd, o2, cnt, gn, ex, nullptr);
+    });
+}
+
+int spdp_group_map_align_s_multi(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                 const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                 const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, int32_t all_out,
+                                 int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons)
+{
+    if (!ix || !codes || !offs || !gene_off || !genes || !exons) { if (g) g->err = "spdp_group_map_align_s_multi: null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr;
+    return group_map_multi(g, "spdp_group_map_align_s_multi", codes, offs, n, gene_off, genes, exons,
+                           [&](SpdpContext* c, int member, const uint8_t* cd, const int64_t* o2, int cnt, int64_t* go, SpdpMapGene** gn, SpdpMapExon** ex) {
+        return spdp_map_align_s_multi(c, ix[member], hix, genome, sc, sp, sigmodel, fprm, rp, cd, o2, cnt, ori, all_out, go, gn, ex, nullptr);
+    });
+}
+
+int spdp_group_map_align_h_multi(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                 const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
+                                 const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                                 int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons)
+{
+    if (!ix || !codes || !offs || !gene_off || !genes || !exons) { if (g) g->err = "spdp_group_map_align_h_multi: null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr;
+    return group_map_multi(g, "spdp_group_map_align_h_multi", codes, offs, n, gene_off, genes, exons,
+                           [&](SpdpContext* c, int member, const uint8_t* cd, const int64_t* o2, int cnt, int64_t* go, SpdpMapGene** gn, SpdpMapExon** ex) {
+        return spdp_map_align_h_multi(c, ix[member], hix, genome, sc, sp, sigmodel, fprm, rp, cd, o2, cnt, all_out, go, gn, ex, nullptr);
+    });
 }
 
 // which member ran problem i in the last group call (cost-balanced: spdp_cells per problem, longest first)

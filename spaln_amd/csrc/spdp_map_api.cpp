@@ -3,6 +3,10 @@
 // per-query driver does around alignS_ng when the genome is searched (src/spaln.cc:880-1010: blkaln / spalign2, genomicseq at
 // :913 reading the region and building its Exinon), batched: all loci of a chunk of queries share one signal launch, one
 // seeded call and one rescoring call.  Host code only; the device work is that of the entries it calls.
+//
+// One chain serves two outputs: the best locus of a query (spdp_map_align_s / _h) and the list of loci spaln -M prints
+// (spdp_map_align_s_multi / _h_multi, blkaln's selection at src/spaln.cc:913-976).  The chain hands every candidate locus,
+// aligned and rescored, to a sink in the block search's order; the two selections are sinks.
 #include "spdp_internal.h"
 #include "spdp_h_internal.h"
 #include "spdp_region.h"
@@ -12,7 +16,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
+#include <numeric>
 #include <vector>
 
 int spdh_signals_run(SpdpContext* ctx, const SpdpSignalModelH* m, const std::vector<SigJobH>& jobs, SignalArgsH args, int pack);   // spdp_signals_api.cpp
@@ -36,23 +42,159 @@ double since(std::chrono::steady_clock::time_point t)
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
 }
 
+// one candidate locus after the walk and rescoring: what blkaln's Gsinfo of that locus holds when its loop is done
+struct LocusOut {
+    bool aligned;                    // the walk gave a skeleton (Gsinfo::skl)
+    SpdpMapGene g;                   // chr, rvs, q_rev, score (Gsinfo::scr), val (fstat.val; 0 -- vclear -- when not aligned)
+    std::vector<SpdpMapExon> ex;     // its exons as -O4 prints them
+};
+// called once per locus, in the block search's order (query by query, a query's loci as findblock listed them)
+using LocusSink = std::function<void(const SpdpLocus& L, LocusOut&& o)>;
+
+SpdpMapGene no_gene()
+{
+    SpdpMapGene g;
+    g.chr = -1; g.rvs = 0; g.q_rev = 0; g.score = SPDP_NEVSEL; g.val = 0; g.n_loci = 0; g.n_exons = 0; g.exon_off = 0;
+    return g;
+}
+
+// per query: the genes it reports, in order -> gene_off[n + 1] of the caller, *genes and *exons malloc'ed
+struct Reported {
+    std::vector<std::vector<SpdpMapGene>> genes;
+    std::vector<std::vector<std::vector<SpdpMapExon>>> ex;
+    explicit Reported(int n) : genes(n), ex(n) {}
+};
+int hand_out(SpdpContext* ctx, const char* who, const Reported& r, int n, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons)
+{
+    size_t ng = 0, ne = 0;
+    for (int i = 0; i < n; ++i) { ng += r.genes[i].size(); for (const auto& e : r.ex[i]) ne += e.size(); }
+    *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
+    *genes = (SpdpMapGene*) malloc(sizeof(SpdpMapGene) * std::max<size_t>(ng, 1));
+    if (!*exons || !*genes) {
+        free(*exons); *exons = nullptr; free(*genes); *genes = nullptr;
+        ctx->err = std::string(who) + ": out of memory"; return -1;
+    }
+    size_t o = 0, k = 0;
+    gene_off[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        for (size_t j = 0; j < r.genes[i].size(); ++j, ++k) {
+            SpdpMapGene G = r.genes[i][j];
+            const std::vector<SpdpMapExon>& e = r.ex[i][j];
+            G.exon_off = (int64_t) o; G.n_exons = (int32_t) e.size();
+            if (!e.empty()) memcpy(*exons + o, e.data(), sizeof(SpdpMapExon) * e.size());
+            o += e.size();
+            (*genes)[k] = G;
+        }
+        gene_off[i + 1] = (int64_t) k;
+    }
+    return 0;
+}
+
+// the best locus of a query: the highest fstat.val of the aligned ones, the first on ties; no threshold (spdp_map_align_s / _h)
+struct BestSink {
+    std::vector<SpdpMapGene> best;
+    std::vector<std::vector<SpdpMapExon>> ex;
+    explicit BestSink(int n) : best(n, no_gene()), ex(n) {}
+    void operator()(const SpdpLocus& L, LocusOut&& o)
+    {
+        if (!o.aligned) return;
+        SpdpMapGene& G = best[L.query];
+        ++G.n_loci;
+        if (G.chr >= 0 && G.val >= o.g.val) return;
+        const int32_t nl = G.n_loci;
+        G = o.g; G.n_loci = nl;
+        ex[L.query] = std::move(o.ex);
+    }
+    int finish(SpdpContext* ctx, const char* who, int n, SpdpMapGene* genes, SpdpMapExon** exons)
+    {
+        size_t ne = 0;
+        for (int i = 0; i < n; ++i) ne += ex[i].size();
+        *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
+        if (!*exons) { ctx->err = std::string(who) + ": out of memory"; return -1; }
+        size_t o = 0;
+        for (int i = 0; i < n; ++i) {
+            genes[i] = best[i];
+            genes[i].exon_off = (int64_t) o; genes[i].n_exons = (int32_t) ex[i].size();
+            if (!ex[i].empty()) memcpy(*exons + o, ex[i].data(), sizeof(SpdpMapExon) * ex[i].size());
+            o += ex[i].size();
+        }
+        return 0;
+    }
+};
+
+// what spaln -M N prints of a query (blkaln, src/spaln.cc:913-976): every locus is dropped (scr = NEVSEL, not counted in n_out)
+// whose walk failed or -- unless all_out (-pw) -- whose score is <= Vthr; ALL loci, the dropped ones too, are insertion-sorted by
+// fstat.val (descending, stable); the first min(n_out, MaxOut) positions of that order are printed, those without a skeleton
+// skipped.  So a locus dropped by the threshold keeps its place in the order and is printed when it lands in one of those slots.
+struct MultiSink {
+    std::vector<std::vector<LocusOut>> all;
+    int max_out, all_out, vthr;
+    MultiSink(int n, int max_out_, int all_out_, int vthr_) : all(n), max_out(max_out_), all_out(all_out_), vthr(vthr_) {}
+    void operator()(const SpdpLocus& L, LocusOut&& o) { all[L.query].push_back(std::move(o)); }
+    int finish(SpdpContext* ctx, const char* who, int n, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons)
+    {
+        Reported r(n);
+        for (int i = 0; i < n; ++i) {
+            std::vector<LocusOut>& v = all[i];
+            const int np = (int) v.size();
+            int n_out = 0, n_aligned = 0;
+            for (const LocusOut& o : v) {
+                n_aligned += o.aligned;
+                n_out += o.aligned && (all_out || o.g.score > vthr);
+            }
+            std::vector<int> odr(np);
+            std::iota(odr.begin(), odr.end(), 0);
+            for (int k = 1; k < np; ++k) {                         // (the reference's insertion sort: ties keep their order)
+                const int l = odr[k];
+                int m = k;
+                while (--m >= 0 && v[l].g.val > v[odr[m]].g.val) odr[m + 1] = odr[m];
+                odr[m + 1] = l;
+            }
+            n_out = std::min(n_out, max_out);
+            for (int k = 0; k < n_out; ++k) {
+                LocusOut& o = v[odr[k]];
+                if (!o.aligned) continue;
+                if (!all_out && o.g.score <= vthr) o.g.score = SPDP_NEVSEL;     // (dropped, printed all the same: its scr is NEVSEL by then)
+                o.g.n_loci = n_aligned;
+                r.genes[i].push_back(o.g);
+                r.ex[i].push_back(std::move(o.ex));
+            }
+        }
+        return hand_out(ctx, who, r, n, gene_off, genes, exons);
+    }
+};
+
+// the checks the multi entries add: MaxOut as blkaln reads it, and an index whose queues were sized for it (Ncand = MaxOut + 10,
+// src/blksrc.cc:2220)
+int check_multi(SpdpContext* ctx, const char* who, const SpdpBlkIndexDesc* hix, const SpdpBlkFindParams* fprm)
+{
+    if (!hix || !fprm) { ctx->err = std::string(who) + ": null argument"; return -1; }
+    if (fprm->max_out < 1 || fprm->max_out2 < fprm->max_out) {
+        ctx->err = std::string(who) + ": max_out must be >= 1 and max_out2 >= max_out (spaln -M N[.M])"; return -1;
+    }
+    if (hix->ncand != fprm->max_out + 10) {
+        ctx->err = std::string(who) + ": the index was made for another MaxOut (its ncand " + std::to_string(hix->ncand) + " != max_out + 10 = " +
+                   std::to_string(fprm->max_out + 10) + "; SpdpBlkSearchOpts.max_out sets it)";
+        return -1;
+    }
+    return 0;
+}
+
 }  // namespace
 
 static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                                 const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
                                 const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                                SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
+                                const LocusSink& sink, double* seconds)
 {
     if (!ctx) return -1;
-    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs || !genes || !exons) {
+    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
         ctx->err = "spdp_map_align_s: null argument"; return -1;
     }
     if (ori != 1 && ori != 3) { ctx->err = "spdp_map_align_s: ori must be 1 (the query as given) or 3 (both orientations)"; return -1; }
     if (!sp->wilip) { ctx->err = "spdp_map_align_s: SpdpSeedParams.wilip missing (the HSP searches of this call are the library's own)"; return -1; }
-    *exons = nullptr;
     double sec[4] = {0, 0, 0, 0};
-    for (int i = 0; i < n; ++i) { genes[i].chr = -1; genes[i].rvs = 0; genes[i].q_rev = 0; genes[i].score = SPDP_NEVSEL; genes[i].val = 0; genes[i].n_loci = 0; genes[i].n_exons = 0; genes[i].exon_off = 0; }
     if (n <= 0) return 0;
     auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> ql(n, 0), qr(n);
@@ -80,7 +222,6 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     size_t chunk_positions = (size_t) 2048 << 20;
     for (const char* v : {"SPDP_MAP_CHUNK_MB", "SPDP_MAP_CHUNK_MPOS"})
         if (const char* e = getenv(v)) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    std::vector<std::vector<SpdpMapExon>> kept(n);
     int partial = 0;
     (void) hipSetDevice(ctx->device);
     // chunks of loci: as few as the position limit allows, of equal size (a call's time is a chain of request latencies, not
@@ -182,16 +323,15 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         memset(res.data(), 0, sizeof(SpdpRescored) * m);
         if (spdp_skl_rng_s(ctx, sc, rp, probs.data(), m, aln.data(), res.data())) { spdp_free_alignments(aln.data(), m); return -1; }
         for (int k = 0; k < m; ++k) {
-            if (aln[k].n_skl < 1) continue;
             const SpdpLocus& L = loci[c0 + k];
-            SpdpMapGene& G = genes[L.query];
-            ++G.n_loci;
-            if (G.chr >= 0 && G.val >= res[k].val) continue;
+            LocusOut o;
+            o.aligned = aln[k].n_skl >= 1;
+            o.g = no_gene();
+            if (!o.aligned) { sink(L, std::move(o)); continue; }
             const int rvs = orient[k] ? !L.rvs : (L.rvs != 0);                                    // the strand the aligned region lies on
             const int a_len = probs[k].a_len;
-            G.chr = L.chr; G.rvs = rvs; G.q_rev = orient[k]; G.score = res[k].score; G.val = res[k].val;
-            std::vector<SpdpMapExon>& ex = kept[L.query];
-            ex.clear();
+            o.g.chr = L.chr; o.g.rvs = rvs; o.g.q_rev = orient[k]; o.g.score = res[k].score; o.g.val = res[k].val;
+            std::vector<SpdpMapExon>& ex = o.ex;
             auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
             for (int e = 0; e < res[k].n_exons; ++e) {
                 const SpdpExon& x = res[k].exons[e];
@@ -199,21 +339,12 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
                 if (orient[k]) ex.push_back({a_len - x.rleft, a_len - x.rright + 1, site(x.left), site(x.right - 1)});     // positions of the query as given
                 else ex.push_back({x.rleft + 1, x.rright, site(x.left), site(x.right - 1)});
             }
+            sink(L, std::move(o));
         }
         spdp_free_rescored(res.data(), m);
         spdp_free_alignments(aln.data(), m);
         sec[3] += since(t0);
         c0 = c1;
-    }
-    size_t ne = 0;
-    for (int i = 0; i < n; ++i) ne += kept[i].size();
-    *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
-    if (!*exons) { ctx->err = "spdp_map_align_s: out of memory"; return -1; }
-    size_t o = 0;
-    for (int i = 0; i < n; ++i) {
-        genes[i].exon_off = (int64_t) o; genes[i].n_exons = (int32_t) kept[i].size();
-        if (!kept[i].empty()) memcpy(*exons + o, kept[i].data(), sizeof(SpdpMapExon) * kept[i].size());
-        o += kept[i].size();
     }
     if (seconds) memcpy(seconds, sec, sizeof sec);
     if (partial) { ctx->err = "spdp_map_align_s: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
@@ -226,10 +357,42 @@ extern "C" int spdp_map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const 
                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
                                 SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
 {
-    try { return map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori, genes, exons, seconds); }
+    if (!ctx) return -1;
+    if (!genes || !exons) { ctx->err = "spdp_map_align_s: null argument"; return -1; }
+    *exons = nullptr;
+    try {
+        BestSink best(std::max(n, 0));
+        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
+        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori, std::ref(best), seconds);
+        if (rc < 0 || n <= 0) return rc;
+        return best.finish(ctx, "spdp_map_align_s", n, genes, exons) ? -1 : rc;
+    }
     catch (const std::bad_alloc&) {                     // (nothing of C++ crosses the C boundary)
-        if (ctx) ctx->err = "spdp_map_align_s: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        if (exons && *exons) { free(*exons); *exons = nullptr; }
+        ctx->err = "spdp_map_align_s: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
+        if (*exons) { free(*exons); *exons = nullptr; }
+        return -1;
+    }
+}
+
+extern "C" int spdp_map_align_s_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                      const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                      const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                      const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, int32_t all_out,
+                                      int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
+{
+    if (!ctx) return -1;
+    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_s_multi: null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr;
+    if (check_multi(ctx, "spdp_map_align_s_multi", hix, fprm)) return -1;
+    try {
+        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
+        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori, std::ref(multi), seconds);
+        if (rc < 0) return rc;
+        return multi.finish(ctx, "spdp_map_align_s_multi", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = "spdp_map_align_s_multi: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
         return -1;
     }
 }
@@ -239,23 +402,21 @@ extern "C" int spdp_map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const 
 // The same chain for amino-acid queries against the translated index (`spaln -W -KP`): spdp_blk_find (the vote on the amino-acid
 // words, the HSP search on regions read as tron codes) -> per locus the region as the aligner reads it (other strand, Seq::nuc2tron) and
 // its SGPT6 signals, all loci of a chunk in one launch of spdp_signals_h -> spdp_align_h_seeded with the library's own HSP searches ->
-// the junction phases the walks chose written back (skl_rngH_ng reads them: spdp_seeded_phase_marks) -> spdp_skl_rng_h -> the locus with
-// the highest fstat.val.  What blkaln / genomicseq / spalign2 do per query (src/spaln.cc:846-1010, 1137-1152), for a batch.
+// the junction phases the walks chose written back (skl_rngH_ng reads them: spdp_seeded_phase_marks) -> spdp_skl_rng_h -> every locus
+// to the sink (the best one, or the list spaln -M prints).  What blkaln / genomicseq / spalign2 do per query (src/spaln.cc:846-1010, 1137-1152), for a batch.
 static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                        const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
                        const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
                        const uint8_t* codes, const int64_t* offs, int32_t n,
-                       SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
+                       const LocusSink& sink, double* seconds)
 {
     if (!ctx) return -1;
-    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs || !genes || !exons) {
+    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
         ctx->err = "spdp_map_align_h: null argument"; return -1;
     }
     if (!sp->wilip || sp->wilip->dvsp != 1) { ctx->err = "spdp_map_align_h: SpdpSeedParams.wilip must be the protein model (dvsp = 1)"; return -1; }
     if (!sc->intpen || sc->intpen_len <= 0) { ctx->err = "spdp_map_align_h: SpdpScoringH.intpen missing"; return -1; }
-    *exons = nullptr;
     double sec[4] = {0, 0, 0, 0};
-    for (int i = 0; i < n; ++i) { genes[i].chr = -1; genes[i].rvs = 0; genes[i].q_rev = 0; genes[i].score = SPDP_NEVSEL; genes[i].val = 0; genes[i].n_loci = 0; genes[i].n_exons = 0; genes[i].exon_off = 0; }
     if (n <= 0) return 0;
     auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> ql(n, 0), qr(n);
@@ -270,7 +431,6 @@ static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     sec[0] = since(t0);
     size_t chunk_positions = (size_t) 512 << 20;        // 14 B per position on both sides of the bus
     if (const char* e = getenv("SPDP_MAP_CHUNK_MPOS")) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    std::vector<std::vector<SpdpMapExon>> kept(n);
     int partial = 0;
     (void) hipSetDevice(ctx->device);
     for (int k = 0; k < n_loci; ++k) {
@@ -355,35 +515,32 @@ static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         memset(res.data(), 0, sizeof(SpdpRescored) * m);
         if (spdp_skl_rng_h(ctx, sc, rp, probs.data(), m, aln.data(), res.data())) return -1;
         for (int j = 0; j < m; ++j) {
-            if (aln[j].n_skl < 1) continue;
             const SpdpLocus& L = loci[c0 + j];
-            SpdpMapGene& G = genes[L.query];
-            ++G.n_loci;
-            if (G.chr >= 0 && G.val >= res[j].val) continue;
-            G.chr = L.chr; G.rvs = L.rvs != 0; G.q_rev = 0; G.score = res[j].score; G.val = res[j].val;
-            std::vector<SpdpMapExon>& ex = kept[L.query];
-            ex.clear();
+            LocusOut o;
+            o.aligned = aln[j].n_skl >= 1;
+            o.g = no_gene();
+            if (!o.aligned) { sink(L, std::move(o)); continue; }
+            o.g.chr = L.chr; o.g.rvs = L.rvs != 0; o.g.q_rev = 0; o.g.score = res[j].score; o.g.val = res[j].val;
+            std::vector<SpdpMapExon>& ex = o.ex;
             const int rvs = L.rvs != 0;
             auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
+            // an exon closes at a record that carries an intron score; records of frame shifts inside it (iscr = NEVSEL, skl_rngH_ng:
+            // src/fwd2h1.cc:739-751, 783-797) do not: the printer reads the exon across them (src/sqpr.cc:896-952, spdp_exon_form)
+            int open = -1;
             for (int e = 0; e < res[j].n_exons; ++e) {
                 const SpdpExon& x = res[j].exons[e];
                 if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
-                ex.push_back({x.rleft + 1, x.rright, site(x.left), site(x.right - 1)});
+                if (open < 0) open = e;
+                if (x.iscr <= SPDP_NEVSEL) continue;
+                const SpdpExon& x0 = res[j].exons[open];
+                ex.push_back({x0.rleft + 1, x.rright, site(x0.left), site(x.right - 1)});
+                open = -1;
             }
+            sink(L, std::move(o));
         }
         spdp_free_rescored(res.data(), m);
         sec[3] += since(t0);
         c0 = c1;
-    }
-    size_t ne = 0;
-    for (int i = 0; i < n; ++i) ne += kept[i].size();
-    *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
-    if (!*exons) { ctx->err = "spdp_map_align_h: out of memory"; return -1; }
-    size_t o = 0;
-    for (int i = 0; i < n; ++i) {
-        genes[i].exon_off = (int64_t) o; genes[i].n_exons = (int32_t) kept[i].size();
-        if (!kept[i].empty()) memcpy(*exons + o, kept[i].data(), sizeof(SpdpMapExon) * kept[i].size());
-        o += kept[i].size();
     }
     if (seconds) memcpy(seconds, sec, sizeof sec);
     if (partial) { ctx->err = "spdp_map_align_h: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
@@ -396,10 +553,42 @@ extern "C" int spdp_map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const 
                                 const uint8_t* codes, const int64_t* offs, int32_t n,
                                 SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
 {
-    try { return map_align_h(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, genes, exons, seconds); }
+    if (!ctx) return -1;
+    if (!genes || !exons) { ctx->err = "spdp_map_align_h: null argument"; return -1; }
+    *exons = nullptr;
+    try {
+        BestSink best(std::max(n, 0));
+        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
+        const int rc = map_align_h(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, std::ref(best), seconds);
+        if (rc < 0 || n <= 0) return rc;
+        return best.finish(ctx, "spdp_map_align_h", n, genes, exons) ? -1 : rc;
+    }
     catch (const std::bad_alloc&) {
-        if (ctx) ctx->err = "spdp_map_align_h: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
-        if (exons && *exons) { free(*exons); *exons = nullptr; }
+        ctx->err = "spdp_map_align_h: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
+        if (*exons) { free(*exons); *exons = nullptr; }
+        return -1;
+    }
+}
+
+extern "C" int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                      const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
+                                      const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+                                      const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                                      int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
+{
+    if (!ctx) return -1;
+    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_h_multi: null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr;
+    if (check_multi(ctx, "spdp_map_align_h_multi", hix, fprm)) return -1;
+    try {
+        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
+        const int rc = map_align_h(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, std::ref(multi), seconds);
+        if (rc < 0) return rc;
+        return multi.finish(ctx, "spdp_map_align_h_multi", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = "spdp_map_align_h_multi: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
         return -1;
     }
 }

@@ -57,12 +57,20 @@ def make_dataset(td, args):
     n_chr = 4
     per = args.genes // n_chr
     tot = 0
+    # (paralogs: every gene twice, the copy diverged -- a stream of its own, so that the rest of the data set stays as it is)
+    prng = np.random.default_rng(synth.SEED + 8900) if getattr(args, "paralogs", False) else None
     with open(os.path.join(td, "gnm.mfa"), "w") as f:
         for c in range(n_chr):
             parts = []
-            for g in genes[c * per:(c + 1) * per]:
+            for k, g in enumerate(genes[c * per:(c + 1) * per]):
                 spacer = int(getattr(args, "spacer", 0) or 0)                     # (--spacer: a larger genome around the same genes)
                 parts += [synth.random_dna(rng, int(rng.integers(3000, 20000)) if not spacer else int(rng.integers(spacer // 2, spacer))), g.window]
+                if prng is not None:                          # cDNA: 4 - 10 % substitutions and some indels; protein: 5 %, no indels (ORFs stay)
+                    copy = synth.mutate(prng, g.window, 0.05, 0.0) if args.protein else \
+                        synth.mutate(prng, g.window, float(prng.choice([0.04, 0.07, 0.1])), 0.002)
+                    if k % 3 == 1:                            # (on the other strand)
+                        copy = np.frombuffer(bytes(copy).translate(bytes.maketrans(b"ACGTacgt", b"TGCAtgca"))[::-1], dtype=np.uint8)
+                    parts += [synth.random_dna(prng, int(prng.integers(300, 1500) if k % 2 else prng.integers(4000, 9000))), copy]
             s = bytes(np.concatenate(parts)).decode()
             tot += len(s)
             f.write(f">chr{c + 1}\n")

@@ -15,7 +15,14 @@ reference's own `spaln -W -KD`; cDNA queries = mutated transcripts).  Two runs:
 
 Compared: per query the exon table (query range, chromosome range of every exon) of the best locus.  The parameter sets
 (scoring, seeded walk, signal model, HSP-search model, block-search constants) are the reference's defaults as its own dumps
-hold them (tests/golden/q_c2_seed0.spdg, blk_k1.spdg).  One JSON line."""
+hold them (tests/golden/q_c2_seed0.spdg, blk_k1.spdg).  One JSON line.
+
+Several loci per query (`spaln -M N`; opt-in, the output without these flags is unchanged):
+  --max-out N   -M N for the program and the parameter recorder; the index is read / built for MaxOut N (Ncand = N + 10) and
+                the library runs spdp_map_align_s_multi / _h_multi: every query's ORDERED list of printed loci and their exon
+                tables is compared (identical_locus_lists), and the best-only call is timed beside it
+  --all-out     -pw: no output threshold
+  --paralogs    every gene of the genome twice, the copy diverged (some on the other strand): paralogs to report"""
 import argparse
 import ctypes as C
 import json
@@ -95,21 +102,88 @@ def reference_exons(text):
     return out
 
 
+def reference_loci(text):
+    """-O4 output -> {query: [(chr, strand, [(ref_l, ref_r, tgt_l, tgt_r)])]}: EVERY record of a query, in print order (spaln -M N
+    prints up to N per query; the summary line `@ chr strand ( .. ) query [..]` closes a record's exon lines)"""
+    out, cur = {}, []
+    for line in text.splitlines():
+        if line.startswith("#"):
+            continue
+        if line.startswith("@"):
+            f = line.split()
+            m = re.search(r"\) (\S+) \[", line)
+            out.setdefault(m.group(1) if m else f[7], []).append((f[1], f[2], cur))
+            cur = []
+            continue
+        f = line.split("\t")
+        if len(f) >= 10:
+            cur.append((int(f[6]), int(f[7]), int(f[8]), int(f[9])))
+    return out
+
+
+def loci_of(genes, chr_names):
+    """a _multi entry's lists -> the layout of reference_loci"""
+    return [[(chr_names[g["chr"]], "-" if g["rvs"] else "+", [tuple(e) for e in g["exons"]]) for g in lst] for lst in genes]
+
+
+def multi_opts(args):
+    """the program's options of --max-out / --all-out"""
+    return ([f"-M{args.max_out}"] if args.max_out else []) + (["-pw"] if args.all_out else [])
+
+
+def run_multi(args, ref_stdout, q_names, chr_names, multi, best, load_s):
+    """--max-out: the multi entry (twice: the first call of a context also loads the code objects) against every record the program
+    printed, then the best-only entry once on the same index (its time beside the multi call's)"""
+    want = reference_loci(ref_stdout)
+    runs = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        lists, phases, rc = multi()
+        runs.append((time.perf_counter() - t0, phases))
+    t0 = time.perf_counter()
+    best()
+    best_s = time.perf_counter() - t0
+    got = {q_names[i]: v for i, v in enumerate(loci_of(lists, chr_names)) if v}
+    same = [k for k, v in want.items() if got.get(k) == v]
+    # both orientations: after a locus aligned with the query reverse-complemented the program aligns the query's further loci in that
+    # state (alignS_ng leaves it so, src/fwd2s1.cc:2766-2777); the library aligns every locus on its own -- such queries are counted apart
+    rev_first = {k for k, v in want.items() if v[0][2] and v[0][2][0][0] > v[0][2][0][1]}
+    diff = sorted((set(want) | set(got)) - set(same))
+    for k in diff[:args.show]:
+        sys.stderr.write(f"{k}\n  reference {want.get(k)}\n  library   {got.get(k)}\n")
+    if args.dump_diff:
+        os.makedirs(os.path.dirname(os.path.abspath(args.dump_diff)), exist_ok=True)
+        gi = {q_names[i]: v for i, v in enumerate(lists)}
+        json.dump([{"name": k, "reference": want.get(k), "library": got.get(k), "library_genes": gi.get(k)} for k in diff],
+                  open(args.dump_diff, "w"), indent=1)
+    lib_s, phases = runs[-1]
+    return {"queries": args.queries, "max_out": args.max_out, "all_out": bool(args.all_out), "paralogs": bool(args.paralogs),
+            "reference_aligned": len(want), "library_aligned": len(got),
+            "reference_loci": sum(len(v) for v in want.values()), "library_loci": sum(len(v) for v in got.values()),
+            "identical_locus_lists": len(same), "different": len(diff),
+            "identical_first_loci": sum(1 for k, v in want.items() if got.get(k, [None])[0] == v[0]), "reversed_first": len(rev_first),
+            "identical_lists_of_the_others": sum(1 for k in same if k not in rev_first),
+            "library_s": {"index_and_genome_load": round(load_s, 3), "multi_call": round(lib_s, 3), "best_only_call": round(best_s, 3),
+                          "first_call": round(runs[0][0], 3), "find": round(phases[0], 3), "regions_and_signals": round(phases[1], 3),
+                          "align": round(phases[2], 3), "rescore": round(phases[3], 3)},
+            "return_code": rc}
+
+
 def main_protein(args):
     """BASELINE configs[0] / [2]'s whole path: protein queries, `spaln -Q7 -O4` against ONE spdp_map_align_h call"""
     t_all = time.perf_counter()
     with tempfile.TemporaryDirectory(prefix="spdp_e2e_p_") as td:
         genome_nt, env = dropin_demo.make_dataset(td, args)
         t0 = time.perf_counter()
-        r = subprocess.run([os.path.join(dropin_demo.REF, "spaln"), "-Q7", "-O4", f"-t{args.threads}", "-dgnm", "q.fa"], cwd=td, env=env,
-                           capture_output=True, text=True)
+        r = subprocess.run([os.path.join(dropin_demo.REF, "spaln"), "-Q7", "-O4", f"-t{args.threads}"] + multi_opts(args) + ["-dgnm", "q.fa"],
+                           cwd=td, env=env, capture_output=True, text=True)
         ref_s = time.perf_counter() - t0
         if r.returncode:
             raise SystemExit("reference run failed: " + r.stderr[-300:])
         want = reference_exons(r.stdout)
         eng = engine.Engine(0)
         lib = eng.lib
-        cli = cli_parameters(td, env, [])
+        cli = cli_parameters(td, env, multi_opts(args))
         model = abi.wilip_model_from_fixture(cli)
         # the alignment parameters of a protein run of the reference with the program's cross-species setting (a ref_dump fixture), the
         # intron-length limits and the IntPen table as the program holds them for THIS genome
@@ -123,13 +197,14 @@ def main_protein(args):
         off = np.array([0] + list(np.cumsum([len(c) for c in chroms])), dtype=np.int64)
         # the translated index: built by the library from the same residues (spdp_blk_index_build_p), compared with the reference's
         # file, and the one searched below
-        theirs = blocks.read_index_file(lib, os.path.join(td, "gnm.bkp"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]))
+        mo = {"max_out": args.max_out} if args.max_out else {}
+        theirs = blocks.read_index_file(lib, os.path.join(td, "gnm.bkp"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]), **mo)
         bprm = blocks.build_params_default_p(lib, os.path.getsize(os.path.join(td, "gnm.mfa")), threaded=1)        # (make_dataset formats with -t)
         blocks.build_index_p(eng, gen[:1 << 16], np.array([0, min(len(gen), 1 << 16)], dtype=np.int64), bprm)     # (first launch of the kernels)
         tb = time.perf_counter()
         _, bsec = blocks.build_index_p(eng, gen, off, bprm, write_to=os.path.join(td, "ours.bkp"))
         build_s = time.perf_counter() - tb
-        fx = blocks.read_index_file(lib, os.path.join(td, "ours.bkp"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]))
+        fx = blocks.read_index_file(lib, os.path.join(td, "ours.bkp"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]), **mo)
         index_same = all(np.array_equal(np.asarray(fx[k]), np.asarray(theirs[k])) for k in ("blk_nblk", "blk_wscr", "blk_blkp", "blk_blkb", "blk_chr", "blk_prm"))
         fx["blk_convtab"][:2] = 255
         dix = blocks.BlockIndex(eng, fx)
@@ -152,6 +227,18 @@ def main_protein(args):
         rescore = abi.RescoreParamsH(minl, rp[4], hp["lcl"], rp[1])
         load_s = time.perf_counter() - t0
         sp.wilip = C.addressof(model)
+        if args.max_out:
+            multi = lambda: blocks.map_align_h_multi(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, all_out=args.all_out)  # noqa: E731
+            best = lambda: blocks.map_align_h(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries)  # noqa: E731
+            out = run_multi(args, r.stdout, q_names, chr_names, multi, best, load_s)
+            out.update({"what": "protein queries: every locus `spaln -Q7 -O4 -M%d%s` prints against spdp_map_align_h_multi" % (args.max_out, " -pw" if args.all_out else ""),
+                        "genome_nt": genome_nt, "reference_wall_s": round(ref_s, 2), "reference_threads": args.threads,
+                        "index": {"built_by": "spdp_blk_index_build_p", "tables_identical_to_the_reference_file": bool(index_same)},
+                        "wall_s": round(time.perf_counter() - t_all, 1)})
+            print(json.dumps(out))
+            dix.free()
+            eng.close()
+            return
         runs = []
         for _ in range(2):
             t0 = time.perf_counter()
@@ -197,8 +284,16 @@ def main():
                     help="1: the queries as given against `spaln -S1`; 3: every other query reverse-complemented, both orientations "
                          "tried, against spaln's default (-S3)")
     ap.add_argument("--protein", action="store_true", help="protein queries against the translated index (spaln -W -KP): spdp_map_align_h")
+    ap.add_argument("--max-out", type=int, default=0,
+                    help="N > 0: spaln -M N against spdp_map_align_s_multi / _h_multi -- every query's ordered list of loci is compared")
+    ap.add_argument("--all-out", action="store_true", help="with --max-out: -pw (no output threshold) for both programs")
+    ap.add_argument("--paralogs", action="store_true", help="every gene of the genome twice, the copy diverged")
     ap.add_argument("--dump-diff", default="", help="write the queries whose exon tables differ (name, both tables, the library's gene record) to this JSON file")
     args = ap.parse_args()
+    if args.all_out and not args.max_out:
+        ap.error("--all-out needs --max-out")
+    if args.max_out and args.members > 1:
+        ap.error("--max-out runs on one context (--members 1)")
     if args.protein:
         return main_protein(args)
     t_all = time.perf_counter()
@@ -211,8 +306,8 @@ def main():
                 lines[i + 1] = lines[i + 1].translate(comp)[::-1]
             open(os.path.join(td, "q.fa"), "w").write("\n".join(lines))
         t0 = time.perf_counter()
-        r = subprocess.run([os.path.join(dropin_demo.REF, "spaln"), "-Q7"] + (["-S1"] if args.ori == 1 else []) + ["-O4", f"-t{args.threads}", "-dgnm", "q.fa"],
-                           cwd=td, env=env, capture_output=True, text=True)
+        r = subprocess.run([os.path.join(dropin_demo.REF, "spaln"), "-Q7"] + (["-S1"] if args.ori == 1 else []) + ["-O4", f"-t{args.threads}"] +
+                           multi_opts(args) + ["-dgnm", "q.fa"], cwd=td, env=env, capture_output=True, text=True)
         ref_s = time.perf_counter() - t0
         if r.returncode:
             raise SystemExit("reference run failed: " + r.stderr[-300:])
@@ -222,10 +317,11 @@ def main():
         eng = engine.Engine(0)
         lib = eng.lib
         fq = spdg.load(os.path.join(ROOT, "tests", "golden", "q_c2_seed0.spdg"))
-        cli = cli_parameters(td, env, ["-S1"] if args.ori == 1 else [])
+        cli = cli_parameters(td, env, (["-S1"] if args.ori == 1 else []) + multi_opts(args))
         t0 = time.perf_counter()
         # ExtBlock = max_intron_len() / blklen + 1 follows from the program's IntronPrm.maxl (src/blksrc.cc:2071-2082, 2222): as recorded
-        fx = blocks.read_index_file(lib, os.path.join(td, "gnm.bkn"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]))
+        fx = blocks.read_index_file(lib, os.path.join(td, "gnm.bkn"), ext_block=int(cli["blk_prm"][blocks._PRM["extblock"]]),
+                                    **({"max_out": args.max_out} if args.max_out else {}))
         fx["blk_convtab"][:2] = 255
         dix = blocks.BlockIndex(eng, fx)
         chr_names, chroms = read_fasta(os.path.join(td, "gnm.mfa"))
@@ -245,6 +341,18 @@ def main():
         sp.wilip = C.addressof(model)
         fs = fq["rng_fstat_A0"] if "rng_fstat_A0" in fq else [0, 0, 0, 0, 0, 0, 3, 1]
         rescore = (fq["prm"]["codonk1"], minl, int(fs[6]), int(fs[7]))
+        if args.max_out:
+            multi = lambda: blocks.map_align_multi(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori, all_out=args.all_out)  # noqa: E731
+            best = lambda: blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)  # noqa: E731
+            out = run_multi(args, r.stdout, q_names, chr_names, multi, best, load_s)
+            out.update({"what": "every locus `spaln -Q7 %s-O4 -M%d%s` prints against spdp_map_align_s_multi" % ("-S1 " if args.ori == 1 else "", args.max_out,
+                                                                                                             " -pw" if args.all_out else ""),
+                        "ori": args.ori, "genome_nt": genome_nt, "reference_wall_s": round(ref_s, 2), "reference_threads": args.threads,
+                        "wall_s": round(time.perf_counter() - t_all, 1)})
+            print(json.dumps(out))
+            dix.free()
+            eng.close()
+            return
         # one call: spdp_blk_find -> regions and their signals (one launch) -> spdp_align_s_seeded -> spdp_skl_rng_s -> the
         # locus that stays.  Twice: the first call of a context also loads the kernels' code objects and sizes its pools
         runs = []
