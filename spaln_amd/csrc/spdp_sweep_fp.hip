@@ -17,7 +17,7 @@
 //     short lengths, which yields exactly `nevsel` there, as the reference's blend does;
 //   * the bottom row leaves the stripe through LDS: its lane writes the step's {H, Fcand, links} into slot `step` of a
 //     16-entry block under a one-lane exec mask (a ds_write beside the VALU stream) and lane j reads slot j back at the
-//     flush (round 2 used one 64-bit row_newbcast DPP per pair of values and step; the int kernels a rotate + shift per value).
+//     flush; the block shares its LDS with the feed, which slot `step` no longer needs by then (round 2 used one 64-bit row_newbcast DPP per pair of values and step; the int kernels a rotate + shift per value).
 //
 // Reference recurrence: src/fwd2s1_wip_simd.h:97-202 (score-only), :555-758 (linear space),
 // boundary set-up / end selection src/fwd2s1_simd.cc:163-262.  Geometry (16-row stripes = DPP rows, four
@@ -131,8 +131,9 @@ template <bool B> struct BoolTag { static constexpr bool value = B; };
 // ---------------------------------------------------------------------------
 // WPB / CROSS / work mapping / progress words: exactly as spdp_sweep (spdp_kernels.hip).
 // SPJ: splice signals on (PwdB::DvsP != 0): with it off there is no donor / acceptor state at all.
+// A 4-wave block of one CU asks for five waves per SIMD: <= 32 KB of LDS and <= 96 VGPRs.
 template <int FL, int WPB, bool CROSS, bool SPJ>
-__global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
+__global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB == 4 && !CROSS ? 5 : 1))) void spdp_sweep_fp(SweepArgs A)
 {
     // FL_FORWARD (round 4): the traceback flavour -- one code byte per cell in the layout spdp_walk reads (spdp_kernels.hip:
     // 256 bytes per block of 16 steps, 16 per lane) -- on this kernel's step; local ends stay with spdp_kernels.hip
@@ -146,22 +147,25 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
     //    36 floats: the 16 common (query, genome) pairs then sit in 16 different banks (rows of 32 put a whole
     //    column in ONE bank: up to 4 addresses per bank and instruction);
     //  * column records as two rings (signals 8 B, matrix column offset 4 B) instead of one 16-byte record: the 16
-    //    lanes of a row read 16 consecutive slots = 32 (16) consecutive banks, and the next row of the wave, 16
-    //    slots behind, the other half;
+    //    lanes of a row read 16 consecutive slots = 32 (16) consecutive banks; all rows of a wave are at the same
+    //    ring position (their lag, 4 blocks, is a multiple of the 2-block ring), and the rings of consecutive rows
+    //    lie RS = 80 slots apart (160 dwords = 32 mod 64 banks for the 8-byte reads, 80 = 16 mod 32 for the 4-byte
+    //    ones): the two rows of a 32-lane half read the two halves of the banks;
     //  * the feed of a row is padded by one entry, so the entries the rows of a wave broadcast in one
     //    instruction lie in different banks.
+    constexpr int RS = 80;
     __shared__ float  s_mtx[32 * 36];
     __shared__ int    s_perm[32];
     __shared__ float2 s_pen[SPDP_FPEN_TAB];
-    // per wave, per DPP row: 2 x 48-slot rings of column records (each record written twice, 48 slots apart: any
-    // 31-column window is contiguous) and the 16 boundary entries of the block
-    __shared__ float2 s_sig[WPB][4][96];                // {sig5 + ipen, sig3}
-    __shared__ int    s_bof[WPB][4][96];                // byte offset of the base's matrix column
-    __shared__ int    s_feed[WPB][4][16 * BW + BW];
-    // bottom-row results of a block's 16 steps, written by the bottom lane of a stripe, read back by lane = step at the
-    // flush (a ds_write under a one-lane exec mask issues beside the VALU stream; the 64-bit DPP collectors it
-    // replaces were two of the six most expensive instructions of the step, and sixteen registers)
-    __shared__ int    s_out[WPB][4][16 * BW + BW];
+    // per wave, per DPP row: 2 x 32-slot rings of column records (each record written twice, 32 slots apart: the
+    // 31-column window of a block is contiguous) and the 16 boundary entries of the block
+    __shared__ float2 s_sig[WPB][4][RS];                // {sig5 + ipen, sig3}
+    __shared__ int    s_bof[WPB][4][RS];                // byte offset of the base's matrix column
+    // the feed (the 16 boundary entries a block reads, slot j read ahead at step j - 1) and, in the same slots, the
+    // bottom-row results of the block's 16 steps: written by the bottom lane of a stripe at step j, read back by
+    // lane = step at the flush (a ds_write under a one-lane exec mask issues beside the VALU stream; the 64-bit DPP
+    // collectors it replaces were two of the six most expensive instructions of the step, and sixteen registers)
+    __shared__ int    s_io[WPB][4][16 * BW + BW];
     __shared__ int    s_prog_lds[WPB];
 
     const DevScoring* __restrict__ sc = A.sc;
@@ -189,10 +193,14 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
     const int g = lane >> 4;                    // DPP row = stripe slot of the pass
     const int k = lane & 15;                    // lane within the stripe
     const float gef = (float) sc->gep, gnf = (float) (sc->gep + sc->gop);
+    // the gap candidates every stripe starts from, as scalars: kept in vector registers across the passes they were
+    // spilled at five waves per SIMD
+    const float hg0 = as_f(__builtin_amdgcn_readfirstlane(as_i(fmaxf(NEVF + gnf, FLOORF))));
+    const float fm0 = as_f(__builtin_amdgcn_readfirstlane(as_i(fmaxf(NEVF + gef, hg0))));
     const int ge = sc->gep;
     const int cap8 = pen_cap * 8;               // hil is carried as the byte offset of its table entry
 
-    const int wv = threadIdx.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (uniform: a scalar, not a register of every lane)
     const int G = CROSS ? A.cross_g : 1;            // blocks cooperating on my problem
     const bool multi = CROSS || (int) blockIdx.x < A.n_multi;
     const int W = multi ? WPB * G : 1;              // waves cooperating on my problem
@@ -339,8 +347,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
             }
         }
         const bool imd_row = UDH && imd_i >= 0;
-        int* imd_p = nullptr;
-        if constexpr (UDH) if (imd_row) imd_p = A.imd + P.imd_off + (int64_t) imd_i * 4 * width;
+        int* const imd_p = A.imd + P.imd_off;           // (UDH) the link planes of intermediate row imd_i: 4 x width from imd_p + 4 width imd_i
         if (!mine) continue;                            // bookkeeping above ran; the sweep is another wave's
         // only the last stripe of a problem can be partial (fewer than 16 rows)
         const bool pass_partial = (s0 + 4 >= n_stripes) && ((a_right - a_left) & 15);
@@ -353,7 +360,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
         // opened from H, shared by my E and by the F of the row below; Fm / FCm: the row below's vertical-gap
         // candidate and its link), E, the diagonal neighbour, the donor state
         float Hs = NEVF, E = NEVF, Hd = NEVF, hv2 = NEVF;
-        float Hg = fmaxf(NEVF + gnf, FLOORF), Fm = fmaxf(NEVF + gef, Hg);
+        float Hg = hg0, Fm = fm0;
         // hil is carried as the byte offset of its table entry; the entry itself is read one step ahead (for
         // hil + 1, i.e. assuming no donor fires in between: a donor resets hil to 1, whose candidate is `nevsel`
         // whatever the donor score, llmt >= 1) so that no LDS round trip sits inside the cell-to-cell recurrence
@@ -362,11 +369,11 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
         bool don_prev = false;
         int Cs = 0, FCm = 0, Cd = 0, ec = 0, hc2 = 0;              // UDH links
         int donor_r = 0, rlst = INT32_MAX;                         // UDH, lane k8 only
-        int* const outb = &s_out[wv][g][0];
+        int* const outb = &s_io[wv][g][0];
         const bool is_bottom = k == max(j8, 0);                    // (a partial last stripe: its last real row)
         float2* const sigring = &s_sig[wv][g][0];
         int*    const bofring = &s_bof[wv][g][0];
-        int*    const feed = &s_feed[wv][g][0];
+        int*    const feed = &s_io[wv][g][0];
 
         auto run_pass = [&](auto partial_tag, auto imd_tag) {
             constexpr bool PARTIAL = decltype(partial_tag)::value;
@@ -377,17 +384,18 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
             const rsrc_t brs = bnd_rsrc(bnd);                                 // (CROSS: the boundary array of this problem as a buffer)
             // a row's blocks are prefetched in order (block 0 once, then lb + 1 from block lb), so the two addresses and
             // the flush address below are carried along, 16 entries per block, instead of being rebuilt from lb
-            int64_t pf_b = (int64_t) BIDX(n_start + k - ml) * BW;            // (index into bnd) sweep step n_start + 16 lbn + k of this lane
-            const int2* pf_c = cols + (n_start + k);
-            int* st_p = bnd + (int64_t) BIDX(n_start + k - (ml + 1) - 2 * j8) * BW;
+            // (32-bit indices against the problem's base pointers, not 64-bit addresses: two registers fewer each, section 6g)
+            int pf_b = BIDX(n_start + k - ml) * BW;                         // (index into bnd) sweep step n_start + 16 lbn + k of this lane
+            int pf_c = n_start + k;                                         // (index into cols)
+            int st_p = BIDX(n_start + k - (ml + 1) - 2 * j8) * BW;           // (index into bnd)
             // the reference's write condition (fwd2s1_wip_simd.h:205-209) as a range of the sweep step n0 + k
             const int fl_lo = max(b_left + j9, lw + (ml + 1) + 2 * j8);
             const int fl_hi = j9 > 0 ? min(up + (ml + 1) + 2 * j8 + 1, n_end) : INT32_MIN;
-            int lbm = 0;                                                // (16 lb) mod 48: where the block sits in the 48-slot rings
+            int lbm = 0;                                                // (16 lb) mod 32: where the block sits in the 32-slot rings
             auto prefetch = [&](int) {
                 if constexpr (UDH) nx_b = ldx_b4<CROSS>(brs, bnd, pf_b);
                 else { const int2 v = ldx_b2<CROSS>(brs, bnd, pf_b); nx_b.x = v.x; nx_b.y = v.y; }
-                nx_c = *pf_c;                                           // raw record: no use here, the load must stay in flight
+                nx_c = cols[pf_c];                                      // raw record: no use here, the load must stay in flight
                 pf_b += 16 * BW; pf_c += 16;
             };
             // multi-wave: row 0 reads boundary entries of the previous pass, produced by wave `prod`;
@@ -435,8 +443,11 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
                         // lanes need, and lane 0's up-left neighbour comes from the boundary array
                         const int c = n_start - 1 - k;
                         const int bof0 = s_perm[((c > b_left && c <= b_right) ? cols[c].y : 0) & 31] * 4;
-                        if constexpr (SPJ) { sigring[15 - k] = make_float2(0.f, 0.f); sigring[15 - k + 48] = make_float2(0.f, 0.f); }
-                        bofring[15 - k] = bof0; bofring[15 - k + 48] = bof0;
+                        // (slot 15 - k, written as lbm + 15 - k with lbm = 0 here: an address formed in this branch, not one
+                        // hoisted out of the pass and kept in a register throughout)
+                        const int s0k = lbm + 15 - k;
+                        if constexpr (SPJ) { sigring[s0k] = make_float2(0.f, 0.f); sigring[s0k + 32] = make_float2(0.f, 0.f); }
+                        bofring[s0k] = bof0; bofring[s0k + 32] = bof0;
                         const int r = n_start - (ml + 1);
                         donor_r = r;
                         if (k == 0) {
@@ -456,29 +467,28 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
                         if (nn <= b_left) bs = 0;
                         const float2 srec = make_float2((float) (short) sg, (float) (sg >> 16));
                         const int bof = s_perm[bs & 31] * 4;
-                        const int slot = lbm + k + 16 >= 48 ? lbm + k + 16 - 48 : lbm + k + 16;      // (16 lb + k + 16) mod 48
-                        if constexpr (SPJ) { sigring[slot] = srec; sigring[slot + 48] = srec; }
-                        bofring[slot] = bof; bofring[slot + 48] = bof;
+                        const int slot = (lbm + k + 16) & 31;                    // (16 lb + k + 16) mod 32
+                        if constexpr (SPJ) { sigring[slot] = srec; sigring[slot + 32] = srec; }
+                        bofring[slot] = bof; bofring[slot + 32] = bof;
                     }
                     // ---- ... and the next block's loads are issued now, to land while this one computes
                     if (lb + 1 < nb) prefetch(lb + 1);
                     WAVE_ORDER();
                     // lane k reads column n0 + J - k at step J: one contiguous run of 16 ring slots
-                    const int myslot = lbm - k + 16 == 48 ? 0 : lbm - k + 16;             // (16 lb - k + 16) mod 48
+                    const int myslot = (lbm - k + 16) & 31;                               // (16 lb - k + 16) mod 32
                     const float2* const mysig = sigring + myslot;
                     const int* const mybof = bofring + myslot;
                     // intermediate row (lane k8 of its stripe): the steps of this block whose cell lies on it inside the band,
                     // its diagonal at step 0, and the four link planes at that diagonal -- once per block, not per step
-                    int imd_jlo = 99, imd_jhi = -1, imd_r0 = 0, imd_r0w = 0;
-                    int *imd_h0 = nullptr, *imd_h1 = nullptr, *imd_v = nullptr, *imd_f = nullptr;
+                    // (the planes as one index against imd_p: imd_h0 + J, then + width, + 2 width, + 3 width)
+                    int imd_jlo = 99, imd_jhi = -1, imd_r0 = 0, imd_r0w = 0, imd_h0 = 0;
                     if constexpr (UDH && IMD) {
                         if (imd_row && k == k8) {
                             imd_r0 = n0 - (ml + 1) - 2 * k;
                             imd_r0w = imd_r0 + width;
                             imd_jlo = max(0, lw - imd_r0);
                             imd_jhi = min(15, min(up - imd_r0, n_end - n0 - 1));
-                            imd_h0 = imd_p + BIDX(imd_r0);
-                            imd_h1 = imd_h0 + width; imd_v = imd_h1 + width; imd_f = imd_v + width;
+                            imd_h0 = imd_i * 4 * width + BIDX(imd_r0);
                         }
                     }
 
@@ -567,12 +577,13 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
                             /* scalar bookkeeping of the intermediate row (lane k8 of its stripe) */         \
                             if (J >= imd_jlo && J <= imd_jhi) {                                              \
                                 const int rj = imd_r0 + J;                      /* my cell's diagonal */     \
-                                if (SPJ && is_acc) { st_b1<CROSS>(imd_h0 + J, donor_r); st_b1<CROSS>(imd_h1 + J, donor_r + width); } \
+                                int* const ih = imd_p + (imd_h0 + J);                                        \
+                                if (SPJ && is_acc) { st_b1<CROSS>(ih, donor_r); st_b1<CROSS>(ih + width, donor_r + width); } \
                                 rlst = ((SPJ && is_acc) || pb3 == 0) ? rj : rlst;                            \
                                 if (SPJ) donor_r = is_don ? rj : donor_r;                                    \
-                                if (pb3 == 1) st_b1<CROSS>(imd_h0 + J, rlst);                                \
-                                st_b1<CROSS>(imd_v + J, hc); hc = rj;                                        \
-                                st_b1<CROSS>(imd_f + J, fl); fl = imd_r0w + J;                               \
+                                if (pb3 == 1) st_b1<CROSS>(ih, rlst);                                        \
+                                st_b1<CROSS>(ih + 2 * width, hc); hc = rj;                                   \
+                                st_b1<CROSS>(ih + 3 * width, fl); fl = imd_r0w + J;                          \
                             }                                                                                \
                         }                                                                                    \
                         Hd = upH; Hs = h;                                                                    \
@@ -608,11 +619,11 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
                     {
                         const int n = n_start + lb * 16 + k;
                         if (n >= fl_lo && n < fl_hi) {
-                            if constexpr (UDH) st_b4<CROSS>(st_p, reinterpret_cast<const int4*>(outb)[k]);
-                            else st_b2<CROSS>(st_p, reinterpret_cast<const int2*>(outb)[k]);
+                            if constexpr (UDH) st_b4<CROSS>(bnd + st_p, reinterpret_cast<const int4*>(outb)[k]);
+                            else st_b2<CROSS>(bnd + st_p, reinterpret_cast<const int2*>(outb)[k]);
                         }
                         st_p += 16 * BW;
-                        lbm = lbm == 32 ? 0 : lbm + 16;
+                        lbm ^= 16;
                     }
                     if constexpr (FWD) {
                         uint4* dst = reinterpret_cast<uint4*>(A.tb + my_tb + 256ll * lb + 16 * k);
@@ -672,7 +683,8 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
         if constexpr (CROSS) WAVE_ORDER();
         else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
-    // ---- fhlastS1 (src/fwd2s1_simd.cc:241-262)
+    // ---- fhlastS1 (src/fwd2s1_simd.cc:241-262); the lane number is taken afresh rather than kept live through the passes
+    const int ln = __lane_id();
     DevResult R;
     R.score = SPDP_NEV16; R.mr = a_right; R.nr = b_right; R.ml = a_left; R.ulk = END_OF_ULK; R.maxr = 0;
     R.pad[0] = R.pad[1] = 0;
@@ -681,7 +693,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
         // first maximum over [lo, hi): returns index (lo if the range is empty)
         auto argmax_first = [&](int lo, int hi) {
             float bv = -3.0e38f; int bi = INT32_MAX;
-            for (int r = lo + lane; r < hi; r += 64) {
+            for (int r = lo + ln; r < hi; r += 64) {
                 const float v = as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW]));
                 if (v > bv) { bv = v; bi = r; }
             }
@@ -704,7 +716,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep_fp(SweepArgs A)
         if constexpr (UDH) R.ulk = ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW + 2]);
         R.maxr = maxr;
     }
-    if (lane == 0) A.res[pi] = R;
+    if (ln == 0) A.res[pi] = R;
 #undef BIDX
 }
 
