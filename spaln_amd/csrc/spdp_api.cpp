@@ -453,9 +453,10 @@ static int stripe_blocks(const DevProblem& P, int s, bool forward)
 // that its pool can be reused
 void DevRun::release() { if (in_flight && ctx) { (void) hipStreamSynchronize(strm()); in_flight = false; } }
 
+#define POOL_OF_RUN ctx->pool[side ? 8 : (flav == 7 ? 3 : (flav >= 5 ? 4 : flav))]
 #define POOLGET(dst, slot, bytes)                                                        \
     do {                                                                                 \
-        (dst) = ctx->pool[side ? 8 : (flav == 7 ? 3 : (flav >= 5 ? 4 : flav))].get((slot), (size_t) (bytes)); \
+        (dst) = POOL_OF_RUN.get((slot), (size_t) (bytes));                                \
         if (!(dst)) { ctx->err = "out of device memory"; return -1; }                    \
     } while (0)
 
@@ -695,44 +696,21 @@ int DevRun::build(const DevStore* st, const std::vector<RunItem>& items, int fla
         POOLGET(d_gprog, POOL_GPROG, sizeof(int) * words);
         HIPCHK(hipMemsetAsync(d_gprog, 0, sizeof(int) * words, strm()));
     }
-    // forwardS_ng / scorealoneS_ng: a problem's 64-row tiles as a pipeline of waves (SPDP_A0_PIPE=0: one wave each)
-    pipe_on = false;
-    if (flav >= 6 && flav <= 8 && n > 0) {
-        // -A1 engines: work item = (four problems, 16-row stripe), spdp_exact<., true>
-        const char* e = getenv("SPDP_A1_PIPE");
-        int mt = 1;
-        h_items.clear();
-        for (int q = 0; 4 * q < n; ++q) {
-            int ns = 1;
-            for (int j = 4 * q; j < std::min(n, 4 * q + 4); ++j)
-                ns = std::max(ns, (h_probs[j].a_right - h_probs[j].a_left + SPDP_NELEM - 1) / SPDP_NELEM);
-            mt = std::max(mt, ns);
-            for (int t = 0; t < ns; ++t) { h_items.push_back(q); h_items.push_back(t); }
-        }
-        if ((!e || atoi(e) != 0) && mt >= 2) {
-            pipe_on = true; pipe_tiles = mt;
-            pipe_stride = 2 + 7 * mt + max_n_im;
-            pipe_words = ((size_t) n * pipe_stride + 2 + 1) & ~(size_t) 1;
-            POOLGET(d_gprog, POOL_GPROG, sizeof(int) * (pipe_words + h_items.size()));
-        }
-    }
-    if ((flav == 3 || flav == 4 || flav == 5) && n > 0) {
-        const char* e = getenv("SPDP_A0_PIPE");
-        int mt = 1;
-        h_items.clear();
-        for (int j = 0; j < n; ++j) {
-            const DevProblem& P = h_probs[j];
-            const int r0 = P.a_left + (P.flags & 1);
-            const int th = flav == 5 ? std::max(1, std::min(64, P.imd_intvl)) : 64;
-            const int nt = std::max(1, (P.a_right - r0 + th) / th);          // as the kernel counts them
-            mt = std::max(mt, nt);
-            for (int t = 0; t < nt; ++t) { h_items.push_back(j); h_items.push_back(t); }
-        }
-        if ((!e || atoi(e) != 0) && mt >= 2 && !cut) {
-            pipe_on = true; pipe_tiles = mt;
-            pipe_stride = flav == 5 ? 2 + 9 * mt + max_n_im : 2 + 5 * mt;
-            pipe_words = ((size_t) n * pipe_stride + 2 + 1) & ~(size_t) 1;
-            POOLGET(d_gprog, POOL_GPROG, sizeof(int) * (pipe_words + h_items.size()));
+    // a problem's tiles / stripes as a pipeline of waves (TilePipe; SPDP_A1_PIPE=0, SPDP_A0_PIPE=0: one wave each)
+    pipe = TilePipe();
+    const bool a1 = flav >= 6 && flav <= 8;
+    if ((a1 || flav == 3 || flav == 4 || flav == 5) && n > 0) {
+        const char* e = getenv(a1 ? "SPDP_A1_PIPE" : "SPDP_A0_PIPE");
+        if (a1) pipe.plan_groups(h_probs, 4);           // -A1 engines: work item = (four problems, 16-row stripe), spdp_exact<., true>
+        else                                            // forwardS_ng / scorealoneS_ng: 64-row tiles; hirschbergS_ng: imd_intvl rows
+            for (int j = 0; j < n; ++j) {
+                const DevProblem& P = h_probs[j];
+                pipe.plan(j, P.a_right - (P.a_left + (P.flags & 1)), flav == 5 ? std::max(1, std::min(64, P.imd_intvl)) : 64);
+            }
+        const int mt = pipe.max_tiles;
+        const bool wanted = (!e || atoi(e) != 0) && mt >= 2 && !cut;
+        if (wanted && !pipe.reserve(POOL_OF_RUN, POOL_GPROG, n, a1 ? 2 + 7 * mt + max_n_im : (flav == 5 ? 2 + 9 * mt + max_n_im : 2 + 5 * mt))) {
+            ctx->err = "out of device memory"; return -1;
         }
     }
     if (n) HIPCHK(hipMemcpyAsync(d_probs, h_probs.data(), sizeof(DevProblem) * n, hipMemcpyHostToDevice, strm()));
@@ -746,13 +724,7 @@ int DevRun::launch()
     in_flight = true;
     if (flavour >= 3) {
         ScalarArgs S{};
-        if (pipe_on) {
-            int* w = (int*) d_gprog;
-            HIPCHK(hipMemsetAsync(w, 0, sizeof(int) * pipe_words, strm()));
-            HIPCHK(hipMemcpyAsync(w + pipe_words, h_items.data(), sizeof(int) * h_items.size(), hipMemcpyHostToDevice, strm()));
-            S.pipe = w; S.pipe_stride = pipe_stride; S.pipe_ticket = n * S.pipe_stride; S.max_tiles = pipe_tiles;
-            S.items = (const int2*) (w + pipe_words); S.n_items = (int) (h_items.size() / 2);
-        }
+        HIPCHK(pipe.arm(strm(), n, S));
         S.sc = (const DevScoring*) store->d_sc; S.probs = (const DevProblem*) d_probs; S.n_probs = n;
         S.a_codes = (const uint8_t*) store->d_a; S.cols = (const int2*) store->d_cols;
         S.aux = (const uint8_t*) store->d_aux; S.intpen = (const int16_t*) store->d_intpen;
@@ -778,8 +750,8 @@ int DevRun::launch()
             C.cpos = (int*) d_cpos; C.ranges = (int*) d_ranges; C.scores = (int*) d_scores;
             C.cpos_stride = 10 * (max_n_im + 1); C.strict = flavour == 8; C.local = store->sc.local ? 1 : 0;
             C.edge = (int*) d_scores + n;
-            C.pipe = (flavour == 8 && pipe_on) ? (const int*) d_gprog : nullptr;
-            C.pipe_stride = pipe_stride; C.rlf_off = 2 + 7 * pipe_tiles;
+            C.pipe = (flavour == 8 && pipe.on) ? pipe.d : nullptr;
+            C.pipe_stride = pipe.stride; C.rlf_off = 2 + 7 * pipe.max_tiles;
             HIPCHK(spdp_launch_cpos(&C, strm()));
         }
         return 0;
@@ -850,16 +822,13 @@ int DevRun::sync()
             HIPCHK(hipStreamSynchronize(strm()));
         }
     }
-    if (pipe_on) {
-        // a wave that waited in vain for the tile above it leaves a mark: the launch is repeated with one wave per problem
-        int mark[2] = {0, 0};
-        HIPCHK(spdp_copy_sync(mark, (int*) d_gprog + (size_t) n * pipe_stride, sizeof mark, hipMemcpyDeviceToHost, strm()));
-        if (mark[1] != 0 || getenv("SPDP_A0_PIPE_TEST_STALL")) {
-            ++ctx->rerun_stats[1];
-            pipe_on = false;
-            if (launch()) return -1;
-            HIPCHK(hipStreamSynchronize(strm()));
-        }
+    bool gave_up = false;                               // a wave waited in vain for the tile above it: repeated with one wave per problem
+    HIPCHK(pipe.stalled(strm(), n, &gave_up));
+    if (gave_up) {
+        ++ctx->rerun_stats[1];
+        pipe.on = false;
+        if (launch()) return -1;
+        HIPCHK(hipStreamSynchronize(strm()));
     }
     kernel_ms = 0.f;
     if (n) HIPCHK(hipEventElapsedTime(&kernel_ms, evb(), eve()));
@@ -870,7 +839,7 @@ int DevRun::sync()
             mcell = std::max<int64_t>(mcell, h_probs[j].cells);
         }
         fprintf(stderr, "[spdp run] flavour %d n %d cells %.3g (largest %.3g, rows <= %d, width <= %d) pipe %d items %zu  %.2f ms  %.1f GCUPS\n",
-                flavour, n, (double) total_cells, (double) mcell, mr, mc, (int) pipe_on, h_items.size() / 2, kernel_ms,
+                flavour, n, (double) total_cells, (double) mcell, mr, mc, (int) pipe.on, pipe.items.size() / 2, kernel_ms,
                 total_cells / (kernel_ms * 1e6));
     }
     return 0;

@@ -62,15 +62,21 @@ void spdp_stripe31(const SpdpProblemH* p, int sh, SpdpWindow* w)
     stripe31_rng(p->a_left, p->a_right, p->b_left, p->b_right, sh, w);
 }
 
-int64_t spdp_cells_h(const SpdpProblemH* p, const SpdpWindow* w)
-{   // (aa, nt) cells of the band as the scalar loops bound n, src/fwd2h1.cc:322-330
+static int64_t cells31_rng(int a_left, int a_right, int b_left, int b_right, const SpdpWindow& w)
+{   // (aa, nt) cells of the band as the scalar loops bound n, src/fwd2h1.cc:322-330 (the protein form of spdp_cells_w: three
+    // columns per row)
     int64_t c = 0;
-    for (int m = p->a_left + 1; m <= p->a_right; ++m) {
-        const int n0 = std::max(3 * m + w->lw - 1, p->b_left);
-        const int n9 = std::min(3 * m + w->up, p->b_right);
+    for (int m = a_left + 1; m <= a_right; ++m) {
+        const int n0 = std::max(3 * m + w.lw - 1, b_left);
+        const int n9 = std::min(3 * m + w.up, b_right);
         if (n9 > n0) c += n9 - n0;
     }
     return c;
+}
+
+int64_t spdp_cells_h(const SpdpProblemH* p, const SpdpWindow* w)
+{
+    return cells31_rng(p->a_left, p->a_right, p->b_left, p->b_right, *w);
 }
 
 // ---- resident inputs of a set of parent problems ------------------------------------------
@@ -285,14 +291,6 @@ static HItem item_of(const SpdpProblemH& p, int top, int sh)
     return it;
 }
 
-static int64_t cells_of(const HItem& it)
-{
-    SpdpProblemH q;
-    memset(&q, 0, sizeof q);
-    q.a_left = it.a_left; q.a_right = it.a_right; q.b_left = it.b_left; q.b_right = it.b_right;
-    return spdp_cells_h(&q, &it.w);
-}
-
 // descriptors shared by both engines
 static void fill_desc(const HStore& st, const HItem& it, DevProblemH& d)
 {
@@ -311,7 +309,7 @@ static void fill_desc(const HStore& st, const HItem& it, DevProblemH& d)
     d.a_len = st.probs[it.top].a_len; d.b_len = st.probs[it.top].b_len;
     d.cip_off = st.cip_off.empty() ? -1 : st.cip_off[it.top];
     d.a_pad = st.probs[it.top].a_pad;
-    d.cells = cells_of(it);
+    d.cells = cells31_rng(it.a_left, it.a_right, it.b_left, it.b_right, it.w);
 }
 
 // ---- forwardH1_wip over a list of items -----------------------------------------------------
@@ -322,6 +320,17 @@ struct HFwdOut {
     std::vector<SpdpSkl> skl;
     float sweep_ms = 0.f;
     int64_t cells = 0, tb_elems = 0;
+    void add_cost(const HFwdOut& o) { sweep_ms += o.sweep_ms; cells += o.cells; tb_elems = std::max(tb_elems, o.tb_elems); }
+    void append(const HFwdOut& o)               // the items of another launch behind these
+    {
+        if (off.empty()) off.push_back(0);
+        res.insert(res.end(), o.res.begin(), o.res.end());
+        n_skl.insert(n_skl.end(), o.n_skl.begin(), o.n_skl.end());
+        const int64_t base = off.back();
+        for (size_t i = 1; i < o.off.size(); ++i) off.push_back(base + o.off[i]);
+        skl.insert(skl.end(), o.skl.begin(), o.skl.end());
+        add_cost(o);
+    }
 };
 
 static int run_forward_group(HStore& st, const std::vector<HItem>& items, bool walk, HFwdOut& out)
@@ -443,103 +452,93 @@ static int run_forward(HStore& st, const std::vector<HItem>& items, bool walk, H
     cut.push_back(nr);
     if (cut.size() == 2) return run_forward_group(st, items, walk, out);
     out = HFwdOut();
-    out.off.assign(1, 0);
     for (size_t g = 0; g + 1 < cut.size(); ++g) {
         std::vector<HItem> part(items.begin() + cut[g], items.begin() + cut[g + 1]);
         HFwdOut po;
         if (run_forward_group(st, part, walk, po)) return -1;
-        out.res.insert(out.res.end(), po.res.begin(), po.res.end());
-        out.n_skl.insert(out.n_skl.end(), po.n_skl.begin(), po.n_skl.end());
-        const int64_t base = out.off.back();
-        for (size_t i = 1; i < po.off.size(); ++i) out.off.push_back(base + po.off[i]);
-        out.skl.insert(out.skl.end(), po.skl.begin(), po.skl.end());
-        out.sweep_ms += po.sweep_ms; out.cells += po.cells; out.tb_elems = std::max(out.tb_elems, po.tb_elems);
+        out.append(po);
     }
     return 0;
 }
 
-// ---- the -A0 wavefront kernels with the tiles of a problem as a pipeline of waves (spdh_rowwave<., true>) ----
-// The work list (problem, tile) in dispatch order behind the sync words of the problems; on whenever a problem has
-// two tiles or more (SPDP_A0_PIPE=0: one wave per problem).  A wave that waited in vain for the tile above it
-// leaves a mark and the caller repeats the launch without the pipeline.
-struct HPipe {
-    std::vector<int> items;
-    int max_tiles = 1, stride = 0;
-    size_t words = 0;
-    int* d = nullptr;
-    bool on = false;
-};
-static int pipe_setup(SpdpContext* ctx, DevPool& pool, int slot, const std::vector<DevProblemH>& probs, bool udh, int max_im, HPipe& pp)
+// ---- what the runners of the -A0 / -A1 engines share ---------------------------------------------------------------
+// the argument block as far as it comes from the store; the runner sets its work and output pointers on top
+static HScalarArgs scalar_args(const HStore& st, const void* d_probs, int n, int noll)
 {
-    pp = HPipe();
-    const char* e = getenv("SPDP_A0_PIPE");
-    for (size_t j = 0; j < probs.size(); ++j) {
-        const DevProblemH& P = probs[j];
-        const int r0 = P.a_left + (P.a_exgl ? 1 : 0);
-        const int th = udh ? std::max(1, std::min(64, P.imd_intvl)) : 64;
-        const int nt = std::max(1, (P.a_right - r0 + th) / th);              // as the kernel counts them
-        pp.max_tiles = std::max(pp.max_tiles, nt);
-        for (int t = 0; t < nt; ++t) { pp.items.push_back((int) j); pp.items.push_back(t); }
-    }
-    if ((e && atoi(e) == 0) || pp.max_tiles < 2) return 0;
-    // (Rounds 2 / 3 switched the pipeline off once every SIMD had a problem of its own: the kernels then ran ONE wave per
-    // SIMD -- 256 VGPRs and a handful of AGPRs -- and the pipeline only added memory-side traffic.  Held to 256 registers
-    // (amdgpu_waves_per_eu(2, 2), spdp_h_rowwave.hip) two waves share a SIMD and the pipeline pays at every size measured:
-    // 1000 x 400 aa 2.9 -> 5.1 GCUPS, 1827 problems 3.7 - 4.6 (one wave per problem) -> 5.7.)
-    pp.stride = 2 + 9 * pp.max_tiles + 3 * max_im;
-    pp.words = (probs.size() * (size_t) pp.stride + 2 + 1) & ~(size_t) 1;
-    pp.d = (int*) pool.get(slot, sizeof(int) * (pp.words + pp.items.size()));
-    if (!pp.d) { ctx->err = "device allocation failed (tile pipeline of the scalar aa x genome engines)"; return -1; }
-    pp.on = true;
-    return 0;
-}
-static int pipe_arm(SpdpContext* ctx, const HPipe& pp, int n_probs, HScalarArgs& A)
-{
-    A.pipe = nullptr;
-    if (!pp.on) return 0;
-    HIPCHK(hipMemsetAsync(pp.d, 0, sizeof(int) * pp.words, ctx->stream));
-    HIPCHK(hipMemcpyAsync(pp.d + pp.words, pp.items.data(), sizeof(int) * pp.items.size(), hipMemcpyHostToDevice, ctx->stream));
-    A.pipe = pp.d; A.pipe_stride = pp.stride; A.pipe_ticket = n_probs * pp.stride; A.max_tiles = pp.max_tiles;
-    A.items = (const int2*) (pp.d + pp.words); A.n_items = (int) (pp.items.size() / 2);
-    return 0;
-}
-// after the launch has finished: 1 = a wave gave up (repeat without the pipeline), 0 = fine
-static int pipe_stalled(SpdpContext* ctx, const HPipe& pp, int n_probs)
-{
-    if (!pp.on) return 0;
-    int mark[2] = {0, 0};
-    HIPCHK(spdp_copy_sync(mark, pp.d + (size_t) n_probs * pp.stride, sizeof mark, hipMemcpyDeviceToHost, ctx->stream));
-    return (mark[1] != 0 || getenv("SPDP_A0_PIPE_TEST_STALL")) ? 1 : 0;
+    HScalarArgs A;
+    memset(&A, 0, sizeof A);
+    A.sc = (const DevScoringH*) st.d_sc; A.probs = (const DevProblemH*) d_probs; A.n_probs = n;
+    A.a_codes = (const uint8_t*) st.d_a; A.cols = (const int4*) st.d_cols; A.aux = (const short4*) st.d_aux;
+    A.intpen = (const int16_t*) st.d_intpen; A.intpen_len = st.sc.intpen_len;
+    A.ipen_runs = st.ipen_runs_ok ? (const int16_t*) st.d_intpen + st.sc.intpen_len : nullptr;
+    A.minl = st.sc.minl ? st.sc.minl : st.sc.llmt;
+    A.gape1 = st.sc.gape1; A.gape2 = st.sc.gape2; A.extragop = st.sc.extragop;
+    A.noll = noll; A.lgop = st.sc.lgop;
+    memcpy(A.t53, st.sc.t53, sizeof A.t53);
+    spdp_genetic_code_tables(A.mid, A.tron_of);
+    A.cip = (const int*) st.d_cip;
+    return A;
 }
 
-// the -A1 engines (spdh_exact): a pipelined work item is (G problems, stripe of 16 rows), one wave each; G = 4 once the
-// launch fills the chip that way, fewer before.  SPDP_HX_PIPE=0: the stripes of a problem one after the other in one
-// 16-lane group; SPDP_HX_GROUPS=1|2|4 forces G.
-static int pipe_setup_exact(SpdpContext* ctx, DevPool& pool, int slot, const std::vector<DevProblemH>& probs, int max_im, HPipe& pp, int& G, bool nopipe = false)
+// The tile pipeline (TilePipe, spdp_internal.h) of a launch; udh: of a linear-space run (HU_POOL, up to max_im intermediate rows).
+// -A0 (spdh_rowwave<., true>; udh: tiles of imd_intvl rows): on whenever a problem has two tiles or more (SPDP_A0_PIPE=0: one
+// wave per problem).
+// (Rounds 2 / 3 switched the pipeline off once every SIMD had a problem of its own: the kernels then ran ONE wave per
+// SIMD -- 256 VGPRs and a handful of AGPRs -- and the pipeline only added memory-side traffic.  Held to 256 registers
+// (amdgpu_waves_per_eu(2, 2), spdp_h_rowwave.hip) two waves share a SIMD and the pipeline pays at every size measured:
+// 1000 x 400 aa 2.9 -> 5.1 GCUPS, 1827 problems 3.7 - 4.6 (one wave per problem) -> 5.7.)
+// -A1 (spdh_exact): a pipelined work item is (G problems, stripe of 16 rows), one wave each; G = 4 once the launch fills
+// the chip that way, fewer before.  SPDP_HX_PIPE=0: the stripes of a problem one after the other in one 16-lane group;
+// SPDP_HX_GROUPS=1|2|4 forces G.
+static int pipe_plan(SpdpContext* ctx, const std::vector<DevProblemH>& probs, bool exact, bool udh, int max_im, bool nopipe, TilePipe& pp, int& G)
 {
-    pp = HPipe();
-    const int n = (int) probs.size();
-    int64_t stripes = 0;
-    for (const DevProblemH& P : probs) {
-        const int ns = std::max(1, (P.a_right - P.a_left + 15) / 16);
-        pp.max_tiles = std::max(pp.max_tiles, ns);
-        stripes += ns;
+    pp = TilePipe();
+    const char* e = getenv(exact ? "SPDP_HX_PIPE" : "SPDP_A0_PIPE");
+    const bool wanted = !nopipe && !(e && atoi(e) == 0);
+    if (exact) {
+        int64_t stripes = 0;
+        for (const DevProblemH& P : probs) stripes += std::max(1, (P.a_right - P.a_left + 15) / 16);
+        G = stripes >= 4 * 4096 ? 4 : (stripes >= 2 * 4096 ? 2 : 1);
+        if (const char* g = getenv("SPDP_HX_GROUPS")) { const int v = atoi(g); if (v == 1 || v == 2 || v == 4) G = v; }
+        if (wanted) pp.plan_groups(probs, G);
+    } else
+        for (size_t j = 0; j < probs.size(); ++j) {
+            const DevProblemH& P = probs[j];
+            pp.plan((int) j, P.a_right - (P.a_left + (P.a_exgl ? 1 : 0)), udh ? std::max(1, std::min(64, P.imd_intvl)) : 64);
+        }
+    if (!wanted || pp.max_tiles < 2) return 0;
+    if (!pp.reserve(ctx->pool[udh ? HU_POOL : H_POOL], udh ? HU_PIPE : HP_PIPE, (int) probs.size(), 2 + (exact ? 7 : 9) * pp.max_tiles + 3 * max_im)) {
+        ctx->err = "device allocation failed (tile / stripe pipeline of the aa x genome engines)";
+        return -1;
     }
-    G = stripes >= 4 * 4096 ? 4 : (stripes >= 2 * 4096 ? 2 : 1);
-    if (const char* e = getenv("SPDP_HX_GROUPS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) G = v; }
-    const char* e = getenv("SPDP_HX_PIPE");
-    if (nopipe || (e && atoi(e) == 0) || pp.max_tiles < 2) return 0;
-    for (int q = 0; q * G < n; ++q) {
-        int ns = 1;
-        for (int j = q * G; j < std::min(n, (q + 1) * G); ++j) ns = std::max(ns, std::max(1, (probs[j].a_right - probs[j].a_left + 15) / 16));
-        for (int t = 0; t < ns; ++t) { pp.items.push_back(q); pp.items.push_back(t); }
-    }
-    pp.stride = 2 + 7 * pp.max_tiles + 3 * max_im;
-    pp.words = ((size_t) n * pp.stride + 2 + 1) & ~(size_t) 1;
-    pp.d = (int*) pool.get(slot, sizeof(int) * (pp.words + pp.items.size()));
-    if (!pp.d) { ctx->err = "device allocation failed (stripe pipeline of the -A1 aa x genome engines)"; return -1; }
-    pp.on = true;
     return 0;
+}
+
+// arms the pipeline and launches; a launch in which a wave gave up its wait runs again, one wave per problem
+template <class Launch>
+static int launch_piped(SpdpContext* ctx, TilePipe& pp, int n, HScalarArgs& A, Launch launch)
+{
+    for (;;) {
+        HIPCHK(pp.arm(ctx->stream, n, A));
+        HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+        HIPCHK(launch());
+        HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+        if (!pp.on) return 0;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        bool gave_up = false;
+        HIPCHK(pp.stalled(ctx->stream, n, &gave_up));
+        if (!gave_up) return 0;
+        pp.on = false;                                  // the second launch cannot stall
+    }
+}
+
+// -A1, pipelined: a result whose walk met a link word the reference leaves from stripe to stripe (spdp_h_exact.hip:
+// HXPOISON) runs again, one 16-lane group per problem: their indices, and the items to run in `part`
+static std::vector<int> poisoned(bool piped, const std::vector<DevResultH>& res, const std::vector<HItem>& items, std::vector<HItem>& part)
+{
+    std::vector<int> redo;
+    for (size_t i = 0; piped && i < res.size(); ++i) if (res[i].pad[1]) { redo.push_back((int) i); part.push_back(items[i]); }
+    return redo;
 }
 
 // ---- scalar forwardH_ng over a list of items (spdp_h_rowwave.hip) ------------------------------
@@ -597,36 +596,15 @@ static int run_scalar_group(HStore& st, const std::vector<HItem>& items, bool fo
         return -1;
     }
     HIPCHK(hipMemcpyAsync(d_probs, h_probs.data(), nr * sizeof(DevProblemH), hipMemcpyHostToDevice, ctx->stream));
-    HScalarArgs A;
-    memset(&A, 0, sizeof A);
-    A.sc = (const DevScoringH*) st.d_sc; A.probs = (const DevProblemH*) d_probs; A.n_probs = nr;
-    A.a_codes = (const uint8_t*) st.d_a; A.cols = (const int4*) st.d_cols; A.aux = (const short4*) st.d_aux;
-    A.intpen = (const int16_t*) st.d_intpen; A.intpen_len = st.sc.intpen_len;
-    A.ipen_runs = st.ipen_runs_ok ? (const int16_t*) st.d_intpen + st.sc.intpen_len : nullptr;
-    A.minl = st.sc.minl ? st.sc.minl : st.sc.llmt;
-    A.gape1 = st.sc.gape1; A.gape2 = st.sc.gape2; A.extragop = st.sc.extragop;
-    A.noll = (!exact && st.sc.noll == 3) ? 3 : 2; A.lgop = st.sc.lgop;
-    memcpy(A.t53, st.sc.t53, sizeof A.t53);
-    spdp_genetic_code_tables(A.mid, A.tron_of);
-    A.cip = (const int*) st.d_cip;
+    HScalarArgs A = scalar_args(st, d_probs, nr, (!exact && st.sc.noll == 3) ? 3 : 2);
     A.work = (int*) d_work; A.vmf = (int3*) d_vmf; A.res = (DevResultH*) d_res;
     A.skl = (int2*) d_skl; A.n_skl = (int*) d_nskl; A.skl_cap = skl_cap;
-    HPipe pp;
-    if (exact) { if (pipe_setup_exact(ctx, pool, HP_PIPE, h_probs, 0, pp, A.item_probs, nopipe)) return -1; }
-    else if (!cut && A.noll != 3 && pipe_setup(ctx, pool, HP_PIPE, h_probs, false, 0, pp)) return -1;     // (the cut-range variant and double affine gaps run one wave per problem)
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (pipe_arm(ctx, pp, nr, A)) return -1;
-        HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-        if (exact) HIPCHK(spdh_launch_exact(0, &A, ctx->stream));
-        else HIPCHK(spdh_launch_scalar(cut ? 2 : (forward ? 1 : 0), &A, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-        if (!pp.on) break;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        const int st_ = pipe_stalled(ctx, pp, nr);
-        if (st_ < 0) return -1;
-        if (!st_) break;
-        pp.on = false;
-    }
+    TilePipe pp;
+    if ((exact || (!cut && A.noll != 3)) &&             // (the cut-range variant and double affine gaps run one wave per problem)
+        pipe_plan(ctx, h_probs, exact, false, 0, nopipe, pp, A.item_probs)) return -1;
+    if (launch_piped(ctx, pp, nr, A, [&] {
+            return exact ? spdh_launch_exact(0, &A, ctx->stream) : spdh_launch_scalar(cut ? 2 : (forward ? 1 : 0), &A, ctx->stream);
+        })) return -1;
     out.res.resize(nr); out.n_skl.assign(nr, 0); out.off.assign(nr + 1, 0);
     HIPCHK(hipMemcpyAsync(out.res.data(), d_res, nr * sizeof(DevResultH), hipMemcpyDeviceToHost, ctx->stream));
     std::vector<int2> skl;
@@ -641,14 +619,10 @@ static int run_scalar_group(HStore& st, const std::vector<HItem>& items, bool fo
         fprintf(stderr, "[spdp run] aa x genome %s forward=%d n %d cells %.3g pipe %d items %zu  %.2f ms  %.2f GCUPS\n",
                 exact ? "-A1" : "-A0", (int) forward, nr, (double) out.cells, (int) pp.on, pp.items.size() / 2, out.sweep_ms,
                 out.cells / (out.sweep_ms * 1e6));
-    // -A1, pipelined: a result whose walk met a link word the reference leaves from stripe to stripe (spdp_h_exact.hip:
-    // HXPOISON) runs again, one 16-lane group per problem
-    std::vector<int> redo;
-    for (int i = 0; exact && pp.on && i < nr; ++i) if (out.res[i].pad[1]) redo.push_back(i);
+    std::vector<HItem> part;
+    const std::vector<int> redo = poisoned(exact && pp.on, out.res, items, part);
     HFwdOut ro;
     if (!redo.empty()) {
-        std::vector<HItem> part;
-        for (int i : redo) part.push_back(items[i]);
         if (run_scalar_group(st, part, forward, ro, exact, scale, cut, true)) return -1;
         out.sweep_ms += ro.sweep_ms;                    // (the second run is part of what the call cost)
         for (size_t k = 0; k < redo.size(); ++k) { out.res[redo[k]] = ro.res[k]; out.n_skl[redo[k]] = ro.n_skl[k]; }
@@ -704,22 +678,19 @@ static int run_scalar(HStore& st, const std::vector<HItem>& items, bool forward,
         std::vector<int> again;
         // launches of about equal size (a last small one runs at a fraction of the rate of a full one)
         size_t total = 0;
-        for (int i : todo) { DevProblemH d; fill_desc(st, items[i], d); total += (size_t) vmf_budget_h(d, scale) * sizeof(int3); }
+        std::vector<size_t> bytes(nr, 0);               // record budget of an item at this scale
+        for (int i : todo) { DevProblemH d; fill_desc(st, items[i], d); total += bytes[i] = (size_t) vmf_budget_h(d, scale) * sizeof(int3); }
         const size_t n_launch = std::max<size_t>(1, (total + limit - 1) / limit);
         const size_t even = std::min(limit, total / n_launch + total / n_launch / 16 + 1);
         for (size_t lo = 0; lo < todo.size(); ) {
             size_t hi = lo, sum = 0;
             std::vector<HItem> part;
-            while (hi < todo.size()) {
-                DevProblemH d;
-                fill_desc(st, items[todo[hi]], d);
-                const size_t bytes = (size_t) vmf_budget_h(d, scale) * sizeof(int3);
-                if (hi > lo && sum + bytes > even) break;
-                sum += bytes; part.push_back(items[todo[hi++]]);
+            while (hi < todo.size() && !(hi > lo && sum + bytes[todo[hi]] > even)) {
+                sum += bytes[todo[hi]]; part.push_back(items[todo[hi++]]);
             }
             HFwdOut po;
             if (run_scalar_group(st, part, true, po, exact, scale, cut)) return -1;
-            out.sweep_ms += po.sweep_ms; out.cells += po.cells;
+            out.add_cost(po);
             for (size_t k = lo; k < hi; ++k) {
                 const int i = todo[k], c = po.n_skl[k - lo];
                 if (c == -3) { again.push_back(i); continue; }
@@ -738,17 +709,45 @@ static int run_scalar(HStore& st, const std::vector<HItem>& items, bool forward,
     return 0;
 }
 
-// ---- scalar hirschbergH_ng over a list of items (spdp_h_rowwave.hip) ----------------------------
-struct HUdhOut;
-// engine: 0 hirschbergH_ng (scalar), 1 hirschbergH1 (-A1), 2 hirschbergH1_wip with local ends (-LS)
-static int run_scalar_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out, std::vector<int>& flags, int engine = 0, bool nopipe = false);
-
 // ---- hirschbergH1_wip over a list of items ------------------------------------------------------
 struct HUdhOut {
     std::vector<int32_t> scores, cpos, ranges;  // in item order; cpos stride = stride ints per item
     int stride = 0;
     float sweep_ms = 0.f;
     int64_t cells = 0;
+};
+
+// the output buffers of a linear-space launch (HU_POOL), behind its problems / work / intermediate rows
+struct HUdhBufs {
+    int n = 0, max_im = 1, stride = 0;          // stride: ints of one item's cpos, (max n_im + 1) Dim10 rows
+    void *d_res = nullptr, *d_cpos = nullptr, *d_ranges = nullptr, *d_scores = nullptr;
+    bool alloc(DevPool& pool, const std::vector<HItem>& items)
+    {
+        n = (int) items.size();
+        for (const HItem& it : items) max_im = std::max(max_im, it.n_im);
+        stride = (max_im + 1) * 10;
+        d_res = pool.get(HU_RES, n * sizeof(DevResultH));
+        d_cpos = pool.get(HU_CPOS, (size_t) n * stride * sizeof(int));
+        d_ranges = pool.get(HU_RANGES, (size_t) n * 4 * sizeof(int));
+        d_scores = pool.get(HU_SCORES, (size_t) n * sizeof(int));
+        return d_res && d_cpos && d_ranges && d_scores;
+    }
+    // reads everything back (res: the result records too), waits, and takes the sweep's time from ev0 / ev1
+    int fetch(SpdpContext* ctx, HUdhOut& out, std::vector<DevResultH>* res = nullptr)
+    {
+        out.stride = stride;
+        out.scores.resize(n); out.cpos.resize((size_t) n * stride); out.ranges.resize((size_t) n * 4);
+        HIPCHK(hipMemcpyAsync(out.scores.data(), d_scores, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out.cpos.data(), d_cpos, (size_t) n * stride * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out.ranges.data(), d_ranges, (size_t) n * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (res) {
+            res->resize(n);
+            HIPCHK(hipMemcpyAsync(res->data(), d_res, n * sizeof(DevResultH), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipEventElapsedTime(&out.sweep_ms, ctx->ev0, ctx->ev1));
+        return 0;
+    }
 };
 
 static int run_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out)
@@ -758,9 +757,7 @@ static int run_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out)
     const int nr = (int) items.size();
     out = HUdhOut();
     if (!nr) return 0;
-    int max_im = 1;
-    for (const HItem& it : items) max_im = std::max(max_im, it.n_im);
-    out.stride = (max_im + 1) * 10;
+    HUdhBufs B;
     std::vector<DevProblemH> h_probs(nr);
     int64_t bnd_ent = 0, imd_int = 0;
     for (int i = 0; i < nr; ++i) {
@@ -775,11 +772,7 @@ static int run_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out)
     void* d_probs = pool.get(HU_PROBS, nr * sizeof(DevProblemH));
     void* d_bnd = pool.get(HU_BND, (size_t) bnd_ent * sizeof(int4));
     void* d_imd = pool.get(HU_IMD, (size_t) std::max<int64_t>(imd_int, 1) * sizeof(int));
-    void* d_res = pool.get(HU_RES, nr * sizeof(DevResultH));
-    void* d_cpos = pool.get(HU_CPOS, (size_t) nr * out.stride * sizeof(int));
-    void* d_ranges = pool.get(HU_RANGES, (size_t) nr * 4 * sizeof(int));
-    void* d_scores = pool.get(HU_SCORES, (size_t) nr * sizeof(int));
-    if (!d_probs || !d_bnd || !d_imd || !d_res || !d_cpos || !d_ranges || !d_scores) {
+    if (!B.alloc(pool, items) || !d_probs || !d_bnd || !d_imd) {
         ctx->err = "device allocation failed (aa x genome linear-space run)";
         return -1;
     }
@@ -787,25 +780,21 @@ static int run_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out)
     HUdhArgs A;
     A.sc = (const DevScoringH*) st.d_sc; A.probs = (const DevProblemH*) d_probs; A.n_probs = nr;
     A.a_codes = (const uint8_t*) st.d_a; A.cols = (const int4*) st.d_cols; A.aux = (const short4*) st.d_aux;
-    A.bnd = (int4*) d_bnd; A.imd = (int*) d_imd; A.res = (DevResultH*) d_res;
+    A.bnd = (int4*) d_bnd; A.imd = (int*) d_imd; A.res = (DevResultH*) B.d_res;
     const int pen_cap = st.sc.nquant > 1 ? st.sc.qm_len[st.sc.nquant - 2] + 1 : 0;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     HIPCHK(spdh_launch_udh(&A, st.sc.spj, pen_cap, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     HCposArgs Cc;
     Cc.probs = A.probs; Cc.n_probs = nr; Cc.imd = A.imd; Cc.res = A.res;
-    Cc.cpos = (int*) d_cpos; Cc.ranges = (int*) d_ranges; Cc.scores = (int*) d_scores; Cc.cpos_stride = out.stride;
+    Cc.cpos = (int*) B.d_cpos; Cc.ranges = (int*) B.d_ranges; Cc.scores = (int*) B.d_scores; Cc.cpos_stride = B.stride;
     HIPCHK(spdh_launch_cpos(&Cc, ctx->stream));
-    out.scores.resize(nr); out.cpos.resize((size_t) nr * out.stride); out.ranges.resize((size_t) nr * 4);
-    HIPCHK(hipMemcpyAsync(out.scores.data(), d_scores, nr * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(out.cpos.data(), d_cpos, (size_t) nr * out.stride * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(out.ranges.data(), d_ranges, (size_t) nr * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipEventElapsedTime(&out.sweep_ms, ctx->ev0, ctx->ev1));
-    return 0;
+    return B.fetch(ctx, out);
 }
 
-static int run_scalar_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out, std::vector<int>& flags, int engine, bool nopipe)
+// ---- scalar hirschbergH_ng over a list of items (spdp_h_rowwave.hip) ----------------------------
+// engine: 0 hirschbergH_ng (scalar), 1 hirschbergH1 (-A1), 2 hirschbergH1_wip with local ends (-LS)
+static int run_scalar_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& out, std::vector<int>& flags, int engine = 0, bool nopipe = false)
 {
     const bool exact = engine != 0;
     SpdpContext* ctx = lane_of(st);
@@ -815,16 +804,14 @@ static int run_scalar_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& 
     flags.assign(nr, 0);
     if (!nr) return 0;
     if (engine != 2 && !st.scalar_ok) { ctx->err = "the scalar engine needs SpdpScoringH.intpen / t53 and SpdpProblemH.dinc"; return -1; }
-    int max_im = 1;
-    for (const HItem& it : items) max_im = std::max(max_im, it.n_im);
-    out.stride = (max_im + 1) * 10;
+    HUdhBufs B;
+    const int noll = (engine == 0 && st.sc.noll == 3) ? 3 : 2;            // (Noll = 3: F2 planes, a third plane of links per intermediate row)
     std::vector<DevProblemH> h_probs(nr);
     int64_t work_int = 0, imd_int = 0;
     for (int i = 0; i < nr; ++i) {
         DevProblemH& d = h_probs[i];
         fill_desc(st, items[i], d);
         d.bnd_off = work_int;
-        const int noll = (engine == 0 && st.sc.noll == 3) ? 3 : 2;        // (Noll = 3: F2 planes, a third plane of links per intermediate row)
         work_int += exact ? 6ll * d.buf_size + 8 : 6ll * (noll * ((int64_t) d.width + 4));
         d.imd_off = imd_int;
         imd_int += (int64_t) d.n_im * 4 * noll * d.width;
@@ -833,68 +820,35 @@ static int run_scalar_udh(HStore& st, const std::vector<HItem>& items, HUdhOut& 
     void* d_probs = pool.get(HU_PROBS, nr * sizeof(DevProblemH));
     void* d_work = pool.get(HU_BND, (size_t) work_int * sizeof(int));
     void* d_imd = pool.get(HU_IMD, (size_t) std::max<int64_t>(imd_int, 1) * sizeof(int));
-    void* d_res = pool.get(HU_RES, nr * sizeof(DevResultH));
-    void* d_cpos = pool.get(HU_CPOS, (size_t) nr * out.stride * sizeof(int));
-    void* d_ranges = pool.get(HU_RANGES, (size_t) nr * 4 * sizeof(int));
-    void* d_scores = pool.get(HU_SCORES, (size_t) nr * sizeof(int));
-    if (!d_probs || !d_work || !d_imd || !d_res || !d_cpos || !d_ranges || !d_scores) {
+    if (!B.alloc(pool, items) || !d_probs || !d_work || !d_imd) {
         ctx->err = "device allocation failed (scalar aa x genome linear-space run)";
         return -1;
     }
     HIPCHK(hipMemcpyAsync(d_probs, h_probs.data(), nr * sizeof(DevProblemH), hipMemcpyHostToDevice, ctx->stream));
-    HScalarArgs A;
-    memset(&A, 0, sizeof A);
-    A.sc = (const DevScoringH*) st.d_sc; A.probs = (const DevProblemH*) d_probs; A.n_probs = nr;
-    A.a_codes = (const uint8_t*) st.d_a; A.cols = (const int4*) st.d_cols; A.aux = (const short4*) st.d_aux;
-    A.intpen = (const int16_t*) st.d_intpen; A.intpen_len = st.sc.intpen_len;
-    A.ipen_runs = st.ipen_runs_ok ? (const int16_t*) st.d_intpen + st.sc.intpen_len : nullptr;
-    A.minl = st.sc.minl ? st.sc.minl : st.sc.llmt;
-    A.gape1 = st.sc.gape1; A.gape2 = st.sc.gape2; A.extragop = st.sc.extragop;
-    A.noll = (engine == 0 && st.sc.noll == 3) ? 3 : 2; A.lgop = st.sc.lgop;
-    memcpy(A.t53, st.sc.t53, sizeof A.t53);
-    spdp_genetic_code_tables(A.mid, A.tron_of);
-    A.cip = (const int*) st.d_cip;
-    A.work = (int*) d_work; A.res = (DevResultH*) d_res;
-    A.imd = (int*) d_imd; A.cpos = (int*) d_cpos; A.ranges = (int*) d_ranges; A.scores = (int*) d_scores;
-    A.cpos_stride = out.stride;
-    HPipe pp;
-    if (engine == 1) { if (pipe_setup_exact(ctx, pool, HU_PIPE, h_probs, max_im, pp, A.item_probs, nopipe)) return -1; }
-    else if (engine == 0 && A.noll != 3 && pipe_setup(ctx, pool, HU_PIPE, h_probs, true, max_im, pp)) return -1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (pipe_arm(ctx, pp, nr, A)) return -1;
-        HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-        if (engine == 2) HIPCHK(spdh_launch_local_udh(&A, ctx->stream));
-        else if (exact) HIPCHK(spdh_launch_exact(1, &A, ctx->stream));
-        else HIPCHK(spdh_launch_scalar_udh(&A, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-        if (!pp.on) break;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        const int st_ = pipe_stalled(ctx, pp, nr);
-        if (st_ < 0) return -1;
-        if (!st_) break;
-        pp.on = false;
-    }
-    out.scores.resize(nr); out.cpos.resize((size_t) nr * out.stride); out.ranges.resize((size_t) nr * 4);
-    std::vector<DevResultH> res(nr);
-    HIPCHK(hipMemcpyAsync(out.scores.data(), d_scores, nr * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(out.cpos.data(), d_cpos, (size_t) nr * out.stride * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(out.ranges.data(), d_ranges, (size_t) nr * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(res.data(), d_res, nr * sizeof(DevResultH), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipEventElapsedTime(&out.sweep_ms, ctx->ev0, ctx->ev1));
+    HScalarArgs A = scalar_args(st, d_probs, nr, noll);
+    A.work = (int*) d_work; A.res = (DevResultH*) B.d_res;
+    A.imd = (int*) d_imd; A.cpos = (int*) B.d_cpos; A.ranges = (int*) B.d_ranges; A.scores = (int*) B.d_scores;
+    A.cpos_stride = B.stride;
+    TilePipe pp;
+    if ((engine == 1 || (engine == 0 && noll != 3)) &&
+        pipe_plan(ctx, h_probs, engine == 1, true, B.max_im, nopipe, pp, A.item_probs)) return -1;
+    if (launch_piped(ctx, pp, nr, A, [&] {
+            return engine == 2 ? spdh_launch_local_udh(&A, ctx->stream)
+                               : (exact ? spdh_launch_exact(1, &A, ctx->stream) : spdh_launch_scalar_udh(&A, ctx->stream));
+        })) return -1;
+    std::vector<DevResultH> res;
+    if (B.fetch(ctx, out, &res)) return -1;
     if (getenv("SPDP_TRACE_RUNS"))
         fprintf(stderr, "[spdp run] aa x genome linear space engine %d n %d cells %.3g pipe %d items %zu  %.2f ms  %.2f GCUPS\n",
                 engine, nr, (double) out.cells, (int) pp.on, pp.items.size() / 2, out.sweep_ms, out.cells / (out.sweep_ms * 1e6));
     for (int i = 0; i < nr; ++i) flags[i] = exact ? 0 : res[i].pad[0];
-    // -A1, pipelined: dead results run again in the one-group form (see run_scalar_group)
-    std::vector<int> redo;
-    for (int i = 0; engine == 1 && pp.on && i < nr; ++i) if (res[i].pad[1]) redo.push_back(i);
+    // -A1, pipelined: dead results run again in the one-group form (see poisoned)
+    std::vector<HItem> part;
+    const std::vector<int> redo = poisoned(engine == 1 && pp.on, res, items, part);
     if (getenv("SPDP_TRACE_RUNS") && engine == 1 && pp.on) {
         fprintf(stderr, "[spdp run] -A1 linear space: %zu of %d results run again without the pipeline\n", redo.size(), nr);
     }
     if (!redo.empty()) {
-        std::vector<HItem> part;
-        for (int i : redo) part.push_back(items[i]);
         HUdhOut ro;
         std::vector<int> rf;
         if (run_scalar_udh(st, part, ro, rf, engine, true)) return -1;

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <cstdlib>
 #include <functional>
 #include <string>
 #include <vector>
@@ -248,6 +250,67 @@ static inline hipError_t spdp_copy_sync(void* dst, const void* src, size_t n, hi
     return e != hipSuccess ? e : hipStreamSynchronize(s);
 }
 
+// Host side of the tile / stripe pipelines of the -A0 and -A1 engines, cDNA and protein alike (device side: spdp_pipe.h).
+// The tiles of a problem run as a pipeline of waves: the work list (problem, tile) in dispatch order lies behind the sync
+// words of the problems and their {ticket, stalled} pair.  A wave that waited in vain for the tile above it leaves a mark,
+// and the caller repeats the launch without the pipeline.  Whether a pipeline is wanted (SPDP_A0_PIPE, SPDP_A1_PIPE,
+// SPDP_HX_PIPE, cut ranges, Noll = 3) is the caller's decision.
+//
+// Sync words per problem (`stride`, mt = max_tiles): {records, overflow}, prog[mt], best[mt][.], and what the
+// intermediate rows of a linear-space run hand down:
+//                      -A0 forward / score   -A0 linear space        -A1 (max_im = 0 unless linear space)
+//   cDNA  (ScalarArgs)   2 + 5 mt              2 + 9 mt + max_im       2 + 7 mt + max_im
+//   aa    (HScalarArgs)  2 + 9 mt              2 + 9 mt + 3 max_im     2 + 7 mt + 3 max_im
+struct TilePipe {
+    std::vector<int> items;                 // (problem or group, tile) pairs in dispatch order
+    int max_tiles = 1;                      // most tiles of one problem
+    int stride = 0;                         // sync words per problem
+    size_t words = 0;                       // sync words ahead of the item list
+    int* d = nullptr;                       // words, then items (owned by the pool reserve() took it from)
+    bool on = false;
+
+    void add(int j, int nt) { max_tiles = std::max(max_tiles, nt); for (int t = 0; t < nt; ++t) { items.push_back(j); items.push_back(t); } }
+    // -A0: problem j's tiles of th rows; rows = from the first tiled row to a_right
+    void plan(int j, int rows, int th) { add(j, std::max(1, (rows + th) / th)); }          // as the kernel counts them
+    // -A1: a work item is (G consecutive problems, stripe of 16 rows)
+    template <class Prob> void plan_groups(const std::vector<Prob>& probs, int G)
+    {
+        const int n = (int) probs.size();
+        for (int q = 0; q * G < n; ++q) {
+            int ns = 1;
+            for (int j = q * G; j < std::min(n, (q + 1) * G); ++j) ns = std::max(ns, (probs[j].a_right - probs[j].a_left + 15) / 16);
+            add(q, ns);
+        }
+    }
+    // the device words of n problems; false = out of device memory
+    bool reserve(DevPool& pool, int slot, int n, int stride_)
+    {
+        stride = stride_;
+        words = ((size_t) n * stride + 2 + 1) & ~(size_t) 1;
+        d = (int*) pool.get(slot, sizeof(int) * (words + items.size()));
+        return on = d != nullptr;
+    }
+    // ahead of every launch: clears the words, copies the work list, sets the kernel's six fields (pipe = null when off)
+    template <class Args> hipError_t arm(hipStream_t s, int n, Args& A) const
+    {
+        A.pipe = nullptr;
+        if (!on) return hipSuccess;
+        hipError_t e = hipMemsetAsync(d, 0, sizeof(int) * words, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + words, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice, s);
+        A.pipe = d; A.pipe_stride = stride; A.pipe_ticket = n * stride; A.max_tiles = max_tiles;
+        A.items = (const int2*) (d + words); A.n_items = (int) (items.size() / 2);
+        return e;
+    }
+    // after the launch has finished: *gave_up = a wave gave up (repeat without the pipeline), or the test hook asks for the repeat
+    hipError_t stalled(hipStream_t s, int n, bool* gave_up) const
+    {
+        int mark[2] = {0, 0};
+        const hipError_t e = on ? spdp_copy_sync(mark, d + (size_t) n * stride, sizeof mark, hipMemcpyDeviceToHost, s) : hipSuccess;
+        *gave_up = on && (mark[1] != 0 || getenv("SPDP_A0_PIPE_TEST_STALL"));
+        return e;
+    }
+};
+
 struct SpdpContext {
     DevPool pool[9];                 // one pool per engine flavour (they coexist in a pipeline); [5], [6] = aa x genome path, [7] = rescoring,
                                      // [8] = the forward run on the side stream (coexists with a regular forward run)
@@ -325,7 +388,7 @@ struct RunItem {
 // descriptors + work buffers of one engine flavour over a DevStore:
 // 0 score, 1 forward, 2 udh (the _wip sweeps); 3 scalar exact forward, 4 scalar exact score,
 // 5 scalar udh, 6 -A1 score-only (both share pool 4 with the scalar score run: they never coexist),
-// 7 -A1 forward (shares pool 3 with the scalar forward run), 8 -A1 udh (pool 4)
+// 7 -A1 forward (shares pool 3 with the scalar forward run), 8 -A1 udh (pool 4), 9 local udh (-LS; pool 4)
 struct DevRun {
     SpdpContext* ctx = nullptr;
     SpdpContext* use_ctx = nullptr;         // set before build: the lane to run on (default: the store's context)
@@ -336,13 +399,8 @@ struct DevRun {
     int cross_g = 0;                        // > 0: every problem spread over this many 16-wave blocks (CUs)
     bool fp_ok = false;                     // scores stay inside the exact fp32 range: spdp_sweep_fp.hip may run it
     void* d_gprog = nullptr;                // progress / barrier words of the cross-CU pipelines
-    // -A0 wavefront engines with the tiles of a problem as separate waves (spdp_rowwave<., true>): shares d_gprog
- bool cut = false;                       // flavour 3 with cut ranges on every item (set by build)
-    bool pipe_on = false;
-    int pipe_tiles = 0;                     // most tiles of one problem
-    int pipe_stride = 0;                    // sync words per problem
-    size_t pipe_words = 0;                  // sync words ahead of the item list
-    std::vector<int> h_items;               // (problem, tile) pairs in dispatch order
+    bool cut = false;                       // flavour 3 with cut ranges on every item (set by build)
+    TilePipe pipe;                          // -A0 tiles / -A1 stripes of a problem as separate waves: shares POOL_GPROG with d_gprog
     int max_n_im = 0, max_skl = 0;
     int64_t total_cells = 0, tb_bytes = 0;
     std::vector<DevProblem> h_probs;        // in dispatch order
