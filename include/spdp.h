@@ -132,7 +132,8 @@ typedef struct SpdpAlignment {
     int32_t  reserved;
 } SpdpAlignment;
 /* a linear-space (hirschbergS1[_wip]) call of this query found its path on the free left edge of its window -- a crossing of
- * an intermediate row on or left of the first genomic column, or an empty optimum.  There the reference records link
+ * an intermediate row on or left of the first genomic column, an empty optimum, or a chain of links that ends on no diagonal
+ * of the window (scores pressed against the floor let a path start in such lanes).  There the reference records link
  * lanes it never initialised (src/fwd2s1_wip_simd.h:524: what the previous stripe left behind, heap contents in the first
  * stripe), so its own result is run-dependent; the device starts those lanes from zero and may differ.
  * Planted-gene inputs with the default semi-global ends never set it. */
@@ -312,6 +313,12 @@ int spdp_seeded_stats(const SpdpContext* ctx, int64_t* out, int n);
  * predecessor never arrived.  Results are unaffected (the launch runs again without the pipeline); a non-zero count is
  * time lost. */
 void spdp_rerun_stats(SpdpContext* ctx, int64_t* out, int reset);
+/* launches of the `_wip` sweeps (score-only, traceback, linear-space) on this context and its lanes since the last reset,
+ * repeats counted by spdp_rerun_stats included: out[0] served by the fp32-issue kernel (spdp_sweep_fp), out[1] served by the
+ * int32 kernel (spdp_sweep: local ends, SPDP_FP=0, a penalty table or a score range the fp32 kernel does not take), out[2]
+ * laid out as cross-CU pass groups, out[3] as 16-wave blocks (with or without groups).  For tests and diagnosis: which
+ * kernel and which geometry a call really used. */
+void spdp_sweep_stats(SpdpContext* ctx, int64_t out[4], int reset);
 
 /* stdskl (m_unit 1) / stdskl3 (m_unit 3), src/gaps.cc:140-227: corner list of n path records in any order;
  * out[] needs 2 n + 1 entries, returns the number written.  Host only (no device work). */

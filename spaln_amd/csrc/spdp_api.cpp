@@ -776,6 +776,9 @@ int DevRun::launch()
         else if (e != hipErrorNotSupported) HIPCHK(e);
     }
     if (!done) HIPCHK(spdp_launch_sweep(flavour, store->sc.local ? 1 : 0, nq, pen_cap, &A, grid, wpb, strm()));
+    ++ctx->sweep_stats[done ? 0 : 1];
+    if (cross_g > 0) ++ctx->sweep_stats[2];
+    if (wpb == 16) ++ctx->sweep_stats[3];
     HIPCHK(hipEventRecord(eve(), strm()));
     if (flavour == 1) {
         WalkArgs W;
@@ -800,6 +803,20 @@ extern "C" void spdp_rerun_stats(SpdpContext* ctx, int64_t* out, int reset)
     if (!ctx || !out) return;
     out[0] = ctx->rerun_stats[0]; out[1] = ctx->rerun_stats[1];
     if (reset) ctx->rerun_stats[0] = ctx->rerun_stats[1] = 0;
+    for (SpdpContext* l : ctx->lanes) {                     // chunks of a batch run on the context's lanes
+        out[0] += l->rerun_stats[0]; out[1] += l->rerun_stats[1];
+        if (reset) l->rerun_stats[0] = l->rerun_stats[1] = 0;
+    }
+}
+
+extern "C" void spdp_sweep_stats(SpdpContext* ctx, int64_t* out, int reset)
+{
+    if (!ctx || !out) return;
+    for (int k = 0; k < 4; ++k) {
+        out[k] = reset ? ctx->sweep_stats[k].exchange(0) : ctx->sweep_stats[k].load();
+        for (SpdpContext* l : ctx->lanes)                   // chunks of a batch run on the context's lanes
+            out[k] += reset ? l->sweep_stats[k].exchange(0) : l->sweep_stats[k].load();
+    }
 }
 
 int DevRun::sync()

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <functional>
 #include <string>
@@ -326,6 +327,9 @@ struct SpdpContext {
     int64_t seed_stats[12] = {0};      // spdp_seeded_stats
     std::vector<std::vector<SpdpPhaseMark>> seed_marks;    // spdp_seeded_phase_marks: per query of the last spdp_align_h_seeded call
     int64_t rerun_stats[2] = {0, 0};   // launches repeated because a cross-CU group / a tile pipeline gave up (spdp_rerun_stats)
+    // launches of the `_wip` sweeps (flavours 0 .. 2 of DevRun::launch, repeats included): served by spdp_sweep_fp, served by
+    // spdp_sweep, with cross-CU groups, as 16-wave blocks (spdp_sweep_stats; atomic: a side-stream run launches from its own thread)
+    std::atomic<int64_t> sweep_stats[4] = {};
     void*  stage_ptr[3] = {nullptr, nullptr, nullptr};   // pinned host staging (grow-only): [0], [1] DevStore::upload, [2] the regions and
     size_t stage_cap[3] = {0, 0, 0};                     // signal arrays of spdp_map_align_s
     void*  staging(int k, size_t bytes);

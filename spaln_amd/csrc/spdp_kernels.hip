@@ -966,6 +966,9 @@ __global__ void spdp_udh_cpos(CposArgs A)
             CPOS(i, 0) = END_OF_ULK;
     }
     for ( ; r > up; r -= width) ;
+    // the chain ends on a link that is no diagonal of the window: the zero the device starts the lanes from which the
+    // reference never initialises (every link the boundary hands out lies in lw .. up) -- the same run-dependent case
+    if (!A.strict && !A.local && (r < lw || r > up)) edge = 1;
     if (A.local && (P.flags & 1) && (P.flags & 4)) {    // LocalL: the path's own left end
         a_left = max_ml;
         b_left = r + a_left;

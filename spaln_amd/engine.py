@@ -35,6 +35,7 @@ EXPORTS = [
     "spdp_align_s_seeded", "spdp_align_s_seeded_ori3", "spdp_seeded_stats",
     "spdp_blk_index_create", "spdp_blk_index_destroy", "spdp_blk_vote", "spdp_blk_vote_resident",
     "spdp_blk_search_opts_default", "spdp_blk_index_read", "spdp_blk_index_host_desc", "spdp_blk_index_host_free",
+    "spdp_rerun_stats", "spdp_sweep_stats",
 ]
 
 
@@ -111,6 +112,9 @@ def load_library() -> C.CDLL:
     lib.spdp_group_last_error.restype = C.c_char_p
     lib.spdp_group_last_error.argtypes = [C.c_void_p]
     lib.spdp_group_last_shards.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    for f in ("spdp_rerun_stats", "spdp_sweep_stats"):
+        getattr(lib, f).restype = None
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.spdp_stripe.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.spdp_cells.argtypes = [C.c_void_p, C.c_void_p]
     for f in ("spdp_group_homscore_s", "spdp_group_align_s", "spdp_group_homscore_h", "spdp_group_align_h"):
@@ -325,6 +329,19 @@ class Engine:
         buf = C.create_string_buffer(256)
         self.lib.spdp_device_name(self.ctx, buf, 256)
         return buf.value.decode()
+
+    def rerun_stats(self, reset: bool = False) -> np.ndarray:
+        """spdp_rerun_stats: launches repeated since the last reset [a cross-CU group gave up, a tile pipeline gave up]"""
+        out = np.zeros(2, dtype=np.int64)
+        self.lib.spdp_rerun_stats(self.ctx, out.ctypes.data, int(bool(reset)))
+        return out
+
+    def sweep_stats(self, reset: bool = False) -> np.ndarray:
+        """spdp_sweep_stats: launches of the `_wip` sweeps since the last reset [served by spdp_sweep_fp, served by the
+        int32 spdp_sweep, laid out as cross-CU groups, as 16-wave blocks]"""
+        out = np.zeros(4, dtype=np.int64)
+        self.lib.spdp_sweep_stats(self.ctx, out.ctypes.data, int(bool(reset)))
+        return out
 
     # ---- SimdAln2s1 `_wip` engines ------------------------------------------------
     def splice_signals(self, model: abi.SignalModel, b_codes, left: int = 0, right=None) -> dict:

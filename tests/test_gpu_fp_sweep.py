@@ -2,28 +2,12 @@
 default for non-local score-only / linear-space runs) against spdp_sweep (int32, SPDP_FP=0), on the
 engine entry points and through the whole alignS_ng ladder; and a batch run as pipelined chunks on
 lanes of the context (SPDP_CHUNKS) against the same batch in one piece.  Both knobs are read per call."""
-import os
-
 import numpy as np
 import pytest
 
+from tests.envknobs import Env as _Env
+
 pytestmark = pytest.mark.gpu
-
-
-class _Env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update({k: str(v) for k, v in self.kv.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _batch(n, seed, **kw):

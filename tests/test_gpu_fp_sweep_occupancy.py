@@ -3,28 +3,12 @@ and the bottom-row results in one LDS block, 32-bit indices instead of carried 6
 must stay those of the int32 sweeps of spdp_kernels.hip (SPDP_FP=0), which the four-wave layout matched bit for
 bit: on the headline C2 batch (bench.py's 10 000 x 2 kb queries) through the whole alignS_ng ladder and through
 the linear-space entry point (scores, cpos rows, ranges), and on the shapes of test_gpu_fp_sweep.py."""
-import os
-
 import numpy as np
 import pytest
 
+from tests.envknobs import Env as _Env
+
 pytestmark = pytest.mark.gpu
-
-
-class _Env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update({k: str(v) for k, v in self.kv.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _problems(batch):
