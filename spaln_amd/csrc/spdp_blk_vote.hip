@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spdp_blk_dev.h"
+#include "spdp_wave.h"
 #include "../../include/spdp.h"
 
 namespace {
@@ -40,11 +41,8 @@ constexpr uint32_t NOBODY = 0xffffffffu;
 enum { ST_SIGN = 0, ST_MMCT = 4, ST_NHIT = 8, ST_MAXS = 12, ST_TESTWORD = 16, ST_MAXBSCR = 20, ST_QA_FRONT = 24, ST_QB_FRONT = 28,
        ST_HH_LEVEL = 32, ST_TROUBLE = 33, ST_Q_LEVEL = 40 /* 8: the position tables' levels */, ST_WORDS = 64 };
 
-__device__ __forceinline__ void wave_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint32_t uniu(uint32_t x) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) x); }
-__device__ __forceinline__ int lane_id() { return (int) threadIdx.x; }
 __device__ __forceinline__ int first_lane(u64 m) { return __ffsll((long long) m) - 1; }
 __device__ __forceinline__ int from_lane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
 

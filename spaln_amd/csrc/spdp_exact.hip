@@ -19,14 +19,10 @@
 #include <stdint.h>
 #include "spdp_dev.h"
 #include "spdp_internal.h"
+#include "spdp_pipe.h"
 
 #define XN 16                                    // rows per stripe (SPDP_NELEM)
 #define XNEV SPDP_NEV16
-// post-splice flag of a state (src/aln.h:56): H 4, E 1, F 8 -- arithmetic, not a table in memory
-__device__ __forceinline__ int x_psp_bit_of(int d) { return d == 0 ? 4 : (d == 1 ? 1 : (d == 2 ? 8 : (d == 3 ? 2 : 16))); }    // H, E, F, E2, F2
-
-__device__ __forceinline__ int x_sadd(int a, int b) { return max(a + b, SPDP_FLOOR16); }
-__device__ __forceinline__ int x_up(int v) { return __shfl_up(v, 1, XN); }      // lane k <- lane k - 1 of its group
 
 // FORWARD: forwardS1 (src/fwd2s1_simd.cc:481-773) -- the same sweep with a Vmf pointer riding on H / E / F (one
 // int here; modes 3 / 5 of the reference split it over int16 lanes), a diagonal flag per cell, a record at
@@ -44,21 +40,12 @@ __device__ __forceinline__ int x_up(int v) { return __shfl_up(v, 1, XN); }      
 // before every block of 16 steps it stages.  What the one-wave form carries from stripe to stripe in registers goes
 // through memory: the local maximum (per stripe, first maximum in stripe order), the intermediate-row counter
 // (recomputed), and hs1.rlst -- only ever stored, so a stripe starts from a marker (XINH) and the link walk
-// (spdp_udh_cpos) replaces it by what the intermediate rows above left (rlf[]).
+// (spdp_udh_cpos) replaces it by what the intermediate rows above left (rlf[]).  Where the sync words lie and the
+// publish: spdp_pipe.h.
 #define XINH SPDP_RLST_INHERITED
 #define XPROG0 (1 << 28)
 #define XVCH SPDP_VMF_LANE_CHUNK
 #define XWPB 4                                   // waves per block: they share the read-only tables in LDS
-template <bool X> __device__ __forceinline__ int x_ld(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return __builtin_nontemporal_load(p);
-}
-template <bool X> __device__ __forceinline__ void x_st(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
 
 // DAGP: double affine gaps (PwdB::Noll = 3, -yl3; round 5): the second horizontal / vertical gap states E2 / F2 priced with
 // LongGOP / LongGEP (src/fwd2s1_simd.cc:347-352, 368-378 / 556-569, 592-611), the better gap of each pair competes for the cell
@@ -154,14 +141,14 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
     bool v_asked = false;
     auto vadd = [&](int mm, int nn, int pp) -> int {
         if (v_left == 0) {
-            if (!v_asked) v_pend = atomicAdd(vcount, XVCH);
+            if (!v_asked) v_pend = __hip_atomic_fetch_add(vcount, XVCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             v_next = v_pend; v_left = XVCH; v_asked = false;
         }
         const int i = v_next++;
         --v_left;
-        if (v_left == XVCH / 2 && !v_asked) { v_pend = atomicAdd(vcount, XVCH); v_asked = true; }
+        if (v_left == XVCH / 2 && !v_asked) { v_pend = __hip_atomic_fetch_add(vcount, XVCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v_asked = true; }
         if (i < vcap) {
-            if (PIPE) { x_st<true>(vraw + 3 * i, mm); x_st<true>(vraw + 3 * i + 1, nn); x_st<true>(vraw + 3 * i + 2, pp); }
+            if (PIPE) { gst<true>(vraw + 3 * i, mm); gst<true>(vraw + 3 * i + 1, nn); gst<true>(vraw + 3 * i + 2, pp); }
             else vrec[i] = make_int3(mm, nn, pp);
         }
         return i;
@@ -170,26 +157,21 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
     const int n_stripes = max(1, (a_right - a_left + XN - 1) / XN);     // (DevRun::build lists the same count)
     if (PIPE && my_stripe >= n_stripes) return;  // (a shorter problem of the four)
     // PIPE: what the stripes of the problem share: prog[max_tiles], best[max_tiles][6], rlf[n_im]
-    int* sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
-    int* prog = PIPE ? sy + 2 : nullptr;
-    int* tbest = PIPE ? sy + 2 + A.max_tiles : nullptr;
-    int* rlf = PIPE ? sy + 2 + 7 * A.max_tiles : nullptr;
+    int *sy, *prog, *tbest, *rlf;
+    pipe_words<PIPE, SPDP_PIPE_TPW_A1>(A, pi, sy, prog, tbest, rlf);
     bool stalled = false;
     // waits until stripe t has published at least `req` (per lane: a group waits for its own problem)
     auto wait_for = [&](int t, int req) {
         long spins = 0;
-        while (!stalled && __hip_atomic_load(prog + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < req) {
+        while (!stalled && gld<true>(prog + t) < req) {
             __builtin_amdgcn_s_sleep(8);
             if (++spins > (1l << 22)) {              // (cannot happen with the ticket order; bounds every spin)
-                __hip_atomic_store(A.pipe + A.pipe_ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                gst<true>(A.pipe + A.pipe_ticket + 1, 1);
                 stalled = true;
             }
         }
     };
-    auto publish = [&](int t, int v) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (k == 0) __hip_atomic_store(prog + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int t, int v) { pipe_publish(prog + t, v, k == 0); };
 
     // ---- fhinitS1
     if (!PIPE || my_stripe == 0) {
@@ -208,26 +190,26 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                 else if (ge) { if (r > rl + 1 && r < rr_g) h = gop + ge + (r - rl - 1) * ge; }
                 else if (r > rl + 1 && r < rr) h = gop;
             }
-            x_st<PIPE>(&hv[r], h); x_st<PIPE>(&fv[r], XNEV);
-            if constexpr (DAGP) x_st<PIPE>(&fv2[r], XNEV);
+            gst<PIPE>(&hv[r], h); gst<PIPE>(&fv[r], XNEV);
+            if constexpr (DAGP) gst<PIPE>(&fv2[r], XNEV);
             if constexpr (FORWARD) {                 // the Vmf part of fhinitS1 (:185-205): records 0 (dummy) and 1 (start)
                 const int ru = up + 2 * XN;
                 int c = 0;
                 if (r == rl) c = 1;
                 else if (r > rl && r <= ru) c = a_exgl ? 0 : 1;
                 else if (r < rl) c = b_exgl ? 0 : 1;
-                x_st<PIPE>(&hb[r], 0); x_st<PIPE>(&hc[r], c); x_st<PIPE>(&fc[r], c);
-                if constexpr (DAGP) x_st<PIPE>(&fc2[r], c);              // (src/fwd2s1_simd.cc:236)
+                gst<PIPE>(&hb[r], 0); gst<PIPE>(&hc[r], c); gst<PIPE>(&fc[r], c);
+                if constexpr (DAGP) gst<PIPE>(&fc2[r], c);              // (src/fwd2s1_simd.cc:236)
             }
             if constexpr (UDH) {                     // the Hirschberg part (:206-227): link = diagonal where the path starts
                 const int ru = up + 2 * XN;
                 int c = 0;
                 if (r >= rl) { if (a_exgl) c = (r < ru) ? r : 0; else c = (r <= ru) ? rl : 0; }
                 else c = b_exgl ? r : rl;
-                x_st<PIPE>(&hc[r], c); x_st<PIPE>(&fc[r], c);
+                gst<PIPE>(&hc[r], c); gst<PIPE>(&fc[r], c);
                 int bm = a_left;                     // bbuf = a_left; the free left column counts rows upwards (:209-224)
                 if (b_exgl && r <= rl && r >= lw) bm = a_left + (rl - r);
-                x_st<PIPE>(&hb[r], bm); x_st<PIPE>(&fb[r], a_left);
+                gst<PIPE>(&hb[r], bm); gst<PIPE>(&fb[r], a_left);
             }
         }
         if constexpr (UDH) {
@@ -235,9 +217,9 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         }
         if constexpr (FORWARD) {
             if (k == 0) {
-                x_st<PIPE>(vraw, 0); x_st<PIPE>(vraw + 1, 0); x_st<PIPE>(vraw + 2, 0);
-                x_st<PIPE>(vraw + 3, a_left); x_st<PIPE>(vraw + 4, b_left); x_st<PIPE>(vraw + 5, 0);
-                x_st<PIPE>(vcount, 2);
+                gst<PIPE>(vraw, 0); gst<PIPE>(vraw + 1, 0); gst<PIPE>(vraw + 2, 0);
+                gst<PIPE>(vraw + 3, a_left); gst<PIPE>(vraw + 4, b_left); gst<PIPE>(vraw + 5, 0);
+                gst<PIPE>(vcount, 2);
             }
         }
     }
@@ -287,7 +269,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         const bool imd_here = UDH && is_imd_ && k == k8;     // my row is the intermediate row (m == imd->mi)
         (void) k9;
         if (PIPE && UDH && is_imd_) {
-            for (int e = k; e < 4 * width; e += XN) x_st<true>(imd0 + (int64_t) imd_i * 4 * width + e, 0x7fffffff - 2);
+            for (int e = k; e < 4 * width; e += XN) gst<true>(imd0 + (int64_t) imd_i * 4 * width + e, 0x7fffffff - 2);
             rlst = imd_i == 0 ? 0x7fffffff : XINH;
         }
         const int st = PIPE ? my_stripe : 0;
@@ -308,11 +290,11 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         auto prefetch = [&](int nb_, int rb_) {                           // block starting at step nb_, diagonal rb_
             ld_col(nb_ + k, pc, pax);
             const int e = min(rb_ + 1 + k, e_last);
-            pfd[FD_HV] = x_ld<PIPE>(&hv[e]); pfd[FD_FV] = x_ld<PIPE>(&fv[e]);
-            if constexpr (PTR) { pfd[FD_HC] = x_ld<PIPE>(&hc[e]); pfd[FD_FC] = x_ld<PIPE>(&fc[e]); }
-            if constexpr (FORWARD) pfd[FD_HB] = x_ld<PIPE>(&hb[e]);
-            if constexpr (UDH) { if (LocalL) { pfd[FD_HB] = x_ld<PIPE>(&hb[e]); pfd[FD_FB] = x_ld<PIPE>(&fb[e]); } }
-            if constexpr (DAGP) { pfd[FD_FV2] = x_ld<PIPE>(&fv2[e]); if constexpr (PTR) pfd[FD_FC2] = x_ld<PIPE>(&fc2[e]); }
+            pfd[FD_HV] = gld<PIPE>(&hv[e]); pfd[FD_FV] = gld<PIPE>(&fv[e]);
+            if constexpr (PTR) { pfd[FD_HC] = gld<PIPE>(&hc[e]); pfd[FD_FC] = gld<PIPE>(&fc[e]); }
+            if constexpr (FORWARD) pfd[FD_HB] = gld<PIPE>(&hb[e]);
+            if constexpr (UDH) { if (LocalL) { pfd[FD_HB] = gld<PIPE>(&hb[e]); pfd[FD_FB] = gld<PIPE>(&fb[e]); } }
+            if constexpr (DAGP) { pfd[FD_FV2] = gld<PIPE>(&fv2[e]); if constexpr (PTR) pfd[FD_FC2] = gld<PIPE>(&fc2[e]); }
         };
         auto commit = [&](int nb_) {                                      // the staged block becomes the current one
             ring[(nb_ + k) & 63] = pc; ringx[(nb_ + k) & 63] = (unsigned short) pax;
@@ -331,13 +313,13 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
             ring[(n_first - 16 + k) & 63] = c0; ringx[(n_first - 16 + k) & 63] = (unsigned short) a0;
             if (k == 0) {
                 const int e = min(r, e_last);
-                fd[FD_HV][16] = x_ld<PIPE>(&hv[e]); fd[FD_FV][16] = x_ld<PIPE>(&fv[e]);
-                if constexpr (PTR) { fd[FD_HC][16] = x_ld<PIPE>(&hc[e]); fd[FD_FC][16] = x_ld<PIPE>(&fc[e]); }
-                if constexpr (FORWARD) fd[FD_HB][16] = x_ld<PIPE>(&hb[e]);
-                if constexpr (UDH) { if (LocalL) { fd[FD_HB][16] = x_ld<PIPE>(&hb[e]); fd[FD_FB][16] = x_ld<PIPE>(&fb[e]); } }
-                if constexpr (DAGP) { fd[FD_FV2][16] = x_ld<PIPE>(&fv2[e]); if constexpr (PTR) fd[FD_FC2][16] = x_ld<PIPE>(&fc2[e]); }
+                fd[FD_HV][16] = gld<PIPE>(&hv[e]); fd[FD_FV][16] = gld<PIPE>(&fv[e]);
+                if constexpr (PTR) { fd[FD_HC][16] = gld<PIPE>(&hc[e]); fd[FD_FC][16] = gld<PIPE>(&fc[e]); }
+                if constexpr (FORWARD) fd[FD_HB][16] = gld<PIPE>(&hb[e]);
+                if constexpr (UDH) { if (LocalL) { fd[FD_HB][16] = gld<PIPE>(&hb[e]); fd[FD_FB][16] = gld<PIPE>(&fb[e]); } }
+                if constexpr (DAGP) { fd[FD_FV2][16] = gld<PIPE>(&fv2[e]); if constexpr (PTR) fd[FD_FC2][16] = gld<PIPE>(&fc2[e]); }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_done();
             prefetch(n, r);
         }
         // PIPE: a stripe is finished the moment its last step is done, not when the wave leaves the loop -- the other
@@ -346,7 +328,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         auto finish_stripe = [&]() {
             if (LocalR && k == 0) {
                 int* b = tbest + 6 * st;
-                x_st<true>(b, maxh); x_st<true>(b + 1, max_ulk); x_st<true>(b + 2, max_mr); x_st<true>(b + 3, max_nr); x_st<true>(b + 4, max_ml);
+                gst<true>(b, maxh); gst<true>(b + 1, max_ulk); gst<true>(b + 2, max_mr); gst<true>(b + 3, max_nr); gst<true>(b + 4, max_ml);
             }
             if (st > 0) wait_for(st - 1, INT32_MAX);                      // finished = all stripes up to this one are
             publish(st, INT32_MAX);
@@ -355,11 +337,11 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         int jb = 16;                                                      // step within the block; 16 = a new block starts
         for ( ; n < n9; ++n, ++r) {
             if (jb == 16) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // (this wave's reads of the old block are done)
+                lds_done();        // (this wave's reads of the old block are done)
                 commit(n);
                 if (PIPE) { publish(st, r - 1 - 2 * j8 + XPROG0); ready(r + 32); }
                 prefetch(n + 16, r + 16);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 jb = 0;
             }
             const int j = jb++;
@@ -375,32 +357,32 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                 if constexpr (FORWARD) bB2 = fd[FD_HB][j];
                 if constexpr (UDH) { if (LocalL) { bB2 = fd[FD_HB][j]; bB1 = fd[FD_HB][j + 1]; bFB1 = fd[FD_FB][j + 1]; } }
             }
-            int upH1 = x_up(H1), upF1 = x_up(F1), upH2 = x_up(H2);
+            int upH1 = up16(H1), upF1 = up16(F1), upH2 = up16(H2);
             int upC1 = 0, upFC1 = 0, upB2 = 0, upC2 = 0;
-            if constexpr (PTR) { upC1 = x_up(C1); upFC1 = x_up(FC1); upC2 = x_up(C2); }
-            if constexpr (FORWARD) upB2 = x_up(B2);
+            if constexpr (PTR) { upC1 = up16(C1); upFC1 = up16(FC1); upC2 = up16(C2); }
+            if constexpr (FORWARD) upB2 = up16(B2);
             int upB1 = 0, upFB1 = 0;                          // udh, local left ends: `ml` of the lane above
-            if constexpr (UDH) { if (LocalL) { upB2 = x_up(B2); upB1 = x_up(B1); upFB1 = x_up(FB); } }
+            if constexpr (UDH) { if (LocalL) { upB2 = up16(B2); upB1 = up16(B1); upFB1 = up16(FB); } }
             int upF21 = XNEV, upFC21 = 0;
-            if constexpr (DAGP) { upF21 = x_up(F21); if constexpr (PTR) upFC21 = x_up(FC21); }
+            if constexpr (DAGP) { upF21 = up16(F21); if constexpr (PTR) upFC21 = up16(FC21); }
             if (k == 0) { upH1 = bH1; upF1 = bF1; upH2 = bH2; upC1 = bC1; upFC1 = bFC1; upB2 = bB2; upC2 = bC2; upB1 = bB1; upFB1 = bFB1; upF21 = bF21; upFC21 = bFC21; }
             // insertion, deletion, diagonal
             {
-                const int open = x_sadd(H1, gn), ext = x_sadd(E, ge);
+                const int open = sadd16(H1, gn), ext = sadd16(E, ge);
                 const bool m_ = ext > open;
                 E = m_ ? ext : open;
                 if constexpr (PTR) EC = m_ ? EC : C1;
                 if constexpr (UDH) { if (LocalL) EB = m_ ? EB : B1; }
             }
             if constexpr (DAGP) {                             // the long horizontal gap (:347-352 / :556-569)
-                const int open = x_sadd(H1, gn2), ext = x_sadd(E2, ge2);
+                const int open = sadd16(H1, gn2), ext = sadd16(E2, ge2);
                 const bool m_ = ext > open;
                 E2 = m_ ? ext : open;
                 if constexpr (PTR) EC2 = m_ ? EC2 : C1;
             }
             int F, FC = 0;
             {
-                const int open = x_sadd(upH1, gn), ext = x_sadd(upF1, ge);
+                const int open = sadd16(upH1, gn), ext = sadd16(upF1, ge);
                 const bool m_ = ext > open;
                 F = m_ ? ext : open;
                 if constexpr (PTR) FC = m_ ? upFC1 : upC1;
@@ -408,7 +390,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
             }
             int F2 = XNEV, FC2 = 0;
             if constexpr (DAGP) {                             // the long vertical gap (:368-375 / :592-608)
-                const int open = x_sadd(upH1, gn2), ext = x_sadd(upF21, ge2);
+                const int open = sadd16(upH1, gn2), ext = sadd16(upF21, ge2);
                 const bool m_ = ext > open;
                 F2 = m_ ? ext : open;
                 if constexpr (PTR) FC2 = m_ ? upFC21 : upC1;
@@ -418,7 +400,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
             const int2 col = ring[nj & 63];
             const unsigned axj = ringx[nj & 63];
             if (incell) pv = mrow[col.y];
-            int H = x_sadd(pv, upH2);
+            int H = sadd16(pv, upH2);
             int HC = upC2;
             int code = 0;                                     // diag: 0, hori: 1, vert: 2 (pv_a)
             int HBu = upB2;                                   // udh, local left ends: `ml` of H
@@ -485,7 +467,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                         if (x <= cur) continue;
                         cur = (int) (short) x;
                         if (d == 0) H = cur; else if (d == 1) E = cur; else if (d == 2 || !DAGP) F = cur; else if (d == 3) E2 = cur; else F2 = cur;
-                        ps |= x_psp_bit_of(d);
+                        ps |= psp_bit(d);
                         if constexpr (FORWARD) {
                             const int inner = vadd(m, don, c_ulk[ci]);
                             const int ptr = vadd(m, nj, inner);
@@ -512,13 +494,13 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                         if (imd_here && br_on) {                  // the acceptor sits on the intermediate row (:91-110)
                             const int maxd = br_d;
                             const int lk = maxd == 0 ? mx_lk[0] : (maxd == 1 ? mx_lk[1] : mx_lk[2]);
-                            x_st<PIPE>(&LNK(imd_i, 0, 0, rj), lk); rlst = rj;
+                            gst<PIPE>(&LNK(imd_i, 0, 0, rj), lk); rlst = rj;
                             if (maxd == 0) HC = rj; else if (maxd == 1) EC = rj; else FC = rj;
                             hb_pv = maxd;
                             if (maxd != 0) HC = rj;
                             else {
                                 if (mx_on[1] && E > H + gop) EC = rj + width;
-                                if (mx_on[2] && F > H + gop) { x_st<PIPE>(&LNK(imd_i, 0, 1, rj), lk); FC = rj + width; }
+                                if (mx_on[2] && F > H + gop) { gst<PIPE>(&LNK(imd_i, 0, 1, rj), lk); FC = rj + width; }
                             }
                         }
                     }
@@ -526,7 +508,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                 if (fl & 1) {                                 // donor: Sjsites::put
                     const int sigJ = (int) (short) (col.x & 0xffff) - ipen;
                     for (int kk = hb_pv ? 1 : 0; kk < NOD; ++kk) {
-                        if (ps & x_psp_bit_of(kk)) continue;
+                        if (ps & psp_bit(kk)) continue;
                         const int from = kk == 0 ? H : (kk == 1 ? E : (kk == 2 ? F : (kk == 3 ? E2 : F2)));
                         if (kk && from <= H + (kk <= 2 ? gop : lgop)) continue;      // GOP[(k + 1) / 2]
                         const int x = from + sigJ;
@@ -549,7 +531,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                                 n_ulk = kk == 0 ? HC : (kk == 1 ? EC : (kk == 2 ? FC : (kk == 3 ? EC2 : FC2)));
                             }
                             if constexpr (UDH) {
-                                if (imd_here) { if (kk & 1) x_st<PIPE>(&LNK(imd_i, 0, 0, rj), rlst); n_ulk = rj; }
+                                if (imd_here) { if (kk & 1) gst<PIPE>(&LNK(imd_i, 0, 0, rj), rlst); n_ulk = rj; }
                                 else n_ulk = kk == 0 ? HC : (kk == 1 ? EC : FC);
                                 n_ml = kk == 0 ? HB : (kk == 1 ? EB : FB);
                             }
@@ -568,18 +550,18 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
                 const int rq = r - 2 * k8;
                 if (is_imd_ && k == k8 && rq >= lw && rq <= up) {
                     if (hb_pv == 0) rlst = rq;
-                    if (hb_pv == 1) x_st<PIPE>(&LNK(imd_i, 0, 0, rq), rlst);
-                    x_st<PIPE>(&LNK(imd_i, 1, 0, rq), HC); HC = rq;
-                    x_st<PIPE>(&LNK(imd_i, 1, 1, rq), FC); FC = rq + width;
+                    if (hb_pv == 1) gst<PIPE>(&LNK(imd_i, 0, 0, rq), rlst);
+                    gst<PIPE>(&LNK(imd_i, 1, 0, rq), HC); HC = rq;
+                    gst<PIPE>(&LNK(imd_i, 1, 1, rq), FC); FC = rq + width;
                 }
             }
             // bottom row of the stripe -> boundary arrays
             if (k == j8 && j9 == ke && lw <= r0 && r0 <= up) {
-                x_st<PIPE>(&hv[r0], H); x_st<PIPE>(&fv[r0], F);
-                if constexpr (DAGP) { x_st<PIPE>(&fv2[r0], F2); if constexpr (PTR) x_st<PIPE>(&fc2[r0], FC2); }
-                if constexpr (FORWARD) x_st<PIPE>(&hb[r0], HB);
-                if constexpr (PTR) { x_st<PIPE>(&hc[r0], HC); x_st<PIPE>(&fc[r0], FC); }
-                if constexpr (UDH) { if (LocalL) { x_st<PIPE>(&hb[r0], HB); x_st<PIPE>(&fb[r0], FB); } }
+                gst<PIPE>(&hv[r0], H); gst<PIPE>(&fv[r0], F);
+                if constexpr (DAGP) { gst<PIPE>(&fv2[r0], F2); if constexpr (PTR) gst<PIPE>(&fc2[r0], FC2); }
+                if constexpr (FORWARD) gst<PIPE>(&hb[r0], HB);
+                if constexpr (PTR) { gst<PIPE>(&hc[r0], HC); gst<PIPE>(&fc[r0], FC); }
+                if constexpr (UDH) { if (LocalL) { gst<PIPE>(&hb[r0], HB); gst<PIPE>(&fb[r0], FB); } }
             }
             H2 = H1; H1 = H; F1 = F;
             if constexpr (DAGP) { F21 = F2; FC21 = FC2; }
@@ -590,7 +572,7 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
         if constexpr (UDH) {
             if (is_imd_) {
                 rlst = __shfl(rlst, k8, XN);                              // hs1.rlst is one variable for all lanes
-                if (PIPE && k == 0) x_st<true>(rlf + imd_i, rlst);
+                if (PIPE && k == 0) gst<true>(rlf + imd_i, rlst);
                 ++imd_i;
             }
         }
@@ -608,8 +590,8 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
             maxh = XNEV; max_ulk = 0; max_mr = a_right; max_nr = b_right; max_ml = a_left;
             for (int t = 0; t < n_stripes; ++t) {
                 const int* b = tbest + 6 * t;
-                const int v = x_ld<true>(b);
-                if (v > maxh) { maxh = v; max_ulk = x_ld<true>(b + 1); max_mr = x_ld<true>(b + 2); max_nr = x_ld<true>(b + 3); max_ml = x_ld<true>(b + 4); }
+                const int v = gld<true>(b);
+                if (v > maxh) { maxh = v; max_ulk = gld<true>(b + 1); max_mr = gld<true>(b + 2); max_nr = gld<true>(b + 3); max_ml = gld<true>(b + 4); }
             }
         }
     }
@@ -626,34 +608,34 @@ __global__ void __launch_bounds__(64 * XWPB) __attribute__((amdgpu_waves_per_eu(
             if (a_exgr) {
                 const int r1 = max(lw, b_left - a_right);
                 int best = r1;
-                for (int i = r1 + 1; i < rr; ++i) if (x_ld<PIPE>(&hv[i]) > x_ld<PIPE>(&hv[best])) best = i;
+                for (int i = r1 + 1; i < rr; ++i) if (gld<PIPE>(&hv[i]) > gld<PIPE>(&hv[best])) best = i;
                 maxr = best;
             }
             if (b_exgr) {
                 const int r2 = min(up - 1, b_right - a_left);
                 int best = rr;
-                for (int i = rr + 1; i < r2; ++i) if (x_ld<PIPE>(&hv[i]) > x_ld<PIPE>(&hv[best])) best = i;
-                if (x_ld<PIPE>(&hv[best]) > x_ld<PIPE>(&hv[maxr])) maxr = best;
+                for (int i = rr + 1; i < r2; ++i) if (gld<PIPE>(&hv[i]) > gld<PIPE>(&hv[best])) best = i;
+                if (gld<PIPE>(&hv[best]) > gld<PIPE>(&hv[maxr])) maxr = best;
             }
-            R.score = x_ld<PIPE>(&hv[maxr]);
+            R.score = gld<PIPE>(&hv[maxr]);
             R.maxr = maxr;
             if (maxr > rr) R.mr = b_right - maxr; else R.nr = a_right + maxr;
-            if constexpr (PTR) end_ulk = x_ld<PIPE>(&hc[maxr]);
-            if constexpr (UDH) { if (LocalL) R.ml = x_ld<PIPE>(&hb[maxr]); }
+            if constexpr (PTR) end_ulk = gld<PIPE>(&hc[maxr]);
+            if constexpr (UDH) { if (LocalL) R.ml = gld<PIPE>(&hb[maxr]); }
         }
         if constexpr (FORWARD) {
             const int ptr = vadd(R.mr, R.nr, end_ulk);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int used = x_ld<PIPE>(vcount);
+            stores_drained();
+            const int used = gld<PIPE>(vcount);
             int2* out = A.skl + (int64_t) pi * A.skl_cap;
             int cnt = 0, status = used > vcap ? -3 : 0;
             if (!status) {
                 const int* vr = reinterpret_cast<const int*>(vrec);
                 int cur = ptr, lm = 0, ln = 0;
                 for (;;) {
-                    const int sm = x_ld<PIPE>(vr + 3 * (int64_t) cur);
-                    const int sn = x_ld<PIPE>(vr + 3 * (int64_t) cur + 1);
-                    const int sp = x_ld<PIPE>(vr + 3 * (int64_t) cur + 2);
+                    const int sm = gld<PIPE>(vr + 3 * (int64_t) cur);
+                    const int sn = gld<PIPE>(vr + 3 * (int64_t) cur + 1);
+                    const int sp = gld<PIPE>(vr + 3 * (int64_t) cur + 2);
                     if (cnt < A.skl_cap) out[cnt] = make_int2(sm, sn); else status = -1;
                     lm = sm; ln = sn; ++cnt;
                     if (!sp) break;

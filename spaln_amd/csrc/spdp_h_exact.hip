@@ -39,12 +39,14 @@
 //    intermediate rows above left (rlf[]); the local maximum is reduced per stripe and combined in stripe order;
 //    Vmf record numbers are reserved eight at a time per lane.  The reference's link planes are not
 //    re-initialised from stripe to stripe; only cells at nevsel ever read the stale words, and no result
-//    (score, records, cpos) can see them, so a stripe starts them at zero.
+//    (score, records, cpos) can see them, so a stripe starts them at zero.  Where the sync words lie and the
+//    publish: spdp_pipe.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "spdp_h_dev.h"
 #include "spdp_h_internal.h"
+#include "spdp_pipe.h"
 
 #define XN 16
 #define XNEV (-32768 + 1024)
@@ -58,21 +60,7 @@
 
 __device__ __forceinline__ int xh_add(int a, int b) { return min(max(a + b, -32768), 32767); }
 __device__ __forceinline__ int xh_w16(int x) { return (int) (short) x; }
-__device__ __forceinline__ int xh_up(int v) { return __shfl_up(v, 1, XN); }
 __device__ __forceinline__ int xh_mod6(int x) { x %= 6; return x < 0 ? x + 6 : x; }
-// lane i of every 16-lane row <- lane i - 1; lane 0 of the row keeps `old`
-__device__ __forceinline__ int xh_shr1(int old, int src) { return __builtin_amdgcn_update_dpp(old, src, 0x111, 0xf, 0xf, false); }
-__device__ __forceinline__ int xh_psp_bit(int d) { return d == 0 ? 4 : (d == 1 ? 1 : 8); }
-template <bool X> __device__ __forceinline__ int xh_ld(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <bool X> __device__ __forceinline__ void xh_st(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
 #define SEL3(a, x0, x1, x2) ((a) == 0 ? (x0) : ((a) == 1 ? (x1) : (x2)))
 
 enum { FD_HV, FD_FV, FD_HC, FD_FC, FD_HB, FD_FB, FD_N };
@@ -160,7 +148,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         const int i = v_next++;
         --v_left;
         if (v_left == HXVCH / 2 && !v_asked) { v_pend = __hip_atomic_fetch_add(vcount, HXVCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v_asked = true; }
-        if (i < vcap) { xh_st<PIPE>(vraw + 3 * i, mm); xh_st<PIPE>(vraw + 3 * i + 1, nn); xh_st<PIPE>(vraw + 3 * i + 2, pp); }
+        if (i < vcap) { gst<PIPE>(vraw + 3 * i, mm); gst<PIPE>(vraw + 3 * i + 1, nn); gst<PIPE>(vraw + 3 * i + 2, pp); }
         return i;
     };
     int* imd0 = A.imd + (UDH ? P.imd_off : 0);   // hlnk[2], vlnk[2] per intermediate row, `width` ints each
@@ -176,38 +164,33 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
     const int n_stripes = max(1, (a_right - a_left + XN - 1) / XN);
     if (PIPE && my_stripe >= n_stripes) return;  // (a shorter problem of the four)
     // PIPE: what the stripes of the problem share: prog[max_tiles], best[max_tiles][6], rlf[n_im][3]
-    int* sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
-    int* prog = PIPE ? sy + 2 : nullptr;
-    int* tbest = PIPE ? sy + 2 + A.max_tiles : nullptr;
-    int* rlf = PIPE ? sy + 2 + 7 * A.max_tiles : nullptr;
+    int *sy, *prog, *tbest, *rlf;
+    pipe_words<PIPE, SPDP_PIPE_TPW_H_A1>(A, pi, sy, prog, tbest, rlf);
     bool stalled = false;
-    auto wait_for = [&](int t, int req) {        // until stripe t has published at least `req` (per lane: a group waits for its own problem)
+    auto wait_for = [&](int t, int req) {        // (per lane: a group waits for its own problem)
         long spins = 0;
-        while (!stalled && __hip_atomic_load(prog + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < req) {
+        while (!stalled && gld<true>(prog + t) < req) {
             __builtin_amdgcn_s_sleep(8);
-            if (++spins > (1l << 22)) {          // (cannot happen with the ticket order; bounds every spin)
-                __hip_atomic_store(A.pipe + A.pipe_ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (++spins > (1l << 22)) {              // (cannot happen with the ticket order; bounds every spin)
+                gst<true>(A.pipe + A.pipe_ticket + 1, 1);
                 stalled = true;
             }
         }
     };
-    auto publish = [&](int t, int v) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (k == 0) __hip_atomic_store(prog + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int t, int v) { pipe_publish(prog + t, v, k == 0); };
 
     // ---- fhinitH1 (:546-689): bulk fills by all lanes, the sequential parts by lane 0
     const int rl = b_left - 3 * a_left;
     if (!PIPE || my_stripe == 0) {
         for (int e = k; e < 2 * B; e += XN) {
-            xh_st<PIPE>(hv + lw - 3 + e, XNEV);
-            xh_st<PIPE>(hb + lw - 3 + e, UDH ? a_left : 0);
-            xh_st<PIPE>(hc + lw - 3 + e, 0);
+            gst<PIPE>(hv + lw - 3 + e, XNEV);
+            gst<PIPE>(hb + lw - 3 + e, UDH ? a_left : 0);
+            gst<PIPE>(hc + lw - 3 + e, 0);
         }
         if constexpr (UDH && !PIPE)
             for (int e = k; e < n_im * 4 * width; e += XN) imd0[e] = X_EOU;
-        if (k == 0) xh_st<PIPE>(vcount, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (k == 0) gst<PIPE>(vcount, 0);
+        stores_drained();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         int sc_on = 0, sc_r = 0, sc_n = 0, sc_bb = 0, sc_rr = 0;        // the first-row scan, where it stands (lane 0 -> group)
         int sh1 = 0, sh2 = 0, sh3 = 0, sc1 = 0, sc2 = 0, sc3 = 0, sl0 = 0, sl1 = 0, sl2 = 0;
@@ -219,35 +202,35 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                 if (!(a_exgl && b_exgl)) ptr0 = vadd(a_left, b_left, ptr0);
             }
             ptr0 = __shfl(ptr0, 0, XN);
-            for (int r = rl + k; r < up; r += XN) xh_st<PIPE>(hc + r, a_exgl ? 0 : ptr0);
-            for (int r = lw + k; r < rl; r += XN) xh_st<PIPE>(hc + r, b_exgl ? 0 : ptr0);
+            for (int r = rl + k; r < up; r += XN) gst<PIPE>(hc + r, a_exgl ? 0 : ptr0);
+            for (int r = lw + k; r < rl; r += XN) gst<PIPE>(hc + r, b_exgl ? 0 : ptr0);
         } else {
             const int re = a_exgl ? rl : up;
-            for (int r = lw + k; r < re; r += XN) xh_st<PIPE>(hc + r, r);
-            for (int i = k, r = rl - k; r >= lw; r -= XN, i += XN) xh_st<PIPE>(hb + r, a_left + i / 3);
+            for (int r = lw + k; r < re; r += XN) gst<PIPE>(hc + r, r);
+            for (int i = k, r = rl - k; r >= lw; r -= XN, i += XN) gst<PIPE>(hb + r, a_left + i / 3);
         }
-        if (b_exgl == 1) { for (int r = lw + k; r < rl; r += XN) xh_st<PIPE>(hv + r, 0); }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (b_exgl == 1) { for (int r = lw + k; r < rl; r += XN) gst<PIPE>(hv + r, 0); }
+        stores_drained();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         if (k == 0) {
-            if constexpr (!UDH) { if (b_exgl == 2) xh_st<PIPE>(fc + rl, ptr0); }
-            if (b_exgl == 2) { xh_st<PIPE>(fv + rl, 0); xh_st<PIPE>(fc + rl, rl); }
+            if constexpr (!UDH) { if (b_exgl == 2) gst<PIPE>(fc + rl, ptr0); }
+            if (b_exgl == 2) { gst<PIPE>(fv + rl, 0); gst<PIPE>(fc + rl, rl); }
             int rr = b_right - 3 * a_left;
             if (up < rr) rr = up;
             int r = rl;
             if (!a_exgl) {
-                if (b_exgl) { xh_st<PIPE>(fv + r, 0); xh_st<PIPE>(fc + r, UDH ? rl : ptr0); }       // (= hc[rl] as set above)
-                xh_st<PIPE>(hv + r++, 0);
-                xh_st<PIPE>(hv + r++, xh_w16(g1));
-                xh_st<PIPE>(hv + r++, xh_w16(g2));
-                xh_st<PIPE>(hv + r++, xh_w16(g3));
+                if (b_exgl) { gst<PIPE>(fv + r, 0); gst<PIPE>(fc + r, UDH ? rl : ptr0); }       // (= hc[rl] as set above)
+                gst<PIPE>(hv + r++, 0);
+                gst<PIPE>(hv + r++, xh_w16(g1));
+                gst<PIPE>(hv + r++, xh_w16(g2));
+                gst<PIPE>(hv + r++, xh_w16(g3));
                 int h1 = xh_w16(g3), h2 = xh_w16(g2), h3 = xh_w16(g1);      // hv[r - 1], [r - 2], [r - 3]
                 if (gep) {
                     const int x = (XNEV - g3) / gep + r;
                     if (x < rr) rr = x;
-                    for ( ; r < rr; ++r) { const int h = xh_w16(h3 + gep); xh_st<PIPE>(hv + r, h); h3 = h2; h2 = h1; h1 = h; }
+                    for ( ; r < rr; ++r) { const int h = xh_w16(h3 + gep); gst<PIPE>(hv + r, h); h3 = h2; h2 = h1; h1 = h; }
                 } else if (rr > r)
-                    for (const int v = h1; r < rr; ++r) xh_st<PIPE>(hv + r, v);
+                    for (const int v = h1; r < rr; ++r) gst<PIPE>(hv + r, v);
             } else {
                 int n = b_left;
                 int le0 = r, le1 = r + 1, le2 = r + 2;            // lend[f], rotated with f
@@ -257,9 +240,9 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                     const int s = aux[bb].x;
                     const int h = s > 0 ? s : 0;
                     int c;
-                    if constexpr (!UDH) { c = vadd(a_left, n, 0); xh_st<PIPE>(hb + r, 1); }
+                    if constexpr (!UDH) { c = vadd(a_left, n, 0); gst<PIPE>(hb + r, 1); }
                     else c = r;
-                    xh_st<PIPE>(hv + r, h); xh_st<PIPE>(hc + r, c);
+                    gst<PIPE>(hv + r, h); gst<PIPE>(hc + r, c);
                     h3 = h2; h2 = h1; h1 = h; c3 = c2; c2 = c1; c1 = c;
                 }
                 sc_on = 1; sc_r = r; sc_n = n; sc_bb = bb; sc_rr = rr;
@@ -274,12 +257,12 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             int* const sI = reinterpret_cast<int*>(s_col[g16]);
             while (sc_on && sc_r < sc_rr) {
                 const int cnt = min(128, sc_rr - sc_r);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 for (int i = k; i < cnt + 3; i += XN) {
                     const short4 a = aux[max(sc_bb - 3 + i, 0)];
                     sI[i] = (int) ((unsigned) (unsigned short) a.x | ((unsigned) (unsigned short) a.z << 16));      // sigS | sigE << 16
                 }
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                mem_done();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 int stop = 0;
                 if (k == 0) {
@@ -290,7 +273,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                         if (!(a_exgl & 1) && gl == 3) h = xh_w16(h + gop);
                         if (!(a_exgl & 2)) h = xh_w16(h + gext3(gl));
                         h = xh_w16(h + (sI[i] >> 16));                        // aux[bb - 3].z
-                        if (h < XNEV) { xh_st<PIPE>(hv + r, h); xh_st<PIPE>(hc + r, c); stop = 1; break; }
+                        if (h < XNEV) { gst<PIPE>(hv + r, h); gst<PIPE>(hc + r, c); stop = 1; break; }
                         int x = xh_w16(sh1 + g1);
                         if (x > h) { h = x; c = sc1; }
                         x = xh_w16(sh2 + g2);
@@ -299,10 +282,10 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                         x = sS > 0 ? sS : 0;
                         if (x > h) {
                             h = x; sl0 = r;
-                            if constexpr (!UDH) { c = vadd(a_left, n, 0); xh_st<PIPE>(hb + r, 1); }
+                            if constexpr (!UDH) { c = vadd(a_left, n, 0); gst<PIPE>(hb + r, 1); }
                             else c = r;
                         }
-                        xh_st<PIPE>(hv + r, h); xh_st<PIPE>(hc + r, c);
+                        gst<PIPE>(hv + r, h); gst<PIPE>(hc + r, c);
                         sh3 = sh2; sh2 = sh1; sh1 = h; sc3 = sc2; sc2 = sc1; sc1 = c;
                         const int t_ = sl0; sl0 = sl1; sl1 = sl2; sl2 = t_;
                     }
@@ -310,9 +293,9 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                 if (__shfl(stop, 0, XN)) break;
                 sc_r += cnt; sc_n += cnt; sc_bb += cnt;
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_done();
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stores_drained();
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 
@@ -383,7 +366,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         int PS[4] = {0, 0, 0, 0}, PV[3] = {0, 0, 0}, CP[4] = {0, 0, 0, 0};
         // what came down from the lane above 1, 2, 3 steps ago (its cells of 4, 5, 6 steps ago)
         int uH[4] = {XNEV, XNEV, XNEV, XNEV}, uC[4] = {0, 0, 0, 0}, uB[4] = {0, 0, 0, 0};
-        if (!PIPE) { uC[1] = xh_shr1(0, HC[4]); uC[2] = xh_shr1(0, HC[5]); uC[3] = xh_shr1(0, HC[6]); }
+        if (!PIPE) { uC[1] = row_shr1(0, HC[4]); uC[2] = row_shr1(0, HC[5]); uC[3] = row_shr1(0, HC[6]); }
         else if (ml != a_left) uC[1] = uC[2] = uC[3] = HXPOISON;
         // the donor candidates of my row, best first: value, donor position, `ml` / link of the state it left, and what an
         // acceptor needs of the donor's column (c_dk)
@@ -410,7 +393,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         const int* mrow_m = s_mtx + acode(m) * 32;            // a codon split by an intron is scored against these rows
         const int* mrow_m1 = s_mtx + acode(m + 1) * 32;
         if (PIPE && UDH && is_imd_) {
-            for (int e = k; e < 4 * width; e += XN) xh_st<true>(imd0 + (int64_t) imd_i * 4 * width + e, X_EOU);
+            for (int e = k; e < 4 * width; e += XN) gst<true>(imd0 + (int64_t) imd_i * 4 * width + e, X_EOU);
             if (imd_i) { rl0 = HXINH; rl1 = HXINH + 1; rl2 = HXINH + 2; }
         }
         // ---- staging: the ring holds columns [nb - 48, nb + 32) while the block that starts at step nb runs; the feed
@@ -425,14 +408,14 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         int pfd[FD_N] = {0, 0, 0, 0, 0, 0};
         auto ld_feed = [&](int e, int* o) {                    // entry e of each row (clamped to what exists; beyond: never used)
             const int ee = min(max(e, e_lo), e_hi - B);
-            o[FD_HV] = xh_ld<PIPE>(hv + ee); o[FD_FV] = xh_ld<PIPE>(fv + ee);
-            o[FD_HC] = xh_ld<PIPE>(hc + ee); o[FD_FC] = xh_ld<PIPE>(fc + ee);
-            o[FD_HB] = useB ? xh_ld<PIPE>(hb + ee) : 0;
-            o[FD_FB] = UL ? xh_ld<PIPE>(fb + ee) : 0;
+            o[FD_HV] = gld_l1<PIPE>(hv + ee); o[FD_FV] = gld_l1<PIPE>(fv + ee);
+            o[FD_HC] = gld_l1<PIPE>(hc + ee); o[FD_FC] = gld_l1<PIPE>(fc + ee);
+            o[FD_HB] = useB ? gld_l1<PIPE>(hb + ee) : 0;
+            o[FD_FB] = UL ? gld_l1<PIPE>(fb + ee) : 0;
         };
         {
             ready(r + 3 + 15 + 16);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_done();
 #pragma unroll
             for (int t = 0; t < 5; ++t) ring[(n_first - 48 + 16 * t + k) & (HXRING - 1)] = ld_col(n_first - 48 + 16 * t + k);
             int f0[FD_N];
@@ -441,9 +424,9 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             for (int a = 0; a < FD_N; ++a) fd[a][k] = f0[a];
             // lane 0's history of the first step: entries r, r + 1, r + 2 (what it would have received 3, 2, 1 steps ago)
             if (k == 0) {
-                uH[3] = xh_ld<PIPE>(hv + r); uH[2] = xh_ld<PIPE>(hv + r + 1); uH[1] = xh_ld<PIPE>(hv + r + 2);
-                uC[3] = xh_ld<PIPE>(hc + r); uC[2] = xh_ld<PIPE>(hc + r + 1); uC[1] = xh_ld<PIPE>(hc + r + 2);
-                if (useB) { uB[3] = xh_ld<PIPE>(hb + r); uB[2] = xh_ld<PIPE>(hb + r + 1); uB[1] = xh_ld<PIPE>(hb + r + 2); }
+                uH[3] = gld_l1<PIPE>(hv + r); uH[2] = gld_l1<PIPE>(hv + r + 1); uH[1] = gld_l1<PIPE>(hv + r + 2);
+                uC[3] = gld_l1<PIPE>(hc + r); uC[2] = gld_l1<PIPE>(hc + r + 1); uC[1] = gld_l1<PIPE>(hc + r + 2);
+                if (useB) { uB[3] = gld_l1<PIPE>(hb + r); uB[2] = gld_l1<PIPE>(hb + r + 1); uB[1] = gld_l1<PIPE>(hb + r + 2); }
             }
             pc = ld_col(n_first + 32 + k);
             ld_feed(r + 3 + 16 + k, pfd);
@@ -451,10 +434,10 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         auto finish_stripe = [&]() {
             if (LocalR && k == 0) {
                 int* b = tbest + 6 * st;
-                xh_st<true>(b, max_val); xh_st<true>(b + 1, max_ulk); xh_st<true>(b + 2, max_mr); xh_st<true>(b + 3, max_nr); xh_st<true>(b + 4, max_ml);
+                gst<true>(b, max_val); gst<true>(b + 1, max_ulk); gst<true>(b + 2, max_mr); gst<true>(b + 3, max_nr); gst<true>(b + 4, max_ml);
             }
             if (UDH && is_imd_) {                                             // (lane k8 holds them)
-                if (k == k8) { xh_st<true>(rlf + 3 * imd_i, rl0); xh_st<true>(rlf + 3 * imd_i + 1, rl1); xh_st<true>(rlf + 3 * imd_i + 2, rl2); }
+                if (k == k8) { gst<true>(rlf + 3 * imd_i, rl0); gst<true>(rlf + 3 * imd_i + 1, rl1); gst<true>(rlf + 3 * imd_i + 2, rl2); }
             }
             if (st > 0) wait_for(st - 1, INT32_MAX);                          // finished = all stripes up to this one are
             publish(st, INT32_MAX);
@@ -463,14 +446,14 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         int jb = 0;                                                           // step within the block
         for ( ; n < n9; ++n, ++r, q = (q == 5 ? 0 : q + 1)) {
             if (jb == 16) {                                                   // a new block: its loads become current, the next one's start
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 ring[(n + 16 + k) & (HXRING - 1)] = pc;
 #pragma unroll
                 for (int a = 0; a < FD_N; ++a) fd[a][k] = pfd[a];
                 if (PIPE) { publish(st, r - 1 - 6 * 15 - 2 + HXPROG0); ready(r + 3 + 15 + 16); }
                 pc = ld_col(n + 32 + k);
                 ld_feed(r + 3 + 16 + k, pfd);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 jb = 0;
             }
             const int j = jb++;
@@ -485,14 +468,14 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             // the value it used to the lane below, which uses it three steps later
             int cv = CP[3];
             if (k == 0 && spj && !nb) cv = (int) (short) (cx & 0xffff);
-            CP[0] = xh_shr1(cv, cv);
+            CP[0] = row_shr1(cv, cv);
             // the row of the lane above (its cell of three steps ago); lane 0: the previous stripe's bottom row
-            uH[0] = xh_shr1(fd[FD_HV][j], HV[3]);
-            uC[0] = xh_shr1(fd[FD_HC][j], HC[3]);
-            const int uF3 = xh_shr1(fd[FD_FV][j], FV[3]);
-            const int uFC3 = xh_shr1(fd[FD_FC][j], FC[3]);
-            uB[0] = useB ? xh_shr1(fd[FD_HB][j], HB[3]) : 0;
-            const int uFB3 = UL ? xh_shr1(fd[FD_FB][j], FB[3]) : 0;
+            uH[0] = row_shr1(fd[FD_HV][j], HV[3]);
+            uC[0] = row_shr1(fd[FD_HC][j], HC[3]);
+            const int uF3 = row_shr1(fd[FD_FV][j], FV[3]);
+            const int uFC3 = row_shr1(fd[FD_FC][j], FC[3]);
+            uB[0] = useB ? row_shr1(fd[FD_HB][j], HB[3]) : 0;
+            const int uFB3 = UL ? row_shr1(fd[FD_FB][j], FB[3]) : 0;
             // insertion: frame shifts, codon insertion, extension (:879-915)
             int ev, eb, ec;
             {
@@ -645,18 +628,18 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                                 if (d == 0) { HV[aa] = w; HB[aa] = cml; HC[aa] = lk; }
                                 else if (d == 1) { EV[aa] = w; EB[aa] = cml; EC[aa] = lk; }
                                 else { FV[aa] = w; FB[aa] = cml; FC[aa] = lk; }
-                                PS[aa] |= xh_psp_bit(d);
+                                PS[aa] |= psp_bit3(d);
                                 if (d && w > HV[aa]) { HV[aa] = w; HB[aa] = cml; HC[aa] = lk; }
                                 hnow = HV[aa]; hbnow = HB[aa]; hcnow = HC[aa];
                             }
                         if (k + 1 == XN) {
-                            xh_st<PIPE>(hv + rr, hnow);
-                            if (imd_lane) xh_st<PIPE>(LNK(imd_i, 0, 0, rr), culk);
-                            else { xh_st<PIPE>(hb + rr, hbnow); xh_st<PIPE>(hc + rr, hcnow); }
+                            gst<PIPE>(hv + rr, hnow);
+                            if (imd_lane) gst<PIPE>(LNK(imd_i, 0, 0, rr), culk);
+                            else { gst<PIPE>(hb + rr, hbnow); gst<PIPE>(hc + rr, hcnow); }
                             if (d == 2) {
-                                xh_st<PIPE>(fv + rr, w);
-                                if (imd_lane) xh_st<PIPE>(LNK(imd_i, 0, 1, rr), culk);
-                                else { xh_st<PIPE>(fb + rr, cml); xh_st<PIPE>(fc + rr, lk); }
+                                gst<PIPE>(fv + rr, w);
+                                if (imd_lane) gst<PIPE>(LNK(imd_i, 0, 1, rr), culk);
+                                else { gst<PIPE>(fb + rr, cml); gst<PIPE>(fc + rr, lk); }
                             }
                         }
                     }
@@ -669,7 +652,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                             int fr = f3 - a; if (fr < 0) fr += 3;     // (q - a) mod 3: the frame of that cell
                             const int lstr = acc + p_phs - mm3;
                             if (fr == 0) rl0 = lstr; else if (fr == 1) rl1 = lstr; else rl2 = lstr;
-                            xh_st<PIPE>(LNK(imd_i, 0, 0, lstr), p_ulk);
+                            gst<PIPE>(LNK(imd_i, 0, 0, lstr), p_ulk);
 #pragma unroll
                             for (int aa = 0; aa < 3; ++aa)
                                 if (aa == a) {
@@ -677,7 +660,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                                     PV[aa] = maxd;
                                     if (maxd) HC[aa] = lstr;
                                     else {
-                                        if (mx_on[1] && EV[aa] > HV[aa] + gop) { xh_st<PIPE>(LNK(imd_i, 0, 1, lstr), mx_ulk[1]); EC[aa] = lstr + width; }
+                                        if (mx_on[1] && EV[aa] > HV[aa] + gop) { gst<PIPE>(LNK(imd_i, 0, 1, lstr), mx_ulk[1]); EC[aa] = lstr + width; }
                                         if (mx_on[2] && FV[aa] > HV[aa] + gop) FC[aa] = lstr + width;
                                     }
                                 }
@@ -707,7 +690,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                         for (int kk = 0; kk < 3; ++kk) {
                             if (kk == 0 && h && phs < 1) continue;
-                            if (PS[a] & xh_psp_bit(kk)) continue;
+                            if (PS[a] & psp_bit3(kk)) continue;
                             const bool cross = phs == 1 && kk == 0;
                             const int from = cross ? qv : (kk == 0 ? HV[a] : (kk == 1 ? EV[a] : FV[a]));
                             if (kk && from <= thr) continue;
@@ -730,7 +713,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                                 int n_ulk;
                                 if (imd_lane) {
                                     const int rq = c - a - mm3;
-                                    if (kk == 1) xh_st<PIPE>(LNK(imd_i, 0, 0, rq), SEL3(frm, rl0, rl1, rl2));
+                                    if (kk == 1) gst<PIPE>(LNK(imd_i, 0, 0, rq), SEL3(frm, rl0, rl1, rl2));
                                     n_ulk = rq;
                                 } else
                                     n_ulk = cross ? qc : (kk == 0 ? HC[a] : (kk == 1 ? EC[a] : FC[a]));
@@ -751,20 +734,20 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                 if (is_imd_ && rj >= lw && rj <= up && k == k8) {
                     // lane k8 holds the row's side lanes, lane k9 - 1 == k8 its H / F planes ([k9] in the reference's layout)
                     if (PV[0] == 0) { if (f3 == 0) rl0 = rj; else if (f3 == 1) rl1 = rj; else rl2 = rj; }
-                    if (PV[0] == 1) xh_st<PIPE>(LNK(imd_i, 0, 0, rj), SEL3(f3, rl0, rl1, rl2));
-                    xh_st<PIPE>(LNK(imd_i, 1, 0, rj), HC[0]);
+                    if (PV[0] == 1) gst<PIPE>(LNK(imd_i, 0, 0, rj), SEL3(f3, rl0, rl1, rl2));
+                    gst<PIPE>(LNK(imd_i, 1, 0, rj), HC[0]);
                     HC[0] = rj;
-                    xh_st<PIPE>(LNK(imd_i, 1, 1, rj), FC[0]);
+                    gst<PIPE>(LNK(imd_i, 1, 1, rj), FC[0]);
                     FC[0] = rj + width;
                 }
             }
             // hand the bottom row to the next stripe (:1063-1073 / :1386-1397)
             const int r0 = r - 6 * j8;
             if (k == j8 && j9 == ke && lw <= r0 && (UDH ? r0 < up : r0 <= up)) {
-                xh_st<PIPE>(hv + r0, HV[0]); xh_st<PIPE>(hc + r0, HC[0]);
-                xh_st<PIPE>(fv + r0, FV[0]); xh_st<PIPE>(fc + r0, FC[0]);
-                if constexpr (!UDH) xh_st<PIPE>(hb + r0, HB[0]);
-                else if (LocalL) { xh_st<PIPE>(hb + r0, HB[0]); xh_st<PIPE>(fb + r0, FB[0]); }
+                gst<PIPE>(hv + r0, HV[0]); gst<PIPE>(hc + r0, HC[0]);
+                gst<PIPE>(fv + r0, FV[0]); gst<PIPE>(fc + r0, FC[0]);
+                if constexpr (!UDH) gst<PIPE>(hb + r0, HB[0]);
+                else if (LocalL) { gst<PIPE>(hb + r0, HB[0]); gst<PIPE>(fb + r0, FB[0]); }
             }
             // one step older
 #pragma unroll
@@ -804,16 +787,16 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             max_val = XNEV; max_ulk = X_EOU; max_ml = a_left; max_mr = a_right; max_nr = b_right;
             for (int t = 0; t < n_stripes; ++t) {
                 const int* b = tbest + 6 * t;
-                const int v = xh_ld<true>(b);
-                if (v > max_val) { max_val = v; max_ulk = xh_ld<true>(b + 1); max_mr = xh_ld<true>(b + 2); max_nr = xh_ld<true>(b + 3); max_ml = xh_ld<true>(b + 4); }
+                const int v = gld<true>(b);
+                if (v > max_val) { max_val = v; max_ulk = gld<true>(b + 1); max_mr = gld<true>(b + 2); max_nr = gld<true>(b + 3); max_ml = gld<true>(b + 4); }
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stores_drained();
 
     // ---- fhlastH1 (:691-791): the scans over the last row / the last column one entry after the other on lane 0,
     // their inputs (boundary entries, signals) staged through LDS by the whole group, 128 entries at a time
-    auto HVr = [&](int i) -> int { return xh_ld<PIPE>(hv + i); };
+    auto HVr = [&](int i) -> int { return gld_l1<PIPE>(hv + i); };
     int ptr = 0, maxt = 0;
     const bool by_last = UDH ? !(LocalR && max_mr < a_right) : (!LocalR || max_mr == a_right);
     const int m3 = 3 * a_right;
@@ -835,14 +818,14 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             int p1 = 0, p2 = 0, p3 = 0;                  // hv[h - 1], [h - 2], [h - 3] as they stand (after this loop's writes)
             for (int h0 = rw; h0 <= rr; h0 += 128, bb += 128) {
                 const int cnt = min(128, rr - h0 + 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 for (int i = k; i < cnt; i += XN) sH[i] = HVr(h0 + i);
                 for (int i = k; i < cnt + 2; i += XN) {
                     const short4 a = aux[max(bb - 2 + i, 0)];
                     sYZ[i] = (int) ((unsigned) (unsigned short) a.y | ((unsigned) (unsigned short) a.z << 16));
                     sW[i] = a.w;
                 }
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                mem_done();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 if (k == 0) {
                     for (int i = 0; i < cnt; ++i, ++rf) {
@@ -866,8 +849,8 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                         if (c1 > cb) { kk = 1; cb = c1; }
                         if (c2 > cb) { kk = 2; cb = c2; }
                         if (kk == 0) { gl0 = 0; tc0 = false; }
-                        else if (kk == 1) { hvh = xh_w16(c1 - s5); xh_st<PIPE>(hv + h, hvh); }
-                        else { hvh = xh_w16(c2); xh_st<PIPE>(hv + h, hvh); }
+                        else if (kk == 1) { hvh = xh_w16(c1 - s5); gst<PIPE>(hv + h, hvh); }
+                        else { hvh = xh_w16(c2); gst<PIPE>(hv + h, hvh); }
                         if (h == mx) hmx = hvh;
                         if (hvh > hmx) { mx = h; hmx = hvh; maxr = rf - (kk == 2 ? 3 : 0); }
                         p3 = p2; p2 = p1; p1 = hvh;
@@ -878,7 +861,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             }
         } else if (k == 0) {
             const int y = xh_w16(HVr(rr - 3) + aux[bb + (rr - rw)].y);
-            if (y > HVr(rr)) { xh_st<PIPE>(hv + rr, y); maxr = rr - 3; if (mx == rr) hmx = y; }
+            if (y > HVr(rr)) { gst<PIPE>(hv + rr, y); maxr = rr - 3; if (mx == rr) hmx = y; }
         }
         if (b_exgr) {
             rw = min(up - 1, b_right - 3 * a_left);
@@ -887,9 +870,9 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             if (k == 0 && rw - 3 > rr) { n3 = HVr(rw); n2 = HVr(rw - 1); n1 = HVr(rw - 2); }
             for (int h0 = rw - 3; h0 > rr; h0 -= 256) {
                 const int cnt = min(256, h0 - rr);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_done();
                 for (int i = k; i < cnt; i += XN) sH[i] = HVr(h0 - i);
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                mem_done();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 if (k == 0) {
                     for (int i = 0; i < cnt; ++i) {
@@ -900,20 +883,20 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                         if (!(b_exgr & 2)) ga = xh_w16(ga + gep);
                         int hvh = sH[i];
                         if (hvh > ga) ga = XNEV;
-                        else if (ga > hmx) { mx = h; hvh = ga; hmx = ga; xh_st<PIPE>(hv + h, ga); }
+                        else if (ga > hmx) { mx = h; hvh = ga; hmx = ga; gst<PIPE>(hv + h, ga); }
                         n3 = n2; n2 = n1; n1 = hvh;
                         { const int t_ = ga; ga = gb_; gb_ = gc; gc = t_; }
                     }
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_done();
     }
     if (k) return;
     if (by_last) {
         maxt = mx;
-        if constexpr (UDH) xh_st<PIPE>(hb + maxt, xh_ld<PIPE>(hb + maxr));
-        max_ulk = xh_ld<PIPE>(hc + maxr);
+        if constexpr (UDH) gst<PIPE>(hb + maxt, gld_l1<PIPE>(hb + maxr));
+        max_ulk = gld_l1<PIPE>(hc + maxr);
         int qd = maxr - rr;
         if constexpr (!UDH) {
             int m9 = a_right, n9 = b_right;
@@ -928,7 +911,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         ptr = max_ulk;
     } else if constexpr (!UDH)
         ptr = vadd(max_mr, max_nr, max_ulk);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stores_drained();
 
     DevResultH R;
     R.score = max_val; R.mr = max_mr; R.nr = max_nr; R.maxt = maxt; R.maxr = 0; R.pad[0] = max_ulk; R.pad[2] = 0;
@@ -939,7 +922,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
     if constexpr (!UDH) {
         // Vmf::traceback(ptr) + the fix-up of trcbkalignH_ng
         int2* out = A.skl + (int64_t) pi * A.skl_cap;
-        const int vn = xh_ld<PIPE>(vcount);
+        const int vn = gld_l1<PIPE>(vcount);
         int cnt = 0, status = vn > vcap ? -3 : 0;
         {   // mode 3 keeps the record pointer in one int16 lane (undefined in the reference beyond 32767 records)
             const int mq = a_right - a_left;
@@ -951,8 +934,8 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             int cur = ptr, lm = 0, ln = 0;
             for (;;) {
                 if (PIPE && cur == HXPOISON) { poisoned = true; break; }
-                const int sm_ = xh_ld<PIPE>(vraw + 3 * (int64_t) cur), sn_ = xh_ld<PIPE>(vraw + 3 * (int64_t) cur + 1);
-                const int sp_ = xh_ld<PIPE>(vraw + 3 * (int64_t) cur + 2);
+                const int sm_ = gld_l1<PIPE>(vraw + 3 * (int64_t) cur), sn_ = gld_l1<PIPE>(vraw + 3 * (int64_t) cur + 1);
+                const int sp_ = gld_l1<PIPE>(vraw + 3 * (int64_t) cur + 2);
                 if (cnt < A.skl_cap) out[cnt] = make_int2(sm_, sn_); else status = -1;
                 lm = sm_; ln = sn_; ++cnt;
                 if (!sp_) break;
@@ -973,18 +956,18 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
         auto mi_of = [&](int i) { return a_left + (i + 1) * imd_step; };
         // a horizontal link that stands for "rlst of this frame as the intermediate rows above left it"
         auto hlnk = [&](int ii, int d, int rr_) -> int {
-            int v = xh_ld<PIPE>(LNK(ii, 0, d, rr_));
+            int v = gld_l1<PIPE>(LNK(ii, 0, d, rr_));
             if (PIPE && v == HXPOISON) poisoned = true;
             if (PIPE && v >= HXINH && v < HXINH + 3) {
                 const int fr = v - HXINH;
                 v = 0x7fffffff;
-                for (int j = ii - 1; j >= 0; --j) { const int w = xh_ld<true>(rlf + 3 * j + fr); if (w != HXINH + fr) { v = w; break; } }
+                for (int j = ii - 1; j >= 0; --j) { const int w = gld<true>(rlf + 3 * j + fr); if (w != HXINH + fr) { v = w; break; } }
             }
             return v;
         };
 #define CPOS(i, c) cpos[(i) * 10 + (c)]
         int al = a_left, ar = a_right, bl = b_left, br = b_right;
-        if (by_last) max_ml = LocalL ? xh_ld<PIPE>(hb + maxt) : a_left;
+        if (by_last) max_ml = LocalL ? gld_l1<PIPE>(hb + maxt) : a_left;
         ar = max_mr; br = max_nr;
         int val = max_val;
         int i = n_im;
@@ -995,7 +978,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
             int c = 0, d = 0;
             if (PIPE && (r == HXPOISON || poisoned)) { poisoned = true; break; }
             for ( ; r > up; r -= width) ++d;
-            if (xh_ld<PIPE>(LNK(i, 1, d, r)) < X_EOU) {
+            if (gld_l1<PIPE>(LNK(i, 1, d, r)) < X_EOU) {
                 CPOS(i, c++) = mi_of(i);
                 CPOS(i, c++) = (d > 0) ? 1 : 0;
                 const int m3 = 3 * mi_of(i);
@@ -1003,7 +986,7 @@ __global__ void __launch_bounds__(64 * HXWPB) __attribute__((amdgpu_waves_per_eu
                     CPOS(i, c++) = r + m3;
                 CPOS(i, c++) = r + m3;
                 CPOS(i, c) = X_EOU;
-                r = xh_ld<PIPE>(LNK(i, 1, d, r));
+                r = gld_l1<PIPE>(LNK(i, 1, d, r));
                 if (r == X_EOU) break;
             } else
                 CPOS(i, 0) = X_EOU;
@@ -1178,11 +1161,11 @@ __global__ void __launch_bounds__(64) spdh_local_udh(HScalarArgs A)
             // coding potential pipe (unconditional here, :121-125)
             if (k == 0) LV(W_CP + f3) = (int) (short) (col0.x & 0xffff);
             const int cv = LV(W_CP + f3);
-            { const int u = xh_up(cv); if (k) LV(W_CP + f3) = u; }
-            int uH3 = xh_up(LV(W_HV + q3)), uF3 = xh_up(LV(W_FV + q3)), uH4 = xh_up(LV(W_HV + q4)), uH5 = xh_up(LV(W_HV + q5));
-            int uC3 = xh_up(LV(W_HC + q3)), uFC3 = xh_up(LV(W_FC + q3)), uC4 = xh_up(LV(W_HC + q4)), uC5 = xh_up(LV(W_HC + q5));
-            int uB3 = xh_up(LV(W_HB + q3)), uFB3 = xh_up(LV(W_FB + q3)), uB4 = xh_up(LV(W_HB + q4)), uB5 = xh_up(LV(W_HB + q5));
-            int uH0 = xh_up(LV(W_HV + q)), uC0 = xh_up(LV(W_HC + q)), uB0 = xh_up(LV(W_HB + q));
+            { const int u = up16(cv); if (k) LV(W_CP + f3) = u; }
+            int uH3 = up16(LV(W_HV + q3)), uF3 = up16(LV(W_FV + q3)), uH4 = up16(LV(W_HV + q4)), uH5 = up16(LV(W_HV + q5));
+            int uC3 = up16(LV(W_HC + q3)), uFC3 = up16(LV(W_FC + q3)), uC4 = up16(LV(W_HC + q4)), uC5 = up16(LV(W_HC + q5));
+            int uB3 = up16(LV(W_HB + q3)), uFB3 = up16(LV(W_FB + q3)), uB4 = up16(LV(W_HB + q4)), uB5 = up16(LV(W_HB + q5));
+            int uH0 = up16(LV(W_HV + q)), uC0 = up16(LV(W_HC + q)), uB0 = up16(LV(W_HB + q));
             if (k == 0) {
                 uF3 = fv[r + 3]; uFC3 = fc[r + 3]; uH3 = hv[r + 3]; uC3 = hc[r + 3];
                 uH4 = hv[r + 2]; uC4 = hc[r + 2]; uH5 = hv[r + 1]; uC5 = hc[r + 1];
@@ -1250,7 +1233,7 @@ __global__ void __launch_bounds__(64) spdh_local_udh(HScalarArgs A)
                     else if (a3 & 4u) { f_s = (int) (short) ((unsigned) col0.y >> 16); f_p = 3; }
                     if (k == 0) { LV(W_S3 + pk) = f_s; LV(W_P3 + pk) = f_p; }
                     const int ss = LV(W_S3 + pk), ph = LV(W_P3 + pk);
-                    { const int us = xh_up(ss), upp = xh_up(ph); if (k) { LV(W_S3 + pk) = us; LV(W_P3 + pk) = upp; } }
+                    { const int us = up16(ss), upp = up16(ph); if (k) { LV(W_S3 + pk) = us; LV(W_P3 + pk) = upp; } }
                     const unsigned long long bal = __ballot(ph != 0);
                     if (!((bal >> (grp * 16)) & 0xffffull)) continue;
                     for (int f = 0; f < 3; ++f) {
@@ -1300,7 +1283,7 @@ __global__ void __launch_bounds__(64) spdh_local_udh(HScalarArgs A)
                     else if (a5 & 4u) { f_s = (int) (short) ((unsigned) col0.z >> 16); f_p = 3; }
                     if (k == 0) { LV(W_S5 + pk) = f_s; LV(W_P5 + pk) = f_p; }
                     const int ss = LV(W_S5 + pk), ph = LV(W_P5 + pk);
-                    { const int us = xh_up(ss), upp = xh_up(ph); if (k) { LV(W_S5 + pk) = us; LV(W_P5 + pk) = upp; } }
+                    { const int us = up16(ss), upp = up16(ph); if (k) { LV(W_S5 + pk) = us; LV(W_P5 + pk) = upp; } }
                     const unsigned long long bal = __ballot(ph != 0);
                     if (!((bal >> (grp * 16)) & 0xffffull)) continue;
                     for (int f = k2 ? 2 : 0; f < 3; ++f) {

@@ -22,46 +22,12 @@
 #include <stdint.h>
 #include "spdp_h_dev.h"
 #include "spdp_h_internal.h"
+#include "spdp_wave.h"
 
 // TraceBackCode values (src/rhomb_coord.h:36-61)
 enum { C_DIAG = 1, C_HORI = 2, C_HORL = 3, C_HOR1 = 4, C_HOR2 = 5, C_VERT = 8, C_VERL = 9, C_VER1 = 10, C_VER2 = 11,
        C_ACCM = 13, C_ACCZ = 14, C_ACCP = 15, C_NHOR = 16, C_NVER = 32, C_NHOL = 64, C_DONM = 64,
        C_NVEL = 128, C_DONZ = 128, C_DONP = 256 };
-
-typedef short s16;
-__device__ __forceinline__ s16 sadd(s16 a, s16 b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ s16 smax(s16 a, s16 b) { return a > b ? a : b; }
-// the sweep keeps its int16 scores in the UPPER half of 32-bit registers (value * 65536): `v_add_i32 ... clamp` then
-// saturates exactly where `v_add_i16 ... clamp` does, at less than half the issue cost (profiles/r02_valu_ubench.txt:
-// 7.7 cycles per wave-instruction for the 16-bit VOP3 form, 4 for the 32-bit one), and order comparisons are unchanged
-typedef int q16;
-#define Q16(x) ((q16) ((unsigned) (x) << 16))
-__device__ __forceinline__ q16 qadd(q16 a, q16 b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ q16 qmax(q16 a, q16 b) { return a > b ? a : b; }
-
-#define DPP_ROW_SR(n) (0x110 + (n))
-#define DPP_ROW_RR(n) (0x120 + (n))
-// lane i of every 16-lane row <- lane i-1; lane 0 of the row keeps `old`
-__device__ __forceinline__ int row_shr1(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, DPP_ROW_SR(1), 0xf, 0xf, false);
-}
-// lane 0 of every row <- lane 15 of that row
-__device__ __forceinline__ int row_ror1(int src)
-{
-    return __builtin_amdgcn_mov_dpp(src, DPP_ROW_RR(1), 0xf, 0xf, true);
-}
-
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-// L1-bypassing loads for data another row of this wave stored a few blocks ago
-__device__ __forceinline__ int2 ld_nt2(const int2* p)
-{
-    const v2i_t v = __builtin_nontemporal_load(reinterpret_cast<const v2i_t*>(p));
-    return make_int2(v.x, v.y);
-}
-__device__ __forceinline__ int ld_nt1(const int* p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ unsigned ld_nt_u16(const uint16_t* p) { return __builtin_nontemporal_load(p); }
 
 #define SPDH_PEN_TAB 2048
 

@@ -88,7 +88,6 @@ __device__ __forceinline__ void load_tables(Tables& T, const HScalarArgs& A, con
     ipen_runs_load(T.runs, A.ipen_runs);
     __syncthreads();                                    // the only block-wide barrier
 }
-#define WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
 // a DP state: value, direction, riders (MODE 1: a = Vmf record; MODE 2: a = upr, b = lwr, c = ml, e = ulk)
 struct St { int v, d, a, b, c, e; };
@@ -155,7 +154,7 @@ template <class A> __device__ __forceinline__ int pick(int sel, const A& arr)
 
 }   // namespace
 
-// PIPE (as spdp_rowwave.hip): the tiles of one problem run as separate waves, each a few dozen anti-diagonals behind
+// PIPE (as spdp_rowwave.hip, through spdp_pipe.h): the tiles of one problem run as separate waves, each a few dozen anti-diagonals behind
 // the tile above it.  HScalarArgs::items lists (problem, tile) in dispatch order and a wave draws the next one from a
 // ticket counter, so a tile's predecessor is always resident or done.  The arrays then cross CUs: their accesses
 // go to the memory side (agent-scope atomics; the per-XCD L2s are not coherent with each other) and a tile
@@ -165,17 +164,6 @@ template <class A> __device__ __forceinline__ int pick(int sel, const A& arr)
 // HLNK): a tile starts from the marker INH + slot, every intermediate row leaves what it ends with in rlf[], and
 // the link walk replaces the marker by what the rows above left.
 constexpr int INH = 0x7ffffff0;
-template <bool X> __device__ __forceinline__ int gld(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return __builtin_nontemporal_load(p);
-}
-template <bool X> __device__ __forceinline__ void gst(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-#define STORES_DRAINED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // DAGP: double affine gaps (PwdB::Noll = 3, -yl3; src/fwd2h1.cc:297, 343, 365, 413-449, 577-598 / 1088, 1140, 1162, 1211-1247,
 // 1316-1330, 1412-1440; round 5): a second deletion state F2 (a third group of planes by diagonal) and a second insertion
@@ -265,10 +253,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int vcap = (int) P.imd_off;
     // PIPE: what the tiles of the problem share: {record numbers handed out, overflow}, prog[max_tiles],
     // best[max_tiles][8], rlf[n_im][3]
-    int* __restrict__ sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
-    int* __restrict__ prog = PIPE ? sy + 2 : nullptr;
-    int* __restrict__ tbest = PIPE ? sy + 2 + A.max_tiles : nullptr;
-    int* __restrict__ rlf = PIPE ? sy + 2 + 9 * A.max_tiles : nullptr;
+    int *sy, *prog, *tbest, *rlf;
+    pipe_words<PIPE, SPDP_PIPE_TPW_H_A0>(A, pi, sy, prog, tbest, rlf);
     int vcount = 1;
     int vleft = 0;                                      // PIPE: numbers left of the chunk this wave holds
     bool vover = false;
@@ -277,7 +263,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
         const unsigned long long mask = __ballot(need);
         if (!mask) return 0;
         const int cnt = __popcll(mask);
-        if (PIPE && cnt > vleft) {
+        if (PIPE && cnt > vleft) {                      // numbers come from the problem's counter SPDP_VMF_CHUNK at a time
             int b = 0;
             if (lane == 0) b = __hip_atomic_fetch_add(sy, SPDP_VMF_CHUNK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             vcount = 1 + __builtin_amdgcn_readfirstlane(b);
@@ -295,19 +281,16 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
     };
     auto wait_for = [&](int t, int req) -> bool {
         long spins = 0;
-        while (__hip_atomic_load(prog + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < req) {
+        while (gld<true>(prog + t) < req) {
             __builtin_amdgcn_s_sleep(16);
             if (++spins > (1l << 22)) {                 // (cannot happen with the ticket order; bounds every spin)
-                if (lane == 0) __hip_atomic_store(A.pipe + A.pipe_ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) gst<true>(A.pipe + A.pipe_ticket + 1, 1);
                 return false;
             }
         }
         return true;
     };
-    auto publish = [&](int t, int v) {
-        STORES_DRAINED();
-        if (lane == 0) __hip_atomic_store(prog + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int t, int v) { pipe_publish(prog + t, v, lane == 0); };
     // ---- intermediate rows (MODE 2): hlnk[Noll], vlnk[Noll], lwrb[Noll], uprb[Noll], `width` ints each, entry r - lw + 1
     int* const imd_base = UDH ? A.imd + P.imd_off : nullptr;
     const int64_t us = NOLL * (int64_t) width;
@@ -470,7 +453,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
                 }
                 for (int e = max(res_hi, res_lo) + lane; e < want; e += 64) {
                     const int q = e & (RING - 1);
-                    const int* src[NP * NF]; int val[NP * NF];             // (all planes in flight together: spdp_pipe.h)
+                    const int* src[NP * NF]; int val[NP * NF];             // (all planes in flight together: gld_n, spdp_wave.h)
 #pragma unroll
                     for (int a = 0; a < NP * NF; ++a) src[a] = G(a);
                     gld_n<PIPE>(src, e, val);
@@ -488,7 +471,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
                     Ca[x & (CRING - 1)] = in ? aux[c] : make_short4(0, 0, 0, 0);
                 }
                 cres = c_hi + 1;
-                WAVE_SYNC();
+                lds_done();
             };
             auto COL = [&](int c) -> int4 { return Cc[XC(c) & (CRING - 1)]; };
             auto AUX = [&](int c) -> short4 { return Ca[XC(c) & (CRING - 1)]; };
@@ -527,7 +510,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
                     } else {
                         const int S2 = S - shiftB;
                         if (S2 == S2_begin) {                       // hand the window back and take the one of the new schedule
-                            WAVE_SYNC();
+                            lds_done();
                             for (int e = res_lo + lane; e < res_hi; e += 64) {
                                 const int q = e & (RING - 1);
 #pragma unroll
@@ -844,7 +827,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
                     }
                 }
             }
-            WAVE_SYNC();
+            lds_done();
             for (int e = res_lo + lane; e < res_hi; e += 64) {
                 const int q = e & (RING - 1);
 #pragma unroll
@@ -899,7 +882,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
             best = bb; best_m = bm; best_n = bn;
         }
     } else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    if (UDH) { for (int i = lane; i < 10 * (n_im + 1); i += 64) cpos[i] = EOU; STORES_DRAINED(); }
+    if (UDH) { for (int i = lane; i < 10 * (n_im + 1); i += 64) cpos[i] = EOU; stores_drained(); }
 
     // ---- the end of the alignment: the tracked local maximum, or lastH_ng / hlastH_ng on the last row
     // staging for the sequential relaxations: entries [e0, e0 + cnt) of H through the LDS arrays, cnt <= RING
@@ -907,14 +890,14 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
         for (int i = lane; i < cnt; i += 64)
 #pragma unroll
             for (int a = 0; a < NF; ++a) L[a][i] = gld<PIPE>(G(a) + e0 + i);
-        WAVE_SYNC();
+        lds_done();
     };
     auto stage_out = [&](int e0, int from, int cnt) {
-        WAVE_SYNC();
+        lds_done();
         for (int i = from + lane; i < cnt; i += 64)
 #pragma unroll
             for (int a = 0; a < NF; ++a) gst<PIPE>(G(a) + e0 + i, L[a][i]);
-        if (PIPE) STORES_DRAINED(); else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        if (PIPE) stores_drained(); else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
     };
     auto at = [&](int i) { St s = black;
 #pragma unroll
@@ -999,7 +982,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
                     mx_v = y;
                 }
             }
-            if (PIPE) STORES_DRAINED(); else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+            if (PIPE) stores_drained(); else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
         }
         mx_r = __shfl(mx_r, 0); mx_v = __shfl(mx_v, 0);
         bool from_f = false;
@@ -1068,7 +1051,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
         R.score = fin.v; R.mr = ar; R.nr = br; R.maxt = 0; R.maxr = 0; R.pad[0] = R.pad[1] = R.pad[2] = 0;
         if (!FWD) { if (lane == 0) A.res[pi] = R; return; }
         int vtotal = vcount;                                        // numbers handed out
-        if (PIPE) { STORES_DRAINED(); vtotal = 1 + __hip_atomic_load(sy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        if (PIPE) { stores_drained(); vtotal = 1 + __hip_atomic_load(sy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (gld<true> moves 17 lines here)
         else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
         const bool over_any = __any(vover);
         if (lane == 0) {

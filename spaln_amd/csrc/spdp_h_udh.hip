@@ -20,33 +20,7 @@
 #include <stdint.h>
 #include "spdp_h_dev.h"
 #include "spdp_h_internal.h"
-
-typedef short s16;
-// int16 scores in the upper half of 32-bit registers: see spdp_h_kernels.hip
-typedef int q16;
-#define Q16(x) ((q16) ((unsigned) (x) << 16))
-__device__ __forceinline__ q16 qadd(q16 a, q16 b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ q16 qmax(q16 a, q16 b) { return a > b ? a : b; }
-__device__ __forceinline__ s16 sadd(s16 a, s16 b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ s16 smax(s16 a, s16 b) { return a > b ? a : b; }
-
-#define DPP_ROW_SR(n) (0x110 + (n))
-#define DPP_ROW_RR(n) (0x120 + (n))
-__device__ __forceinline__ int row_shr1(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, DPP_ROW_SR(1), 0xf, 0xf, false);
-}
-__device__ __forceinline__ int row_ror1(int src)
-{
-    return __builtin_amdgcn_mov_dpp(src, DPP_ROW_RR(1), 0xf, 0xf, true);
-}
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int4 ld_nt4(const int4* p)
-{
-    const v4i_t v = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
-    return make_int4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ int ld_nt1(const int* p) { return __builtin_nontemporal_load(p); }
+#include "spdp_wave.h"
 
 #define SPDH_PEN_TAB 2048
 #define END_OF_ULK (INT32_MAX - 2)

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spdp_hsp_dev.h"
+#include "spdp_wave.h"
 
 namespace {
 
@@ -31,10 +32,6 @@ constexpr uint32_t EMPTY = 0xffffffffu;
 __constant__ uint8_t HSP_NCRED[17] = {15, 15, 0, 1, 4, 2, 5, 6, 10, 3, 7, 8, 10, 9, 12, 13, 14};
 __constant__ uint8_t HSP_NCELEM[17] = {0, 0, 0, 1, 2, 2, 0, 2, 0, 3, 3, 3, 1, 1, 2, 3, 0};
 __constant__ uint8_t HSP_MOST_ABUNDANT[4] = {14, 3, 10, 13};
-
-__device__ __forceinline__ int lane_id() { return (int) threadIdx.x; }
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ void wave_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
 // ---- the two sequences as the search reads them -----------------------------------------------------------------------------
 struct Region {                         // [0, len) of the region in the orientation of the search; translated when bbt == 3

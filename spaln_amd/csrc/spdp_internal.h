@@ -251,7 +251,8 @@ static inline hipError_t spdp_copy_sync(void* dst, const void* src, size_t n, hi
     return e != hipSuccess ? e : hipStreamSynchronize(s);
 }
 
-// Host side of the tile / stripe pipelines of the -A0 and -A1 engines, cDNA and protein alike (device side: spdp_pipe.h).
+// Host side of the tile / stripe pipelines of the -A0 and -A1 engines, cDNA and protein alike (device side: spdp_pipe.h,
+// on the wave helpers of spdp_wave.h).
 // The tiles of a problem run as a pipeline of waves: the work list (problem, tile) in dispatch order lies behind the sync
 // words of the problems and their {ticket, stalled} pair.  A wave that waited in vain for the tile above it leaves a mark,
 // and the caller repeats the launch without the pipeline.  Whether a pipeline is wanted (SPDP_A0_PIPE, SPDP_A1_PIPE,
@@ -262,6 +263,8 @@ static inline hipError_t spdp_copy_sync(void* dst, const void* src, size_t n, hi
 //                      -A0 forward / score   -A0 linear space        -A1 (max_im = 0 unless linear space)
 //   cDNA  (ScalarArgs)   2 + 5 mt              2 + 9 mt + max_im       2 + 7 mt + max_im
 //   aa    (HScalarArgs)  2 + 9 mt              2 + 9 mt + 3 max_im     2 + 7 mt + 3 max_im
+// The 2 and the multipliers of mt (words per tile: prog + best[.]), as pipe_words() of spdp_pipe.h carves the words up:
+enum { SPDP_PIPE_HDR = 2, SPDP_PIPE_TPW_A0 = 5, SPDP_PIPE_TPW_A0_UDH = 9, SPDP_PIPE_TPW_A1 = 7, SPDP_PIPE_TPW_H_A0 = 9, SPDP_PIPE_TPW_H_A1 = 7 };
 struct TilePipe {
     std::vector<int> items;                 // (problem or group, tile) pairs in dispatch order
     int max_tiles = 1;                      // most tiles of one problem

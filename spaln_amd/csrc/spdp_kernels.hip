@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include "spdp_dev.h"
 #include "spdp_internal.h"
+#include "spdp_wave.h"
 
 enum { FL_SCORE = 0, FL_FORWARD = 1, FL_UDH = 2 };
 
@@ -37,88 +38,8 @@ enum { TB_DIAG = 1, TB_HORI = 2, TB_VERT = 8, TB_ACCR = 14, TB_NHOR = 16, TB_NVE
 
 #define END_OF_ULK (INT32_MAX - 2)
 
-#define DPP_ROW_SL(n) (0x100 + (n))
-#define DPP_ROW_SR(n) (0x110 + (n))
-#define DPP_ROW_RR(n) (0x120 + (n))
-
-// lane i of every 16-lane row <- lane i-1; lane 0 of the row keeps `old`
-__device__ __forceinline__ int row_shr1(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, DPP_ROW_SR(1), 0xf, 0xf, false);
-}
-// lane 0 of every row <- lane J of that row (other lanes: don't care)
-template <int J>
-__device__ __forceinline__ int row_pick(int src)
-{
-    if constexpr (J == 0) return src;
-    else return __builtin_amdgcn_mov_dpp(src, DPP_ROW_SL(J), 0xf, 0xf, true);
-}
-// lane 0 of every row <- lane 15 of that row
-__device__ __forceinline__ int row_ror1(int src)
-{
-    return __builtin_amdgcn_mov_dpp(src, DPP_ROW_RR(1), 0xf, 0xf, true);
-}
-
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
-__device__ __forceinline__ int sadd16(int a, int b) { return max(a + b, SPDP_FLOOR16); }
-
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-// L1-bypassing loads for data another row of this wave stored a few blocks ago
-__device__ __forceinline__ int4 ld_nt4(const int* p)
-{
-    const v4i_t v = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
-    return make_int4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ int2 ld_nt2(const int* p)
-{
-    const v2i_t v = __builtin_nontemporal_load(reinterpret_cast<const v2i_t*>(p));
-    return make_int2(v.x, v.y);
-}
-
-// Boundary entries that cross CUs (CROSS kernels): the per-XCD L2s are not coherent with each other, so every
-// access to the boundary array goes to the memory side -- agent-scope relaxed atomics compile to sc1
-// loads / stores (write-through, no allocation of stale lines); a flag published after the stores have
-// drained (s_waitcnt vmcnt(0)) orders them for the consumer.
-template <bool X> __device__ __forceinline__ int ld_b1(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return __builtin_nontemporal_load(p);
-}
-template <bool X> __device__ __forceinline__ int4 ld_b4(const int* p)
-{
-    if constexpr (X) return make_int4(ld_b1<true>(p), ld_b1<true>(p + 1), ld_b1<true>(p + 2), ld_b1<true>(p + 3));
-    else return ld_nt4(p);
-}
-template <bool X> __device__ __forceinline__ int2 ld_b2(const int* p)
-{
-    if constexpr (X) return make_int2(ld_b1<true>(p), ld_b1<true>(p + 1));
-    else return ld_nt2(p);
-}
-template <bool X> __device__ __forceinline__ void st_b1(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-template <bool X> __device__ __forceinline__ void st_b4(int* p, int4 v)
-{
-    if constexpr (X) { st_b1<true>(p, v.x); st_b1<true>(p + 1, v.y); st_b1<true>(p + 2, v.z); st_b1<true>(p + 3, v.w); }
-    else *reinterpret_cast<int4*>(p) = v;
-}
-template <bool X> __device__ __forceinline__ void st_b2(int* p, int2 v)
-{
-    if constexpr (X) { st_b1<true>(p, v.x); st_b1<true>(p + 1, v.y); }
-    else *reinterpret_cast<int2*>(p) = v;
-}
-
 template <bool B> struct BoolTag { static constexpr bool value = B; };
-
-// Ordering inside ONE wave needs no hardware fence: a wave's LDS instructions execute in order, and so
-// do its vector-memory instructions (a load issued after a store of the same wave to the same address
-// observes it; the rows of a pass are >= SPDP_GROUP_LAG blocks apart anyway).  Only the compiler must
-// not move accesses across these points.  (A wavefront-scope __builtin_amdgcn_fence would do, but it
-// makes the compiler emit s_waitcnt vmcnt(0) right after the prefetch loads -- no prefetch left.)
-#define WAVE_ORDER() asm volatile("" ::: "memory")
 
 // intron-length penalty modes: flat (nquant == 1, the -A3 model), LDS table, select chain
 enum { NQ_FLAT = 0, NQ_TABLE = 1, NQ_CHAIN = 2 };
@@ -240,11 +161,11 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
             const int tot = P.n_im * 4 * width;
             // (CROSS: memory-side stores -- a dirty line left in one XCD's L2 would later overwrite the links
             //  another XCD's wave stores into the same line)
-            for (int e = lane + 64 * w; e < tot && active; e += 64 * W) st_b1<CROSS>(imd + e, END_OF_ULK);
+            for (int e = lane + 64 * w; e < tot && active; e += 64 * W) gst<CROSS>(imd + e, END_OF_ULK);
         }
         if constexpr (CROSS) {
             // all blocks of the problem have initialised their share before any pass starts
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            stores_drained();
             __syncthreads();
             if (threadIdx.x == 0) {
                 // One word decides: arrivals count in the low bits; a block that waited too long sets GIVEUP and leaves,
@@ -406,8 +327,8 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
                         const int r = n_start - (ml + 1);
                         donor_r = r;
                         if (k == 0) {
-                            Hd = ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW]);
-                            if constexpr (FL == FL_UDH) Cd = ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW + 2]);
+                            Hd = gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW]);
+                            if constexpr (FL == FL_UDH) Cd = gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW + 2]);
                         }
                     }
                     // ---- this block's chunk (prefetched one block ago) goes to LDS ...
@@ -508,12 +429,12 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
                             const int rj = n - (ml + 1) - 2 * k;            /* my cell's diagonal */         \
                             if (imd_row && k == k8 && rj >= lw && rj <= up && n < n_end) {                   \
                                 int* hl0 = imd_p + BIDX(rj);                                                 \
-                                if (spj && is_acc) { st_b1<CROSS>(hl0, donor_r); st_b1<CROSS>(hl0 + width, donor_r + width); rlst = rj; } \
+                                if (spj && is_acc) { gst<CROSS>(hl0, donor_r); gst<CROSS>(hl0 + width, donor_r + width); rlst = rj; } \
                                 if (spj && is_don) donor_r = rj;                                             \
                                 if (pb3 == 0) rlst = rj;                                                     \
-                                if (pb3 == 1) st_b1<CROSS>(hl0, rlst);                                       \
-                                st_b1<CROSS>(hl0 + 2 * width, Cs);  Cs = rj;                                 \
-                                st_b1<CROSS>(hl0 + 3 * width, FCs); FCs = rj + width;                        \
+                                if (pb3 == 1) gst<CROSS>(hl0, rlst);                                         \
+                                gst<CROSS>(hl0 + 2 * width, Cs);  Cs = rj;                                   \
+                                gst<CROSS>(hl0 + 3 * width, FCs); FCs = rj + width;                          \
                             }                                                                                \
                         }                                                                                    \
                         if (LOCAL && LocalR) {                                                               \
@@ -559,14 +480,14 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
                 // vector memory path, loads bypass L1), so only the compiler needs a fence here
                 WAVE_ORDER();
                 if (W > 1) {                                            // publish: this block's stores are done
-                    if constexpr (CROSS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if constexpr (CROSS) stores_drained();
                     else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     if (lane == 0)
                         __hip_atomic_store(&s_prog[w], pass * BIGB + blk + 1, __ATOMIC_RELAXED, PSCOPE);
                 }
             }
             if (W > 1) {
-                if constexpr (CROSS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if constexpr (CROSS) stores_drained();
                 else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (lane == 0)
                     __hip_atomic_store(&s_prog[w], (pass + 1) * BIGB, __ATOMIC_RELAXED, PSCOPE);
@@ -628,7 +549,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
         auto argmax_first = [&](int lo, int hi) {
             int bv = INT32_MIN, bi = INT32_MAX;
             for (int r = lo + lane; r < hi; r += 64) {
-                const int v = ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW]);
+                const int v = gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW]);
                 if (v > bv) { bv = v; bi = r; }
             }
             for (int off = 32; off; off >>= 1) {
@@ -643,11 +564,11 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
             const int r2 = min(up - 1, b_right - a_left);
             int mv = argmax_first(rr, r2);
             if (r2 - rr < 1) mv = rr;
-            if (ld_b1<CROSS>(&bnd[(int64_t) BIDX(mv) * BW]) > ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW])) maxr = mv;
+            if (gld<CROSS>(&bnd[(int64_t) BIDX(mv) * BW]) > gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW])) maxr = mv;
         }
-        R.score = ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]);
+        R.score = gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]);
         if (maxr > rr) R.mr = b_right - maxr; else R.nr = a_right + maxr;
-        if constexpr (FL == FL_UDH) R.ulk = ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW + 2]);
+        if constexpr (FL == FL_UDH) R.ulk = gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW + 2]);
         R.maxr = maxr;
     }
     if (lane == 0) A.res[pi] = R;

@@ -14,13 +14,11 @@
 #include <stdint.h>
 #include "spdp_dev.h"
 #include "spdp_internal.h"
+#include "spdp_wave.h"
 
 #define LN 16
 #define LNEV SPDP_NEV16
 #define L_EOU (0x7fffffff - 2)
-
-__device__ __forceinline__ int l_sadd(int a, int b) { return max(a + b, SPDP_FLOOR16); }
-__device__ __forceinline__ int l_up(int v) { return __shfl_up(v, 1, LN); }
 
 __global__ void __launch_bounds__(64) spdp_local_udh(ScalarArgs A)
 {
@@ -122,9 +120,9 @@ __global__ void __launch_bounds__(64) spdp_local_udh(ScalarArgs A)
             const int Hq = pp ? H0 : H1, Hp = pp ? H1 : H0;
             const int Bq = pp ? B0 : B1, Bp = pp ? B1 : B0;
             const int Cq = pp ? C0 : C1, Cp = pp ? C1 : C0;
-            int uHq = l_up(Hq), uF = l_up(F), uHp = l_up(Hp);
-            int uBq = l_up(Bq), uFB = l_up(FB), uBp = l_up(Bp);
-            int uCq = l_up(Cq), uFC = l_up(FC), uCp = l_up(Cp);
+            int uHq = up16(Hq), uF = up16(F), uHp = up16(Hp);
+            int uBq = up16(Bq), uFB = up16(FB), uBp = up16(Bp);
+            int uCq = up16(Cq), uFC = up16(FC), uCp = up16(Cp);
             if (k == 0) {
                 uHq = hv[r + 1]; uF = fv[r + 1]; uHp = hv[r];
                 // the reference feeds the `ml` lanes from the boundary rows only with local left ends; otherwise
@@ -138,7 +136,7 @@ __global__ void __launch_bounds__(64) spdp_local_udh(ScalarArgs A)
             if (nj >= 0 && nj <= b_right + 1) col = cols[nj];
             if (k >= kb && k < ke) pv = mrow[col.y];
             if (spj) {
-                const int u3 = l_up(s3), u5 = l_up(s5);
+                const int u3 = up16(s3), u5 = up16(s5);
                 if (k == 0) {
                     const int2 c0 = cols[min(n, b_right + 1)];
                     s3 = kb ? 0 : (c0.x >> 16);
@@ -147,31 +145,31 @@ __global__ void __launch_bounds__(64) spdp_local_udh(ScalarArgs A)
             }
             // horizontal
             {
-                const int opn = l_sadd(Hq, gn), ext = l_sadd(E, ge);
+                const int opn = sadd16(Hq, gn), ext = sadd16(E, ge);
                 if (ext > opn) E = ext;
                 else { E = opn; EB = Bq; EC = Cq; }
             }
             // vertical
             int f, fbk, fck;
             {
-                const int fext = l_sadd(uF, ge), fopn = l_sadd(uHq, gn);
+                const int fext = sadd16(uF, ge), fopn = sadd16(uHq, gn);
                 if (fext > fopn) { f = fext; fbk = uFB; fck = uFC; }
                 else { f = fopn; fbk = uBq; fck = uCq; }
             }
             // diagonal, best of three, acceptor
-            int h = l_sadd(pv, uHp), hbk = uBp, hck = uCp, pb3 = 0;
+            int h = sadd16(pv, uHp), hbk = uBp, hck = uCp, pb3 = 0;
             if (f > h) { h = f; pb3 = 2; hbk = fbk; hck = fck; }
             if (E > h) { h = E; pb3 = 1; hbk = EB; hck = EC; }
             is_acc = 0;
             if (spj) {
-                int x = l_sadd(l_sadd(D, s3), qpen(hil));
+                int x = sadd16(sadd16(D, s3), qpen(hil));
                 if (!(hil > llmt)) x = LNEV;
                 if (x > h) { h = x; is_acc = 1; hbk = DB; hck = DC; }
             }
             if (LocalL && 0 > h) h = 0;
             is_don = 0;
             if (spj) {
-                const int qd = l_sadd(h, s5);
+                const int qd = sadd16(h, s5);
                 if (qd > D) { D = qd; is_don = 1; DB = hbk; DC = hck; hil = 0; }
                 hil = min(hil + 1, 32767);
             }

@@ -1,43 +1,32 @@
-// spdp_pipe.h -- two helpers of the wavefront kernels whose tiles / stripes run as pipelines of waves
-// (spdp_rowwave.hip, spdp_h_rowwave.hip): round 5.
+// spdp_pipe.h -- device side of TilePipe (spdp_internal.h): what the five kernels whose tiles / stripes run as a pipeline of
+// waves (spdp_rowwave, spdp_rowwave_udh, spdh_rowwave, spdp_exact, spdh_exact) share of that protocol.  A wave draws a work
+// item from the ticket counter, so a tile's predecessor is always resident or done; the arrays the tiles share cross CUs
+// (gld / gst<true>, spdp_wave.h); a tile publishes how far it has handed its entries back once its stores have drained, and
+// waits for the word of the tile above before it reads.
+// Here: where a problem's sync words lie, and the publish.  The ticket draw, the wait and the Vmf record allocators are
+// still written out in each kernel, on the helpers of spdp_wave.h: as functions they compute the same, but the compiler
+// lays the sweep around them out differently (MEASUREMENTS.md has the sizes), and these kernels are at their register
+// budgets -- they move here once that layout has been timed.  Keep the copies in step until then.
 #ifndef SPDP_PIPE_H
 #define SPDP_PIPE_H
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "spdp_internal.h"
+#include "spdp_wave.h"
 
-// a problem record every lane has read from the same address: its words, said to be wave-uniform, live in SGPRs -- and so
-// does everything computed from them (ranges, array bases, loop bounds)
-template <class T> __device__ __forceinline__ T wave_uniform(const T& t)
+// the sync words of problem pi as TilePipe laid them out; TPW: the engine's SPDP_PIPE_TPW_* (spdp_internal.h)
+template <bool PIPE, int TPW, class Args>
+__device__ __forceinline__ void pipe_words(const Args& A, int pi, int*& sy, int*& prog, int*& tbest, int*& rlf)
 {
-    static_assert(sizeof(T) % 4 == 0, "words");
-    T r;
-    const int* src = reinterpret_cast<const int*>(&t);
-    int* dst = reinterpret_cast<int*>(&r);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; ++i) dst[i] = __builtin_amdgcn_readfirstlane(src[i]);
-    return r;
+    sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
+    prog = PIPE ? sy + SPDP_PIPE_HDR : nullptr;
+    tbest = PIPE ? sy + SPDP_PIPE_HDR + A.max_tiles : nullptr;
+    rlf = PIPE ? sy + SPDP_PIPE_HDR + TPW * A.max_tiles : nullptr;
 }
 
-// The diagonal arrays of a pipelined problem cross CUs; the agent-scope atomic load the compiler emits for each entry is
-// followed by a wait of its own -- a refill of ten planes was ten memory round trips in a row.  The same loads (sc1: the
-// memory side, past the non-coherent L2s) issued together, one wait.  The compiler does not know these loads are
-// asynchronous: nothing may look at v[] before the wait, which the empty statements behind it see to.
-template <bool X, int N>
-__device__ __forceinline__ void gld_n(const int* const (&base)[N], int e, int (&v)[N])      // v[i] = base[i][e], base[] wave-uniform
+// what this wave stored is out before the word says so; one lane (of the wave, or of each group) stores the word
+__device__ __forceinline__ void pipe_publish(int* word, int v, bool i_store)
 {
-    if constexpr (X) {
-        const unsigned off = (unsigned) e * 4u;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            asm volatile("global_load_dword %0, %1, %2 sc1" : "=v"(v[i]) : "v"(off), "s"(base[i]));
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = __builtin_nontemporal_load(base[i] + e);
-    }
+    stores_drained();
+    if (i_store) gst<true>(word, v);
 }
 
 #endif

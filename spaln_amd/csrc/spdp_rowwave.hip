@@ -70,12 +70,8 @@ __device__ __forceinline__ int intpen_of_u(const TablesU& T, const ScalarArgs& A
     if (A.ipen_runs) return ipen_runs_get(T.runs, len, A.intpen_len);          // (kernel-uniform)
     return len >= A.intpen_len ? A.intpen[A.intpen_len - 1] : A.intpen[len];
 }
-// LDS traffic inside ONE wave needs no barrier (its DS instructions execute in order); the compiler must keep it so
-#define WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-
 // the three states a candidate can splice from / into: the cell's diagonal value, the horizontal and the vertical gap
 enum { K_H = 0, K_E = 1, K_F = 2, K_E2 = 3, K_F2 = 4 };   // hf[] of the reference: DIAG, HORI, VERT, HORL, VERL (the last two with Noll = 3)
-__device__ __forceinline__ int psp_bit(int k) { return k == 0 ? 4 : (k == 1 ? 1 : (k == 2 ? 8 : (k == 3 ? 2 : 16))); }    // src/aln.h:56
 
 struct Lds2 {
     int hv[RING], fv[RING];
@@ -92,18 +88,8 @@ template <bool DAGP> using Lds = typename Lds_of<DAGP>::type;
 // (ScalarArgs::items lists (problem, tile) in dispatch order; a wave draws the next one from a ticket counter, so a
 // tile's predecessor is always resident or done).  The arrays then cross CUs: their accesses go to the memory side
 // (agent-scope atomics, the per-XCD L2s are not coherent with each other) and a tile publishes, after its stores have
-// drained, the anti-diagonal up to which it has handed its entries back (prog[tile], +1; INT_MAX = finished).
-template <bool X> __device__ __forceinline__ int gld(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return __builtin_nontemporal_load(p);
-}
-template <bool X> __device__ __forceinline__ void gst(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-#define STORES_DRAINED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// drained, the anti-diagonal up to which it has handed its entries back (prog[tile], +1; INT_MAX = finished).  Where the
+// sync words lie and the publish: spdp_pipe.h; what the words mean is said here.
 
 // ---- an experiment kept behind SPDP_COLFEED (default off: measured slower).  The column records.  A lane loaded the record of its own column (two steps ahead), but any wait for such a load is a
 //     wait for EVERYTHING the wave has in flight (one in-order counter for loads and stores on gfx9), and the compiler, with
@@ -138,8 +124,8 @@ struct ColFeed {
     {
         const int nx = (int) (unsigned) rc;
         const int ny = ((int) (rc >> 32) & 0xff) | (int) (((ra >> sh) & 0xffffu) << 8);
-        x = __builtin_amdgcn_update_dpp(nx, x, 0x138, 0xf, 0xf, false);          // wave_shr:1, lane 0 keeps `old` = the new record
-        ya = __builtin_amdgcn_update_dpp(ny, ya, 0x138, 0xf, 0xf, false);
+        x = wave_shr1(nx, x);                               // lane 0 keeps `old` = the new record
+        ya = wave_shr1(ny, ya);
     }
 };
 // CUT: forwardS_ng with a cut range (`cutrng`, src/fwd2s1.cc:217, 423-430; shortcutS_ng :1899-1930): a row that reaches
@@ -199,9 +185,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
     int* __restrict__ vraw = reinterpret_cast<int*>(vrec);
     const int vcap = (int) P.imd_off;
     // PIPE: what the tiles of the problem share: {records appended, overflow}, prog[max_tiles], best[max_tiles][4]
-    int* __restrict__ sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
-    int* __restrict__ prog = PIPE ? sy + 2 : nullptr;
-    int* __restrict__ tbest = PIPE ? sy + 2 + A.max_tiles : nullptr;
+    int *sy, *prog, *tbest, *rlf_;
+    pipe_words<PIPE, SPDP_PIPE_TPW_A0>(A, pi, sy, prog, tbest, rlf_);
     int vcount = 2;                                     // wave-uniform; records 0 (dummy) and 1 (start) below
     int vleft = 0;                                      // PIPE: numbers left of the chunk this wave holds
     bool vover = false;
@@ -210,8 +195,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
         const unsigned long long mask = __ballot(need);
         if (!mask) return 0;
         const int cnt = __popcll(mask);
-        if (PIPE && cnt > vleft) {                      // numbers come from the problem's counter SPDP_VMF_CHUNK at a time:
-            int b = 0;                                  // they differ from the one-wave order, the chains do not
+        if (PIPE && cnt > vleft) {                      // numbers come from the problem's counter SPDP_VMF_CHUNK at a time
+            int b = 0;
             if (lane == 0) b = __hip_atomic_fetch_add(sy, SPDP_VMF_CHUNK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             vcount = 2 + __builtin_amdgcn_readfirstlane(b);
             vleft = SPDP_VMF_CHUNK;
@@ -230,19 +215,16 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
     // resident: cannot happen with the ticket order, kept as a bound on every spin)
     auto wait_for = [&](int t, int req) -> bool {
         long spins = 0;
-        while (__hip_atomic_load(prog + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < req) {
+        while (gld<true>(prog + t) < req) {
             __builtin_amdgcn_s_sleep(16);
-            if (++spins > (1l << 22)) {
-                if (lane == 0) __hip_atomic_store(A.pipe + A.pipe_ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (++spins > (1l << 22)) {                 // (cannot happen with the ticket order; bounds every spin)
+                if (lane == 0) gst<true>(A.pipe + A.pipe_ticket + 1, 1);
                 return false;
             }
         }
         return true;
     };
-    auto publish = [&](int t, int v) {
-        STORES_DRAINED();
-        if (lane == 0) __hip_atomic_store(prog + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int t, int v) { pipe_publish(prog + t, v, lane == 0); };
 
     // ---- the arrays as vset / initS_ng (sinitS_ng) leave them
     if (t_lo == 0) {
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
                 if constexpr (DAGP) { L.f2v[q] = val[FWD ? 5 : 2]; if constexpr (FWD) L.f2p[q] = val[6]; }
             }
             res_hi = max(res_hi, want);
-            WAVE_SYNC();
+            lds_done();
         };
         // the column records of my next two cells are already on their way when a step starts
         auto ld_col = [&](int vv, int2& c, int& a2) {
@@ -528,7 +510,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
         // everything still resident goes back
         {
-            WAVE_SYNC();
+            lds_done();
             for (int e = res_lo + lane; e < res_hi; e += 64) {
                 const int q = e & (RING - 1);
                 gst<PIPE>(gHv + e, L.hv[q]); gst<PIPE>(gFv + e, L.fv[q]);
@@ -554,7 +536,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
         publish(ti, INT32_MAX);
         if (ti != n_tiles - 1) return;
         // the wave of the last tile ends the problem
-        vover = __hip_atomic_load(sy + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+        vover = gld<true>(sy + 1) != 0;
         if (LocalR) {
             best_v = NEV; best_m = al; best_n = bl; best_p = 0;
             for (int t = lane; t < n_tiles; t += 64) {              // tiles in row order: the first maximum wins
@@ -625,7 +607,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
         R.score = GH(mx);
     }
     int vtotal = vcount;                                            // numbers handed out
-    if (PIPE) { STORES_DRAINED(); vtotal = 2 + __hip_atomic_load(sy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    if (PIPE) { stores_drained(); vtotal = 2 + gld<true>(sy); }
     else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
     const bool over_any = __any(vover);
     // Vmf::traceback(ptr) + the boundary record of trcbkalignS_ng, by one lane
@@ -753,25 +735,20 @@ __global__ __launch_bounds__(64 * WPBU<DAGP>) __attribute__((amdgpu_waves_per_eu
     int* cpos = A.cpos + (int64_t) pi * A.cpos_stride;
 #define CPOS(i, c) cpos[(i) * 10 + (c)]
     // PIPE: what the tiles of the problem share: prog[max_tiles], best[max_tiles][8], rlf[n_im]
-    int* __restrict__ sy = PIPE ? A.pipe + (size_t) pi * A.pipe_stride : nullptr;
-    int* __restrict__ prog = PIPE ? sy + 2 : nullptr;
-    int* __restrict__ tbest = PIPE ? sy + 2 + A.max_tiles : nullptr;
-    int* __restrict__ rlf = PIPE ? sy + 2 + 9 * A.max_tiles : nullptr;
+    int *sy, *prog, *tbest, *rlf;
+    pipe_words<PIPE, SPDP_PIPE_TPW_A0_UDH>(A, pi, sy, prog, tbest, rlf);
     auto wait_for = [&](int t, int req) -> bool {
         long spins = 0;
-        while (__hip_atomic_load(prog + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < req) {
+        while (gld<true>(prog + t) < req) {
             __builtin_amdgcn_s_sleep(16);
-            if (++spins > (1l << 22)) {
-                if (lane == 0) __hip_atomic_store(A.pipe + A.pipe_ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (++spins > (1l << 22)) {                 // (cannot happen with the ticket order; bounds every spin)
+                if (lane == 0) gst<true>(A.pipe + A.pipe_ticket + 1, 1);
                 return false;
             }
         }
         return true;
     };
-    auto publish = [&](int t, int v) {
-        STORES_DRAINED();
-        if (lane == 0) __hip_atomic_store(prog + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int t, int v) { pipe_publish(prog + t, v, lane == 0); };
     auto imd_init = [&](int i) {
         int* b = imd_base + (int64_t) i * 4 * us;
         for (int64_t q = lane; q < us; q += 64) {
@@ -866,7 +843,7 @@ __global__ __launch_bounds__(64 * WPBU<DAGP>) __attribute__((amdgpu_waves_per_eu
                     for (int a = 0; a < NA; ++a) lds[a][q] = val[a];
                 }
                 res_hi = max(res_hi, want);
-                WAVE_SYNC();
+                lds_done();
             };
             auto ld_col = [&](int nn, int2& c, int& a2) {
                 if (any && nn >= n_first && nn <= n_last) { c = cols[nn]; a2 = reinterpret_cast<const unsigned short*>(aux)[nn]; }
@@ -1069,7 +1046,7 @@ __global__ __launch_bounds__(64 * WPBU<DAGP>) __attribute__((amdgpu_waves_per_eu
                 }
                 if constexpr (!OWN) feed.arrived();
             }
-            WAVE_SYNC();
+            lds_done();
             for (int e = res_lo + lane; e < res_hi; e += 64) {
                 const int q = e & (RING - 1);
 #pragma unroll
@@ -1109,7 +1086,7 @@ __global__ __launch_bounds__(64 * WPBU<DAGP>) __attribute__((amdgpu_waves_per_eu
         }
     } else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
     for (int i = lane; i < 10 * (n_im + 1); i += 64) cpos[i] = EOU;
-    STORES_DRAINED();
+    stores_drained();
 
     // ---- the end cell (hlastS_ng) or the tracked local maximum
     auto GL = [&](int arr, int r) { return gld<PIPE>(G(arr) + (r - (lw - 1))); };

@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include "spdp_dev.h"
 #include "spdp_internal.h"
+#include "spdp_wave.h"
 
 namespace {
 
@@ -46,44 +47,9 @@ constexpr float BIGF = 4194304.f;               // 2^22: pushes a candidate belo
 __device__ __forceinline__ float as_f(int x) { return __int_as_float(x); }
 __device__ __forceinline__ int as_i(float x) { return __float_as_int(x); }
 
-// lane i of every 16-lane row <- lane i-1; lane 0 of the row keeps `old`
-__device__ __forceinline__ int row_shr1(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, 0x111, 0xf, 0xf, false);
-}
-__device__ __forceinline__ float row_shr1(float old, float src) { return as_f(row_shr1(as_i(old), as_i(src))); }
-
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int4 ld_nt4(const int* p)
-{
-    const v4i_t v = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
-    return make_int4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ int2 ld_nt2(const int* p)
-{
-    const v2i_t v = __builtin_nontemporal_load(reinterpret_cast<const v2i_t*>(p));
-    return make_int2(v.x, v.y);
-}
-// boundary entries: L1-bypassing inside one CU, memory-side (sc1) when a problem spans CUs -- see spdp_kernels.hip
-template <bool X> __device__ __forceinline__ int ld_b1(const int* p)
-{
-    if constexpr (X) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return __builtin_nontemporal_load(p);
-}
-template <bool X> __device__ __forceinline__ int4 ld_b4(const int* p)
-{
-    if constexpr (X) return make_int4(ld_b1<true>(p), ld_b1<true>(p + 1), ld_b1<true>(p + 2), ld_b1<true>(p + 3));
-    else return ld_nt4(p);
-}
-template <bool X> __device__ __forceinline__ int2 ld_b2(const int* p)
-{
-    if constexpr (X) return make_int2(ld_b1<true>(p), ld_b1<true>(p + 1));
-    else return ld_nt2(p);
-}
-// ... as plain (non-atomic) buffer loads with the same scope bit: the agent-scope ATOMIC load above is followed by a wait of
-// its own, so the "prefetch" of a cross-CU pass was four memory round trips the wave sat out, one after the other, per
-// block of sixteen steps (profiles/r04_wave_pmc.txt: 61 % of C5's resident wave cycles in s_waitcnt).  A buffer load with
+// ld_b4 / ld_b2 (spdp_wave.h) as plain (non-atomic) buffer loads with the same scope bit: the agent-scope ATOMIC load there is
+// followed by a wait of its own, so the "prefetch" of a cross-CU pass was four memory round trips the wave sat out, one after
+// the other, per block of sixteen steps (profiles/r04_wave_pmc.txt: 61 % of C5's resident wave cycles waiting).  A buffer load with
 // sc1 goes the same way to the memory side, stays in flight, and the compiler counts it (round 5).
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t bnd_rsrc(const int* base)
@@ -100,24 +66,7 @@ template <bool X> __device__ __forceinline__ int2 ldx_b2(rsrc_t r, const int* ba
     if constexpr (X) { const v2i_t v = __builtin_amdgcn_raw_buffer_load_b64(r, (int) (idx * 4), 0, 16); return make_int2(v.x, v.y); }
     else return ld_nt2(base + idx);
 }
-template <bool X> __device__ __forceinline__ void st_b1(int* p, int v)
-{
-    if constexpr (X) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-template <bool X> __device__ __forceinline__ void st_b4(int* p, int4 v)
-{
-    if constexpr (X) { st_b1<true>(p, v.x); st_b1<true>(p + 1, v.y); st_b1<true>(p + 2, v.z); st_b1<true>(p + 3, v.w); }
-    else *reinterpret_cast<int4*>(p) = v;
-}
-template <bool X> __device__ __forceinline__ void st_b2(int* p, int2 v)
-{
-    if constexpr (X) { st_b1<true>(p, v.x); st_b1<true>(p + 1, v.y); }
-    else *reinterpret_cast<int2*>(p) = v;
-}
-
 template <bool B> struct BoolTag { static constexpr bool value = B; };
-#define WAVE_ORDER() asm volatile("" ::: "memory")
 // keeps the read-ahead LDS loads of a step where they were written: without it the scheduler sinks them towards
 // their use (fewer live registers) and the waves wait for LDS again
 #ifndef SPDP_NO_PIN
@@ -257,14 +206,14 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
         if constexpr (UDH) {
             int* imd = A.imd + P.imd_off;
             const int tot = P.n_im * 4 * width;
-            for (int e = lane + 64 * w; e < tot && active; e += 64 * W) st_b1<CROSS>(imd + e, END_OF_ULK);
+            for (int e = lane + 64 * w; e < tot && active; e += 64 * W) gst<CROSS>(imd + e, END_OF_ULK);
         }
         if constexpr (CROSS) {
             // all blocks of the problem have initialised their share before any pass starts.  One word decides:
             // arrivals count in the low bits; a block that waited too long sets GIVEUP and leaves, and so does every
             // block that sees the bit on arrival or while waiting (one that got through just before ends at the bounded
             // wait for its producer); the host then repeats the launch with one CU per problem.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            stores_drained();
             __syncthreads();
             if (threadIdx.x == 0) {
                 constexpr int GIVEUP = 1 << 30;
@@ -451,8 +400,8 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                         const int r = n_start - (ml + 1);
                         donor_r = r;
                         if (k == 0) {
-                            Hd = as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW]));
-                            if constexpr (UDH) Cd = ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW + 2]);
+                            Hd = as_f(gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW]));
+                            if constexpr (UDH) Cd = gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW + 2]);
                         }
                     }
                     // ---- this block's chunk (prefetched one block ago) goes to LDS ...
@@ -578,12 +527,12 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                             if (J >= imd_jlo && J <= imd_jhi) {                                              \
                                 const int rj = imd_r0 + J;                      /* my cell's diagonal */     \
                                 int* const ih = imd_p + (imd_h0 + J);                                        \
-                                if (SPJ && is_acc) { st_b1<CROSS>(ih, donor_r); st_b1<CROSS>(ih + width, donor_r + width); } \
+                                if (SPJ && is_acc) { gst<CROSS>(ih, donor_r); gst<CROSS>(ih + width, donor_r + width); } \
                                 rlst = ((SPJ && is_acc) || pb3 == 0) ? rj : rlst;                            \
                                 if (SPJ) donor_r = is_don ? rj : donor_r;                                    \
-                                if (pb3 == 1) st_b1<CROSS>(ih, rlst);                                        \
-                                st_b1<CROSS>(ih + 2 * width, hc); hc = rj;                                   \
-                                st_b1<CROSS>(ih + 3 * width, fl); fl = imd_r0w + J;                          \
+                                if (pb3 == 1) gst<CROSS>(ih, rlst);                                        \
+                                gst<CROSS>(ih + 2 * width, hc); hc = rj;                                   \
+                                gst<CROSS>(ih + 3 * width, fl); fl = imd_r0w + J;                          \
                             }                                                                                \
                         }                                                                                    \
                         Hd = upH; Hs = h;                                                                    \
@@ -609,7 +558,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                 // steps, the stores of the previous block have long landed and the wait is free
                 if constexpr (CROSS) {
                     if (W > 1 && blk > 0) {
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        stores_drained();
                         if (lane == 0) __hip_atomic_store(&s_prog[w], pass * BIGB + blk, __ATOMIC_RELAXED, PSCOPE);
                     }
                 }
@@ -643,7 +592,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                 }
             }
             if (W > 1) {
-                if constexpr (CROSS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if constexpr (CROSS) stores_drained();
                 else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (lane == 0)
                     __hip_atomic_store(&s_prog[w], (pass + 1) * BIGB, __ATOMIC_RELAXED, PSCOPE);
@@ -694,7 +643,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
         auto argmax_first = [&](int lo, int hi) {
             float bv = -3.0e38f; int bi = INT32_MAX;
             for (int r = lo + ln; r < hi; r += 64) {
-                const float v = as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(r) * BW]));
+                const float v = as_f(gld<CROSS>(&bnd[(int64_t) BIDX(r) * BW]));
                 if (v > bv) { bv = v; bi = r; }
             }
             for (int off = 32; off; off >>= 1) {
@@ -709,11 +658,11 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
             const int r2 = min(up - 1, b_right - a_left);
             int mv = argmax_first(rr, r2);
             if (r2 - rr < 1) mv = rr;
-            if (as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(mv) * BW])) > as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]))) maxr = mv;
+            if (as_f(gld<CROSS>(&bnd[(int64_t) BIDX(mv) * BW])) > as_f(gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]))) maxr = mv;
         }
-        R.score = (int) as_f(ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]));
+        R.score = (int) as_f(gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW]));
         if (maxr > rr) R.mr = b_right - maxr; else R.nr = a_right + maxr;
-        if constexpr (UDH) R.ulk = ld_b1<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW + 2]);
+        if constexpr (UDH) R.ulk = gld<CROSS>(&bnd[(int64_t) BIDX(maxr) * BW + 2]);
         R.maxr = maxr;
     }
     if (ln == 0) A.res[pi] = R;
