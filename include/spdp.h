@@ -42,7 +42,10 @@ extern "C" {
  * subset the _wip engines read (src/aln.h:235-308, src/codepot.h:223-257). */
 typedef struct SpdpScoring {
     int32_t mtx_dim;                 /* Simmtx::dim (17 = NSIMD for DNA)                 */
-    int32_t mtx[32 * 32];            /* row-major mtx[a * mtx_dim + b]                   */
+    int32_t mtx[32 * 32];            /* row-major mtx[a * mtx_dim + b], a = query code, b = genomic code; need not be
+                                      * symmetric.  Row 0 and column 0 (code 0, the nil residue) are read as zero
+                                      * whatever they hold: a caller's values there are ignored.  Every residue code
+                                      * of a problem must be below mtx_dim                                         */
     int32_t gop, gep;                /* PwdB::BasicGOP, BasicGEP (both <= 0)             */
     int32_t lgop, lgep;              /* PwdB::LongGOP, LongGEP                           */
     int32_t noll;                    /* PwdB::Noll: 2 affine, 3 double affine            */
@@ -457,7 +460,9 @@ int spdp_batch_stats(const SpdpBatch* bt, double* out, int n);
 /* PwdB / IntronPenalty / Simmtx subset read by SimdAln2h1 (src/aln.h:235-308) */
 typedef struct SpdpScoringH {
     int32_t mtx_rows, mtx_cols;      /* Simmtx::rows (aa, 23), Simmtx::dim (tron, 26)       */
-    int32_t mtx[32 * 32];            /* row-major mtx[aa * mtx_cols + tron]                 */
+    int32_t mtx[32 * 32];            /* row-major mtx[aa * mtx_cols + tron]; taken as given, but the reference's row 0
+                                      * and column 0 (the nil residue) are zero and callers should keep them so, as
+                                      * SpdpScoring.mtx has them.  Query codes < mtx_rows, tron codes < mtx_cols     */
     int32_t gop, gep;                /* PwdB::BasicGOP, BasicGEP (per codon)                */
     int32_t lgep, codonk1;           /* GapExtPen3(i) = i > codonk1 ? LongGEP : BasicGEP    */
     int32_t gapw1, gapw2, gapw3;     /* PwdB::GapW1 / GapW2 (frame shifts), GapW3 (codon gap open) */

@@ -39,7 +39,7 @@ def build_blk_check(force: bool = False) -> str:
     d = os.path.join(_HERE, "..", "spaln_amd", "csrc")
     srcs = [os.path.join(_HERE, "blk_check.cpp"), os.path.join(d, "spdp_loci.h"), os.path.join(d, "spdp_hsp_host.h"),
             os.path.join(d, "spdp_hsp_chain.h"), os.path.join(d, "spdp_region.h"), os.path.join(d, "spdp_gencode.h"),
-            os.path.join(_HERE, "..", "include", "spdp.h")]
+            os.path.join(d, "spdp_complement.h"), os.path.join(_HERE, "..", "include", "spdp.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     if force or not os.path.exists(_BLK_SO) or os.path.getmtime(_BLK_SO) < newest:
         tmp = f"{_BLK_SO}.{os.getpid()}.tmp"

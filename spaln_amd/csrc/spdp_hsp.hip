@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include "spdp_hsp_dev.h"
 #include "spdp_wave.h"
+#include "spdp_complement.h"
 
 namespace {
 
@@ -40,9 +41,9 @@ struct Region {                         // [0, len) of the region in the orienta
     __device__ __forceinline__ int nuc(int i) const
     {
         if (i < 0 || i >= len) return 0;                        // (the pads of the reference's sequence object)
-        const int c = rvs ? g[len - 1 - i] : g[i];
-        if (!rvs) return c > 16 ? 16 : c;
-        switch (c) { case 2: return 9; case 9: return 2; case 3: return 5; case 5: return 3; default: return c > 16 ? 16 : c; }
+        int c = rvs ? g[len - 1 - i] : g[i];
+        if (c > 16) c = 16;
+        return rvs ? spdp_complement(c) : c;                    // (the ambiguity codes turn with the strand: M <-> K, R <-> Y, ...)
     }
     // Seq::nuc2tron (src/seq.cc:774-798): position p stands for the codon (p - 1, p, p + 1)
     __device__ int at(int p) const

@@ -32,11 +32,6 @@ struct DevMem {                      // scoped device allocation
     template <class T> T* as() const { return (T*) p; }
 };
 
-inline uint8_t other_strand(uint8_t c)   // A 2 <-> T 9, C 3 <-> G 5; ambiguity codes stay as the block search's cut leaves them
-{
-    switch (c) { case 2: return 9; case 9: return 2; case 3: return 5; case 5: return 3; default: return c; }
-}
-
 double since(std::chrono::steady_clock::time_point t)
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
@@ -210,7 +205,7 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         codes_rc.resize((size_t) offs[n]);
         on_host_threads(n, [&](int q) {
             const int64_t a0 = offs[q], len = offs[q + 1] - offs[q];
-            for (int64_t i = 0; i < len; ++i) codes_rc[a0 + i] = other_strand(codes[a0 + len - 1 - i]);
+            for (int64_t i = 0; i < len; ++i) codes_rc[a0 + i] = spdp_region::other_strand(codes[a0 + len - 1 - i]);
         });
     }
     SpdpSignalModel sigm = *sigmodel;
@@ -259,7 +254,7 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             const SpdpLocus& L = loci[c0 + (j < m ? j : j - m)];
             const uint8_t* src = genome->codes + genome->chr_off[L.chr] + L.base;
             uint8_t* dst = reg + at[j];
-            if ((L.rvs != 0) == (j < m)) for (int i = 0; i < L.len; ++i) dst[i] = other_strand(src[L.len - 1 - i]);
+            if ((L.rvs != 0) == (j < m)) for (int i = 0; i < L.len; ++i) dst[i] = spdp_region::other_strand(src[L.len - 1 - i]);
             else memcpy(dst, src, (size_t) L.len);
             dst[L.len] = 0;
         });

@@ -7,12 +7,13 @@
 #include <string.h>
 #include <vector>
 #include "spdp_gencode.h"
+#include "spdp_complement.h"
 
 namespace spdp_region {
 
-inline uint8_t other_strand(uint8_t c)  // A 2, C 3, G 5, T 9; the ambiguity codes stay (src/seq.cc: comrev on the 4-bit codes)
+inline uint8_t other_strand(uint8_t c)  // Seq::comrev's code by code: A 2 <-> T 9, C 3 <-> G 5 and the ambiguity codes likewise (M <-> K, ...)
 {
-    switch (c) { case 2: return 9; case 9: return 2; case 3: return 5; case 5: return 3; default: return c; }
+    return c > 16 ? c : (uint8_t) spdp_complement(c);           // (codes beyond the alphabet pass: to_tron reads them as N)
 }
 
 // Seq::nuc2tron (src/seq.cc:774-798, src/utilseq.cc:204-225): position p becomes the codon (p - 1, p, p + 1) in the tron alphabet; the

@@ -27,8 +27,9 @@ from spaln_amd import synth  # noqa: E402
 REF = os.path.join(ROOT, "oracle", "_ref")
 OUT = os.path.dirname(os.path.abspath(__file__))
 COMP = np.zeros(256, dtype=np.uint8)
-for a, b in zip(b"ACGTN", b"TGCAN"):
+for a, b in zip(b"ACGTMRWSYKVHDBN", b"TGCAKYWSRMBDHVN"):      # the full IUPAC complement (Seq::comrev, complcod of src/seq.cc)
     COMP[a] = b
+IUPAC = np.frombuffer(b"MRWSYKVHDB", dtype=np.uint8)
 
 
 def revcomp(s):
@@ -127,16 +128,57 @@ def protein_genome_and_queries(n_genes, n_chr, seed):
     return chroms, queries
 
 
+def iupac_genome_and_queries(n_genes, n_chr, seed, protein=False):
+    """blk_iupac / blk_iupacp: one small genome for both query kinds.  Transcribed genes and coding genes alternate; every
+    second gene of either kind lies on the reverse strand, and those carry an IUPAC letter other than N about every 50 - 100 nt
+    (exons and introns alike), so that words still hit and the search has to read the ambiguity codes of a region through the
+    complement: M <-> K, R <-> Y, H <-> D, V <-> B.  Nucleotide queries (`spaln -W -KD`): transcripts, reverse complements,
+    fragments, diverged copies; protein queries (-KP): the diverged and the exact protein, pieces"""
+    rng = np.random.default_rng(synth.SEED + seed)
+    genes = []
+    for i in range(n_genes):
+        r = np.random.default_rng(synth.SEED + seed + 1 + i)
+        genes.append(synth.make_protein_gene(r, n_exons=4, aa_len=int(rng.integers(150, 300)), flank=300, intron_hi=1000) if i % 2 else
+                     synth.make_gene(r, n_exons=5, mrna_len=900, flank=300, intron_hi=1000))
+    per = n_genes // n_chr
+    chroms = []
+    for c in range(n_chr):
+        parts = []
+        for k, g in enumerate(genes[c * per:(c + 1) * per]):
+            w = g.window
+            if (k // 2) % 2 == 0:                                 # genes 0, 1, 4, 5, ... of a chromosome: the reverse strand
+                w = revcomp(w)
+                at = np.cumsum(rng.integers(50, 101, size=len(w) // 50))
+                at = at[at < len(w)]
+                w[at] = IUPAC[rng.integers(0, len(IUPAC), size=at.size)]
+            parts += [synth.random_dna(rng, int(rng.integers(500, 2000))), w]
+        chroms.append(np.concatenate(parts))
+    queries = []
+    for i, g in enumerate(genes):
+        s = g.query
+        if i % 2 != int(protein):
+            continue
+        if protein:                                               # two queries per gene
+            queries += [s, g.protein if (i // 2) % 2 else s[20:20 + int(rng.integers(60, 120))]]
+        else:
+            m = (i // 2) % 3
+            queries += [s if m else revcomp(s), [s[200:700], synth.mutate(rng, s, 0.05, 0.005), revcomp(s)[100:800]][m]]
+    return chroms, queries
+
+
 def main():
     env = dict(os.environ, ALN_TAB=os.path.join(REF, "table"))
     only = sys.argv[1:]
     for name, fmt_opts, n_genes, seed in (("blk_k1", [], 42, 900), ("blk_k3", ["-XC5"], 28, 950), ("blk_par", [], 24, 980),
-                                          ("blk_p1", [], 30, 1200)):
+                                          ("blk_p1", [], 30, 1200), ("blk_iupac", [], 20, 1400), ("blk_iupacp", ["-Xk3"], 20, 1400)):
         if only and name not in only:
             continue
         par = name in ("blk_par", "blk_p1")
-        prot = name == "blk_p1"
-        chroms, queries = (protein_genome_and_queries if prot else paralog_genome_and_queries if par else genome_and_queries)(n_genes, 2, seed)
+        prot = name in ("blk_p1", "blk_iupacp")
+        if name.startswith("blk_iupac"):
+            chroms, queries = iupac_genome_and_queries(n_genes, 2, seed, protein=prot)
+        else:
+            chroms, queries = (protein_genome_and_queries if prot else paralog_genome_and_queries if par else genome_and_queries)(n_genes, 2, seed)
         with tempfile.TemporaryDirectory() as td:
             with open(os.path.join(td, "gnm.mfa"), "w") as f:
                 for c, s in enumerate(chroms):
@@ -159,8 +201,15 @@ def main():
             from tests import spdg
             fx = spdg.load(log)
             fx["blk_convtab"][:2] = 255
+            if name.startswith("blk_iupac"):
+                # the recorder writes IntPen(n) for n < 2^19; no region of this genome holds an intron longer than its longest
+                # chromosome, so the table is kept up to the next power of two (a smaller file; the library reads no entry beyond)
+                keep = 1 << int(max(len(c) for c in chroms)).bit_length()
+                fx["find_intpen"] = np.ascontiguousarray(np.asarray(fx["find_intpen"])[:keep])
             spdg.save(os.path.join(OUT, name + ".spdg"), {k: v for k, v in fx.items() if k != "prm"})
-            if prot:
+            if name.startswith("blk_iupac"):
+                pass                                              # (the index files of this genome are not an input of any test)
+            elif prot:
                 shutil.copyfile(os.path.join(td, "gnm.bkp"), os.path.join(OUT, name + ".bkp"))
             elif not par:
                 shutil.copyfile(os.path.join(td, "gnm.bkn"), os.path.join(OUT, name + ".bkn"))     # the reference's own index file: an input of the reader's test

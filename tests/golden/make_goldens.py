@@ -164,9 +164,53 @@ def cases():
         c[f"c2_seed{k}"] = (g.window, g.query, ["-A", "0"])
     g = gene(7100, n_exons=24, mrna_len=6000, flank=1000, intron_hi=2500)
     c["c5_6kb"] = (g.window, g.query, ["-A", "0"])
+    c.update(iupac_cases())
     c.update(protein_cases())
     c.update(protein_noll3_cases())
     c.update(cip_cases())
+    return c
+
+
+IUPAC = np.frombuffer(b"MRWSYKVHDBN", dtype=np.uint8)
+
+
+def with_iupac(seq, seed, share, at=()):
+    """a copy of the ASCII sequence with the given share of its positions, and the positions `at`, overwritten by letters drawn
+    from M R W S Y K V H D B N"""
+    rng = np.random.default_rng(synth.SEED + 8800 + seed)
+    s = np.array(seq, dtype=np.uint8)
+    hit = rng.random(s.size) < share
+    hit[[int(x) for x in at if 0 <= x < s.size]] = True
+    s[hit] = IUPAC[rng.integers(0, IUPAC.size, size=int(hit.sum()))]
+    return s
+
+
+def near_junctions(exons):
+    """one position within +-3 of every splice site, the offset moving from site to site (the two bases of the site included)"""
+    at = []
+    for i, (lo, hi) in enumerate(exons):
+        if i + 1 < len(exons):
+            at.append(hi + (-3, -1, 0, 1, 2)[i % 5])              # donor: hi, hi + 1 are its GT
+        if i > 0:
+            at.append(lo + (2, 0, -1, -2, -3)[i % 5])             # acceptor: lo - 2, lo - 1 are its AG
+    return at
+
+
+def iupac_cases():
+    """IUPAC ambiguity letters (all eleven, not N alone) in window and query: the nucleotide matrix's rows and columns 4 .. 15, the
+    signal models' reduced alphabets (red_strict, the pattern scan's counter of unknowns), canonical-site classes next to an
+    ambiguous base, and -- o3_iupac_minus -- Seq::comrev's full complement (M <-> K, R <-> Y, H <-> D, V <-> B)"""
+    c = {}
+    g = gene(71, n_exons=5, mrna_len=600, flank=300, intron_hi=1500)
+    wl, ql = with_iupac(g.window, 1, 0.015, near_junctions(g.exons)), with_iupac(g.query, 2, 0.015)
+    wh, qh = with_iupac(g.window, 3, 0.08, near_junctions(g.exons)), with_iupac(g.query, 4, 0.08)
+    c["s1_iupac_light"] = (wl, ql, ["-u", "1,2,3,5"])
+    c["s1_iupac_heavy"] = (wh, qh, ["-u", "1,2,3,5"])
+    c["c2_iupac"] = (wl, ql, ["-A", "0"])                       # (the -A0 engines' fixtures are the c2_ ones: no _wip records in them)
+    c["s1_iupac_local"] = (wh, qh, ["-L", "-u", "1,2"])
+    g = gene(72, n_exons=5, mrna_len=700, flank=300, intron_hi=900)
+    w, q = with_iupac(g.window, 5, 0.015, near_junctions(g.exons)), with_iupac(g.query, 6, 0.015)
+    c["o3_iupac_minus"] = (revcomp(w), revcomp(q), ["-O"])
     return c
 
 
@@ -185,7 +229,7 @@ def cip_cases():
 
 def revcomp(ascii_seq):
     comp = np.zeros(256, dtype=np.uint8)
-    for x, y in zip(b"ACGTNacgtn", b"TGCANtgcan"):
+    for x, y in zip(b"ACGTMRWSYKVHDBNacgtmrwsykvhdbn", b"TGCAKYWSRMBDHVNtgcakywsrmbdhvn"):     # complcod, src/seq.cc:74
         comp[x] = y
     return comp[np.asarray(ascii_seq, dtype=np.uint8)][::-1].copy()
 
@@ -264,6 +308,19 @@ def protein_cases():
             if i > 0 and (i + k) % 2 == 1:
                 w[lo + 1] = ord("N")
         c[f"h1_amb_junction{k}"] = (w, g.query, ["-u", "1,2"])
+    # IUPAC letters in the window: Seq::nuc2tron's three branches (middle base ambiguous: AMB; first base ambiguous: the likely
+    # residue of the middle one; third base ambiguous: its first element) inside exons at every codon position, plus a scatter over
+    # introns and flanks; and a query with unknown residues (X)
+    g = pgene(45, n_exons=4, aa_len=200, flank=200, intron_hi=500, sub=0.05)
+    at = []
+    for i, (lo, hi) in enumerate(g.exons):
+        at += [lo + 9 + 3 * i, lo + 19 + 3 * i, lo + 29 + 3 * i, hi - 8]       # (exon lengths are no multiple of 3: the positions fall on all three codon positions)
+    assert len({(x - g.exons[0][0]) % 3 for x in at}) == 3
+    c["h1_iupac"] = (with_iupac(g.window, 7, 0.01, at), g.query, ["-u", "1,2,3"])
+    g = pgene(46, n_exons=3, aa_len=150, flank=200, intron_hi=500, sub=0.05)
+    q = g.query.copy()
+    q[[7, 8, 40, 77, 78, 79, 120, len(q) - 1]] = ord("X")
+    c["h1_query_x"] = (g.window, q, ["-u", "1,2"])
     return c
 
 

@@ -17,10 +17,14 @@ from tests.conftest import golden_files
 from oracle import blk, oracle
 from tests.golden import make_blk_goldens as mb
 
-CASES = [("blk_k1", 42, 900, False), ("blk_k3", 28, 950, False), ("blk_par", 24, 980, True)]      # nucleotide queries (also the index builder's and the map + align tests' cases)
-PROTEIN_CASES = [("blk_p1", 30, 1200, True)]                                                      # protein queries, the translated index (-KP)
+# nucleotide queries (also the index builder's and the map + align tests' cases); blk_iupac: IUPAC letters inside the genes of the reverse strand
+CASES = [("blk_k1", 42, 900, False), ("blk_k3", 28, 950, False), ("blk_par", 24, 980, True), ("blk_iupac", 20, 1400, False)]
+# protein queries, the translated index (-KP); blk_iupacp: the genome of blk_iupac
+PROTEIN_CASES = [("blk_p1", 30, 1200, True), ("blk_iupacp", 20, 1400, False)]
+PROTEIN_NAMES = tuple(c[0] for c in PROTEIN_CASES)
+# the reference's nucleotide codes (src/cmn.h): 1 + the set of bases a letter stands for, A = 1, C = 2, G = 4, T = 8; N = 16
 CODE_OF = np.zeros(256, dtype=np.uint8)
-for _ch, _code in zip(b"ACGTN", (2, 3, 5, 9, 16)):
+for _ch, _code in zip(b"ACMGRSVTWYHKDBN", range(2, 17)):
     CODE_OF[_ch] = _code
 
 
@@ -51,7 +55,10 @@ def parse_find(L):
 
 
 def genome_of(name, n_genes, seed, par):
-    chroms, _ = (mb.protein_genome_and_queries if name == "blk_p1" else mb.paralog_genome_and_queries if par else mb.genome_and_queries)(n_genes, 2, seed)
+    if name.startswith("blk_iupac"):
+        chroms, _ = mb.iupac_genome_and_queries(n_genes, 2, seed)
+    else:
+        chroms, _ = (mb.protein_genome_and_queries if name == "blk_p1" else mb.paralog_genome_and_queries if par else mb.genome_and_queries)(n_genes, 2, seed)
     gen = np.concatenate([CODE_OF[c] for c in chroms]).astype(np.uint8)
     off = np.array([0] + list(np.cumsum([len(c) for c in chroms])), dtype=np.int64)
     return gen, off

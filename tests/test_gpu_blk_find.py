@@ -9,7 +9,7 @@ from spaln_amd import abi, blocks, defaults
 from tests import spdg
 from tests.conftest import golden_files
 from oracle import blk
-from tests.test_blk_find import CASES, PROTEIN_CASES, genome_of, parse_find
+from tests.test_blk_find import CASES, PROTEIN_CASES, PROTEIN_NAMES, genome_of, parse_find
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +67,7 @@ def test_random_queries_device_path_equals_host_path(eng, name, n_genes, seed, p
     v = [int(x) for x in fx["find_prm"]]
     sc = defaults.scoring(intpen=np.ascontiguousarray(fx["find_intpen"], dtype=np.int16))
     sc.gop, sc.gep, sc.lgop, sc.lgep, sc.codonk1 = v[13], v[14], v[15], v[16], v[17]
-    protein = name == "blk_p1"
+    protein = name in PROTEIN_NAMES
     letters = np.array(list(range(3, 23)) + [2] if protein else [2, 3, 5, 9, 16], dtype=np.uint8)
     rng = np.random.default_rng(4242)
     pool = [q["codes"] for q in blk.parse_log(fx)]

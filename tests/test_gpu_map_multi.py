@@ -20,8 +20,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
 import make_blk_goldens as mb  # noqa: E402
 
-CODE_OF = np.zeros(256, dtype=np.uint8)
-for _ch, _code in zip(b"ACGTN", (2, 3, 5, 9, 16)):
+CODE_OF = np.zeros(256, dtype=np.uint8)                  # 1 + the set of bases a letter stands for (A = 1, C = 2, G = 4, T = 8); N = 16
+for _ch, _code in zip(b"ACMGRSVTWYHKDBN", range(2, 17)):
     CODE_OF[_ch] = _code
 
 
