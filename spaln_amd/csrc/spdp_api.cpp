@@ -307,7 +307,7 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
     ctx = c; sc = *scp; n_parents = n;
     (void) hipSetDevice(ctx->device);
     // double affine gaps (Noll = 3, -yl3): forwardS_ng / hirschbergS_ng / scorealoneS_ng (the -A0 engines, spdp_rowwave<., ., ., DAGP>,
-    // spdp_rowwave_udh<., DAGP>); the -A1 / -A2 / -A3 engines and the seeded walk's cut range refuse it (DevRun::prepare)
+    // spdp_rowwave_udh<., DAGP>); the -A1 / -A2 / -A3 engines and the seeded walk's cut range refuse it (DevRun::check)
     if (sc.noll != 2 && !(sc.noll == 3 && (sc.scalar_engines == 1 || sc.scalar_engines == 2))) {
         ctx->err = "double affine gaps (Noll = 3) are built for the -A0 and -A1 engines (SpdpScoring.scalar_engines = 1 / 2); Noll must be 2 or 3";
         return -1;
@@ -439,31 +439,23 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
 }
 
 // ---- one sweep over a list of items ---------------------------------------------------
-static int stripe_blocks(const DevProblem& P, int s, bool forward)
+// the 16-column blocks of traceback codes that stripe s of a forward sweep writes
+static int stripe_blocks(const RunItem& it, int s)
 {
-    const int ml = P.a_left + s * SPDP_NELEM;
-    const int j9 = std::min(SPDP_NELEM, P.a_right - ml);
-    const int n_start = std::max(P.b_left, P.lw + ml);
-    const int n9 = std::min(P.b_right, P.up + (ml + j9) + 1) + j9;
-    const int len = std::max(0, n9 + (forward ? 1 : 0) - n_start);
-    return (len + 15) >> 4;
+    const int ml = it.a_left + s * SPDP_NELEM, j9 = std::min(SPDP_NELEM, it.a_right - ml);
+    const int n_start = std::max(it.b_left, it.w.lw + ml);
+    const int n9 = std::min(it.b_right, it.w.up + (ml + j9) + 1) + j9;
+    return (std::max(0, n9 + 1 - n_start) + 15) >> 4;
 }
+static int stripes_of(const DevProblem& P) { return (P.a_right - P.a_left + SPDP_NELEM - 1) / SPDP_NELEM; }
 
-// buffers belong to ctx->pool[..]; a run abandoned in flight (an error elsewhere in the batch) is waited for so
+// buffers belong to pool(); a run abandoned in flight (an error elsewhere in the batch) is waited for so
 // that its pool can be reused
 void DevRun::release() { if (in_flight && ctx) { (void) hipStreamSynchronize(strm()); in_flight = false; } }
 
-#define POOL_OF_RUN ctx->pool[side ? 8 : (flav == 7 ? 3 : (flav >= 5 ? 4 : flav))]
-#define POOLGET(dst, slot, bytes)                                                        \
-    do {                                                                                 \
-        (dst) = POOL_OF_RUN.get((slot), (size_t) (bytes));                                \
-        if (!(dst)) { ctx->err = "out of device memory"; return -1; }                    \
-    } while (0)
+#define POOLGET(dst, slot, bytes) do { if (!((dst) = take((slot), (size_t) (bytes)))) return -1; } while (0)
+void* DevRun::take(int slot, size_t bytes) { void* p = pool().get(slot, bytes); if (!p) ctx->err = "out of device memory"; return p; }
 
-// Vmf record budget of one forwardS_ng / forwardS1 call.  A record is written where a diagonal run starts and twice per
-// accepted intron: on real alignments a few per row.  The budget is one record per two band cells (the band, not the
-// bounding rectangle), at least 64 per row; a call that outgrows it reports so (n_skl = -3) and is run again with
-// vmf_scale x 8 by the ladder -- the old "two per cell of the rectangle" made batches of slabs run in dozens of groups.
 bool spdp_intpen_runs(const int16_t* intpen, int len, int16_t* out)
 {
     if (len <= SPDP_IPR_BASE) {                         // nothing beyond the LDS table: one run
@@ -497,36 +489,73 @@ bool spdp_intpen_runs(const int16_t* intpen, int len, int16_t* out)
     return true;
 }
 
-static int64_t vmf_capacity(const RunItem& it)
+// Vmf record budget of one forwardS_ng / forwardS1 call.  A record is written where a diagonal run starts and twice per
+// accepted intron: on real alignments a few per row.  The budget is one record per two band cells (the band, not the
+// bounding rectangle), at least 64 per row; a call that outgrows it reports so (n_skl = -3) and is run again with
+// vmf_scale x 8 by the ladder -- the old "two per cell of the rectangle" made batches of slabs run in dozens of groups.
+int64_t vmf_capacity(int64_t rows, int64_t cols, int64_t width, int64_t scale)
 {
-    const int64_t rows = it.a_right - it.a_left + 1, cols = it.b_right - it.b_left + 1;
-    const int64_t band = rows * std::min<int64_t>(cols, (int64_t) it.w.width);
+    const int64_t band = rows * std::min(cols, width);
     const int64_t full = 2 * rows * cols + 64;
-    return std::min(full, std::max(band / 2, 64 * rows) * (int64_t) it.vmf_scale + 64);
+    return std::min(full, std::max(band / 2, 64 * rows) * scale + 64);
 }
 
-int DevRun::build(const DevStore* st, const std::vector<RunItem>& items, int flav)
+// what the engine cannot run at all (the callers and the tests know these messages)
+int DevRun::check()
 {
-    store = st; ctx = use_ctx ? use_ctx : st->ctx; flavour = flav; n = (int) items.size();
-    cut = false;
-    (void) hipSetDevice(ctx->device);
-    if (flav >= 3 && !st->has_exact) {
+    const RunTraits& T = traits();
+    if (T.family != FAM_WIP && !store->has_exact) {
         ctx->err = "scalar exact engine needs intpen / t53 in SpdpScoring and cano5 / cano3 / dinc per problem";
         return -1;
     }
-    if (st->sc.noll == 3 && !(flav >= 3 && flav <= 7)) {
+    if (store->sc.noll == 3 && !(T.family == FAM_A0 || (T.family == FAM_A1 && T.kind != KIND_UDH))) {
         // (-A1: scoreonlyS1 / forwardS1 since round 5; the reference's own hirschbergS1 is not usable under -yl3 -- it never lets
         //  the second vertical gap reach H across an intermediate row -- so there is no result to be identical with)
-        ctx->err = flav == 8 ? "double affine gaps (Noll = 3) under -A1: the linear-space engine (hirschbergS1) is undefined in the reference; "
-                               "raise SpdpScoring.max_vmf_space so that the traceback branch is taken"
-                             : "double affine gaps (Noll = 3): only the -A0 and -A1 engines are built";
+        ctx->err = flavour == RUN_A1_UDH ? "double affine gaps (Noll = 3) under -A1: the linear-space engine (hirschbergS1) is undefined in the reference; "
+                                        "raise SpdpScoring.max_vmf_space so that the traceback branch is taken"
+                                      : "double affine gaps (Noll = 3): only the -A0 and -A1 engines are built";
         return -1;
     }
-    // hirschbergS1_wip with local ends (-LS): its own kernel (spdp_local_udh.hip), flavour 9
-    if (flav == 2 && st->sc.local) flav = flavour = 9;
+    return 0;
+}
+
+// one item's share of the three work buffers: ints (x RunTraits::bw) of bnd, traceback bytes or Vmf records of tb, ints of imd
+struct ItemShare { int64_t work, tb, imd; };
+static ItemShare item_share(const RunTraits& T, const RunItem& it, int noll)
+{
+    const int64_t width = it.w.width, buf = width + 2 * SPDP_NELEM, rows = it.a_right - it.a_left;
+    const int64_t n_im = T.rows() ? it.n_im : 0;
+    const int64_t cap = T.vmf ? vmf_capacity(rows + 1, it.b_right - it.b_left + 1, width, it.vmf_scale) : 0;
+    switch (T.family) {
+    case FAM_WIP: {                 // the boundary of one stripe; forward: a 256-byte block of codes per 16 columns of a stripe
+        int64_t tb = 0;
+        if (T.kind == KIND_FORWARD)
+            for (int s = 0; s < (rows + SPDP_NELEM - 1) / SPDP_NELEM; ++s) tb += 256ll * stripe_blocks(it, s);
+        return {buf + SPDP_BND_PAD, tb, n_im * 4 * width};
+    }
+    case FAM_A0:
+        // linear space: Noll * width + 4 states of 5 ints (H and Noll - 1 vertical-gap states); 4 * Noll link / bound rows per intermediate
+        if (T.kind == KIND_UDH) return {5 * (noll * width + 4), 0, n_im * 4 * noll * width};
+        // H, F (values, Vmf pointers) and the direction entries by diagonal (+ F2 with Noll = 3); Vmf records
+        // (+ what the waves of a pipelined problem may leave unused of the chunks of numbers they reserve)
+        return {(noll == 3 ? 7 : 5) * width + 8, T.vmf ? cap + (int64_t) SPDP_VMF_CHUNK * (rows / 64 + 2) : 0, 0};
+    default:
+        // -A1 and local udh: hv / fv (/ hb / hc / fc) by diagonal, buf ints each, a counter; udh forms: + the `ml` row of F;
+        // Noll = 3: + fv2, fc2 behind the counter
+        // (Vmf: + what the lanes may leave unused of the chunks of numbers they reserve, per stripe when pipelined)
+        return {(T.kind == KIND_UDH ? 6 : (noll == 3 ? 8 : 5)) * buf + 8,
+                T.vmf ? cap + (int64_t) 2 * SPDP_VMF_LANE_CHUNK * SPDP_NELEM * (rows / SPDP_NELEM + 2) : 0, n_im * 4 * width};
+    }
+}
+
+// validates the items and fills h_probs (caller order); tot: the buffers' totals in the units of ItemShare
+int DevRun::lay_out(const std::vector<RunItem>& items, ItemShare& tot)
+{
+    const DevStore* st = store;
+    const RunTraits& T = traits();
     h_probs.assign(n, DevProblem());
-    int64_t bnd_tot = 0, tb_tot = 0, imd_tot = 0;
-    total_cells = 0; max_n_im = 0; max_skl = 0;
+    tot = {0, 0, 0};
+    cut = false; total_cells = 0; max_n_im = 0; max_skl = 0;
     for (int i = 0; i < n; ++i) {
         const RunItem& it = items[i];
         DevProblem& P = h_probs[i];
@@ -539,101 +568,76 @@ int DevRun::build(const DevStore* st, const std::vector<RunItem>& items, int fla
         P.lw = it.w.lw; P.up = it.w.up; P.width = it.w.width;
         P.cut_l = P.cut_len = 0;
         if (it.cut_r > it.cut_l) {              // forwardS_ng over a cut range: its arrays are narrower by the cut (src/fwd2s1.cc:234)
-            if (flav != 3 || it.a_exgl || it.w.width - (it.cut_r - it.cut_l) < 3 || it.cut_l < it.b_left || it.cut_r > it.b_right ||
-                (i > 0 && !cut)) { ctx->err = "bad cut range"; return -1; }
+            if (flavour != RUN_A0_FORWARD || it.a_exgl || it.w.width - (it.cut_r - it.cut_l) < 3 || it.cut_l < it.b_left ||
+                it.cut_r > it.b_right || (i > 0 && !cut)) { ctx->err = "bad cut range"; return -1; }
             cut = true;
             P.cut_l = it.cut_l; P.cut_len = it.cut_r - it.cut_l;
             P.width = it.w.width - P.cut_len;
         } else if (cut) { ctx->err = "bad cut range"; return -1; }
         P.buf_size = it.w.width + 2 * SPDP_NELEM;
         P.flags = (it.a_exgl ? 1 : 0) | (it.a_exgr ? 2 : 0) | (it.b_exgl ? 4 : 0) | (it.b_exgr ? 8 : 0);
-        P.n_im = (flav == 2 || flav == 5 || flav == 8 || flav == 9) ? it.n_im : 0;
+        P.n_im = T.rows() ? it.n_im : 0;
         P.imd_intvl = it.imd_intvl;
-        P.a_off = st->a_off[it.parent];
-        P.col_off = st->col_off[it.parent];
+        P.a_off = st->a_off[it.parent]; P.col_off = st->col_off[it.parent];
         P.cip_off = st->cip_off.empty() ? -1 : st->cip_off[it.parent];
-        P.bnd_off = bnd_tot; bnd_tot += (int64_t) P.buf_size + SPDP_BND_PAD;
-        P.tb_off = tb_tot;
-        if (flav >= 6) {                // -A1 engines: hv / fv (/ hb / hc / fc) by diagonal, buf_size ints each, a counter
-            P.bnd_off = bnd_tot - ((int64_t) P.buf_size + SPDP_BND_PAD);
-            bnd_tot = P.bnd_off + (flav >= 8 ? 6ll : (st->sc.noll == 3 ? 8ll : 5ll)) * P.buf_size + 8;   // udh forms: + the `ml` row of F; Noll = 3: + fv2, fc2 behind the counter
-            if (flav >= 8) { P.imd_off = imd_tot; imd_tot += (int64_t) it.n_im * 4 * it.w.width; }
-            if (flav == 7) {
-                // (+ what the lanes may leave unused of the chunks of numbers they reserve, per stripe when pipelined)
-                const int64_t cap = vmf_capacity(it)
-                                    + (int64_t) 2 * SPDP_VMF_LANE_CHUNK * SPDP_NELEM * ((it.a_right - it.a_left) / SPDP_NELEM + 2);
-                P.imd_off = cap;
-                tb_tot += cap;
-            }
-        } else if (flav == 5) { // scalar UDH: Noll * width + 4 states of 5 ints; 4 * Noll link / bound rows per intermediate
-            P.bnd_off = bnd_tot - ((int64_t) P.buf_size + SPDP_BND_PAD);
-            bnd_tot = P.bnd_off + 5ll * (st->sc.noll * it.w.width + 4);                  // H and Noll - 1 vertical-gap states
-            P.imd_off = imd_tot;
-            imd_tot += (int64_t) P.n_im * 4 * st->sc.noll * it.w.width;
-        } else if (flav >= 3) { // scalar: work = 4 * width ints + width dir bytes; Vmf records
-            P.bnd_off = bnd_tot - ((int64_t) P.buf_size + SPDP_BND_PAD);
-            bnd_tot = P.bnd_off + (st->sc.noll == 3 ? 7ll : 5ll) * it.w.width + 8;        // H, F (values, Vmf pointers) and the direction entries by diagonal (+ F2 with Noll = 3)
-            // (+ what the waves of a pipelined problem may leave unused of the chunks of numbers they reserve)
-            const int64_t cap = (flav == 3) ? vmf_capacity(it) + (int64_t) SPDP_VMF_CHUNK * ((it.a_right - it.a_left) / 64 + 2) : 0;
-            P.imd_off = cap;
-            tb_tot += cap;
-        }
-        if (flav == 1) {
-            const int ns = (it.a_right - it.a_left + SPDP_NELEM - 1) / SPDP_NELEM;
-            for (int s = 0; s < ns; ++s) tb_tot += 256ll * stripe_blocks(P, s, true);
-        }
-        if (flav < 3) { P.imd_off = imd_tot; imd_tot += (int64_t) P.n_im * 4 * it.w.width; }
+        const ItemShare sh = item_share(T, it, st->sc.noll);
+        P.bnd_off = tot.work; P.tb_off = tot.tb;
+        P.imd_off = T.vmf ? sh.tb : tot.imd;    // (ScalarArgs::probs: a Vmf-backed problem's record budget goes here)
+        tot.work += sh.work; tot.tb += sh.tb; tot.imd += sh.imd;
         P.cells = spdp_cells_w(it.a_left, it.a_right, it.b_left, it.b_right, it.w);
         total_cells += P.cells;
         max_n_im = std::max(max_n_im, P.n_im);
         max_skl = std::max(max_skl, (it.a_right - it.a_left) + (it.b_right - it.b_left) + 8);
     }
-    tb_bytes = tb_tot;
-    // fp32 sweeps: every score must stay an exactly representable integer below 2^22 - 2^16 (the penalty table
-    // pushes a candidate down by 2^22 to disable it).  Upper bound of a score: matches on every row, plus
-    // whatever an intron can gain where the signals outweigh its penalties (never, with real parameters).
-    {
-        int64_t rows = 0, cols_span = 0;
-        for (int i = 0; i < n; ++i) {
-            rows = std::max<int64_t>(rows, items[i].a_right - items[i].a_left);
-            cols_span = std::max<int64_t>(cols_span, items[i].b_right - items[i].b_left);
-        }
-        const char* e = getenv("SPDP_FP");
-        const int64_t ub = (rows + 1) * st->fp_maxpos + (st->fp_gain > 0 ? (cols_span + 1) * st->fp_gain : 0) + 65536;
-        fp_ok = (!e || atoi(e) != 0) && ub < (1ll << 22) - 65536;
+    tb_bytes = tot.tb;
+    return 0;
+}
+
+// fp32 sweeps: every score must stay an exactly representable integer below 2^22 - 2^16 (the penalty table
+// pushes a candidate down by 2^22 to disable it).  Upper bound of a score: matches on every row, plus
+// whatever an intron can gain where the signals outweigh its penalties (never, with real parameters).
+static bool fp_range_ok(const DevStore* st, const std::vector<RunItem>& items)
+{
+    int64_t rows = 0, cols_span = 0;
+    for (const RunItem& it : items) {
+        rows = std::max<int64_t>(rows, it.a_right - it.a_left);
+        cols_span = std::max<int64_t>(cols_span, it.b_right - it.b_left);
     }
-    const int bw = (flav == 2) ? 4 : (flav >= 3 ? 1 : 2);
+    const int64_t ub = (rows + 1) * st->fp_maxpos + (st->fp_gain > 0 ? (cols_span + 1) * st->fp_gain : 0) + 65536;
+    return spdp_knob_on("SPDP_FP") && ub < (1ll << 22) - 65536;
+}
+
+int DevRun::allocate(const ItemShare& tot)
+{
+    const RunTraits& T = traits();
     const int nn = std::max(n, 1);
     skl_cap = std::min(std::max(max_skl, 1), 1024);     // typical lists are short; DevRun::fetch_skl walks the rest again
     if (const char* e = getenv("SPDP_SKL_CAP")) skl_cap = std::max(4, std::min(skl_cap, atoi(e)));   // test hook: tiny slots
     POOLGET(d_probs, POOL_PROBS, sizeof(DevProblem) * nn);
-    POOLGET(d_bnd, POOL_BND, sizeof(int32_t) * bw * std::max<int64_t>(bnd_tot, 1));
+    POOLGET(d_bnd, POOL_BND, sizeof(int32_t) * T.bw * std::max<int64_t>(tot.work, 1));
     POOLGET(d_res, POOL_RES, sizeof(DevResult) * nn);
-    if (flav == 3 || flav == 7) {
-        POOLGET(d_tb, POOL_TB, sizeof(int3) * std::max<int64_t>(tb_tot, 16));
+    if (T.records()) {
+        POOLGET(d_tb, POOL_TB, (T.vmf ? sizeof(int3) : 1) * std::max<int64_t>(tot.tb, 16));
         POOLGET(d_skl, POOL_SKL, sizeof(int2) * (int64_t) skl_cap * nn);
         POOLGET(d_nskl, POOL_NSKL, sizeof(int) * nn);
     }
-    if (flav == 1) {
-        POOLGET(d_tb, POOL_TB, std::max<int64_t>(tb_tot, 16));
-        POOLGET(d_skl, POOL_SKL, sizeof(int2) * (int64_t) skl_cap * nn);
-        POOLGET(d_nskl, POOL_NSKL, sizeof(int) * nn);
-    }
-    if (flav == 2 || flav == 5 || flav == 8 || flav == 9) {
-        POOLGET(d_imd, POOL_IMD, sizeof(int32_t) * std::max<int64_t>(imd_tot, 1));
-        POOLGET(d_cpos, POOL_CPOS, sizeof(int32_t) * 10 * (max_n_im + 1) * nn);
+    if (T.rows()) {
+        POOLGET(d_imd, POOL_IMD, sizeof(int32_t) * std::max<int64_t>(tot.imd, 1));
+        POOLGET(d_cpos, POOL_CPOS, sizeof(int32_t) * cpos_stride() * nn);
         POOLGET(d_ranges, POOL_RANGES, sizeof(int32_t) * 4 * nn);
         POOLGET(d_scores, POOL_SCORES, sizeof(int32_t) * 2 * nn);          // scores, then the left-edge marks of spdp_udh_cpos
     }
-    // dispatch order = largest problems first (longest-processing-time rule): one wave owns one
-    // problem, so the big ones must not start last.  order[j] = caller index of dispatch slot j.
+    return 0;
+}
+
+// dispatch order = largest problems first (longest-processing-time rule): one wave owns one
+// problem, so the big ones must not start last.  order[j] = caller index of dispatch slot j.
+// Problems that can be spread over a block's waves (>= 16 stripes) come first, see plan_blocks.
+void DevRun::sort_dispatch(bool may_multi)
+{
     order.resize(n);
     for (int i = 0; i < n; ++i) order[i] = i;
-    // Problems that can be spread over a block's waves (>= 16 stripes) come first, see below.
-    const bool may_multi = flav <= 2 && !st->sc.local;
-    auto wide = [&](int x) {
-        return may_multi && (h_probs[x].a_right - h_probs[x].a_left + SPDP_NELEM - 1) / SPDP_NELEM >= 16;
-    };
+    auto wide = [&](int x) { return may_multi && stripes_of(h_probs[x]) >= 16; };
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
         const bool wx = wide(x), wy = wide(y);
         return wx != wy ? wx : h_probs[x].cells > h_probs[y].cells;
@@ -641,121 +645,156 @@ int DevRun::build(const DevStore* st, const std::vector<RunItem>& items, int fla
     std::vector<DevProblem> sorted(n);
     for (int j = 0; j < n; ++j) sorted[j] = h_probs[order[j]];
     h_probs.swap(sorted);
-    // Big problems (>= 16 stripes = 4 passes) are spread over the 4 waves of a block (pipelined passes).
-    // That pays in full launches too: the longest problem bounds the launch, and the passes of one
-    // problem running a few blocks apart share their column records in L2.  (Measured on C2, 10000
-    // queries: 540 -> 652 GCUPS end to end.)  SPDP_MULTI=0 restores one wave per problem.
-    n_multi = 0; wpb = 4;
-    if (may_multi) {
-        const char* force = getenv("SPDP_MULTI");
-        if (!force || atoi(force) != 0)
-            for (int j = 0; j < n; ++j) {
-                const int stripes = (h_probs[j].a_right - h_probs[j].a_left + SPDP_NELEM - 1) / SPDP_NELEM;
-                if (stripes >= 16) n_multi = j + 1; else break;          // sorted: a prefix
-            }
-        // a launch of a few huge problems only (top levels of the recursion on a long cDNA): one
-        // 16-wave block, i.e. a whole CU, per problem
-        const char* w16 = getenv("SPDP_WPB16");
-        if (w16) { if (atoi(w16) != 0) wpb = 16; }
-        else if (n_multi == n && n <= 2 * ctx->n_cu) {
-            const int smallest = (h_probs[n - 1].a_right - h_probs[n - 1].a_left + SPDP_NELEM - 1) / SPDP_NELEM;
-            if (smallest >= 4 * 32) wpb = 16;                            // >= 32 passes each
-            // a handful of mid-sized problems (the stragglers of an EST batch that need the linear-space
-            // engine): the launch is latency-bound, more passes in flight shorten it
-            else if (!beside && n <= ctx->n_cu / 2 && smallest > 4 * 4) wpb = 16;
+}
+
+// Big problems (>= 16 stripes = 4 passes) are spread over the 4 waves of a block (pipelined passes).
+// That pays in full launches too: the longest problem bounds the launch, and the passes of one
+// problem running a few blocks apart share their column records in L2.  (Measured on C2, 10000
+// queries: 540 -> 652 GCUPS end to end.)  SPDP_MULTI=0 restores one wave per problem.
+int DevRun::plan_blocks(bool may_multi)
+{
+    const SpdpScoring& sc = store->sc;
+    n_multi = 0; wpb = 4; cross_g = 0;
+    if (!may_multi) return 0;
+    if (spdp_knob_on("SPDP_MULTI"))
+        while (n_multi < n && stripes_of(h_probs[n_multi]) >= 16) ++n_multi;           // sorted: a prefix
+    // a launch of a few huge problems only (top levels of the recursion on a long cDNA): one
+    // 16-wave block, i.e. a whole CU, per problem
+    if (const char* w16 = getenv("SPDP_WPB16")) { if (atoi(w16) != 0) wpb = 16; }
+    else if (n > 0 && n_multi == n && n <= 2 * ctx->n_cu) {
+        const int smallest = stripes_of(h_probs[n - 1]);
+        if (smallest >= 4 * 32) wpb = 16;                            // >= 32 passes each
+        // a handful of mid-sized problems (the stragglers of an EST batch that need the linear-space
+        // engine): the launch is latency-bound, more passes in flight shorten it
+        else if (!beside && n <= ctx->n_cu / 2 && smallest > 4 * 4) wpb = 16;
+    }
+    // fewer huge problems than a quarter of the CUs (the top levels of the recursion on one long cDNA): each spread over
+    // several CUs -- cross-CU pass pipelines, all blocks resident.  For the linear-space sweep, and for the traceback sweep
+    // where spdp_sweep_fp serves it (the tall slabs a long cDNA's recursion leaves, spdp_host.cpp)
+    const char* cg = getenv("SPDP_CROSS");
+    bool crossable = flavour == RUN_WIP_UDH;
+    if (flavour == RUN_WIP_FORWARD && fp_ok && spdp_knob_on("SPDP_FP_FWD")) {
+        const int nq = std::max(1, std::min(sc.nquant, SPDP_MAX_QUANT));
+        crossable = spdp_sweep_fp_serves(sc.local ? 1 : 0, sc.spj ? 1 : 0, nq, nq > 1 ? sc.qm_len[nq - 2] + 1 : 0, sc.llmt) != 0;
+    }
+    if (crossable && wpb == 16 && n_multi == n && n > 0 && (!cg || atoi(cg) != 0)) {
+        int max_passes = 0, min_passes = 1 << 30;
+        for (int j = 0; j < n; ++j) {
+            max_passes = std::max(max_passes, (stripes_of(h_probs[j]) + 3) / 4);
+            min_passes = std::min(min_passes, (stripes_of(h_probs[j]) + 3) / 4);
         }
-        // fewer huge problems than a quarter of the CUs (the top levels of the recursion on one long
-        // cDNA): spread each over several CUs -- cross-CU pass pipelines, all blocks resident
-        cross_g = 0;
-        const char* cg = getenv("SPDP_CROSS");
-        // (the traceback sweep too, where spdp_sweep_fp serves it: the tall slabs a long cDNA's recursion leaves, spdp_host.cpp)
-        bool fwd_cross = false;
-        if (flav == 1 && fp_ok && !(getenv("SPDP_FP_FWD") && atoi(getenv("SPDP_FP_FWD")) == 0)) {
-            const int nq = std::max(1, std::min(st->sc.nquant, SPDP_MAX_QUANT));
-            fwd_cross = spdp_sweep_fp_serves(st->sc.local ? 1 : 0, st->sc.spj ? 1 : 0, nq, nq > 1 ? st->sc.qm_len[nq - 2] + 1 : 0, st->sc.llmt) != 0;
-        }
-        if ((flav == 2 || fwd_cross) && wpb == 16 && n_multi == n && n > 0 && (!cg || atoi(cg) != 0)) {
-            int max_passes = 0, min_passes = 1 << 30;
-            for (int j = 0; j < n; ++j) {
-                const int stripes = (h_probs[j].a_right - h_probs[j].a_left + SPDP_NELEM - 1) / SPDP_NELEM;
-                max_passes = std::max(max_passes, (stripes + 3) / 4);
-                min_passes = std::min(min_passes, (stripes + 3) / 4);
-            }
-            const int room = ctx->n_cu / n;                              // blocks per problem, one block per CU
-            int g = std::min(room, (max_passes + 15) / 16);
-            // with CUs to spare a wave gets a SIMD to itself: 4-wave blocks, one pass per wave
-            const char* c4 = getenv("SPDP_CROSS_WPB");
-            if (c4 ? atoi(c4) == 4 : (max_passes + 3) / 4 <= room) { wpb = 4; g = std::min(room, (max_passes + 3) / 4); }
-            if (cg && atoi(cg) > 1) g = std::min(room, atoi(cg));
-            if (g >= 2 && min_passes >= 32) cross_g = g;
-            else wpb = 16;
-        }
+        const int room = ctx->n_cu / n;                              // blocks per problem, one block per CU
+        int g = std::min(room, (max_passes + 15) / 16);
+        // with CUs to spare a wave gets a SIMD to itself: 4-wave blocks, one pass per wave
+        const char* c4 = getenv("SPDP_CROSS_WPB");
+        if (c4 ? atoi(c4) == 4 : (max_passes + 3) / 4 <= room) { wpb = 4; g = std::min(room, (max_passes + 3) / 4); }
+        if (cg && atoi(cg) > 1) g = std::min(room, atoi(cg));
+        if (g >= 2 && min_passes >= 32) cross_g = g;
+        else wpb = 16;
     }
     if (cross_g > 0) {
         const size_t words = (size_t) n * (cross_g * wpb + 2);
         POOLGET(d_gprog, POOL_GPROG, sizeof(int) * words);
         HIPCHK(hipMemsetAsync(d_gprog, 0, sizeof(int) * words, strm()));
     }
-    // a problem's tiles / stripes as a pipeline of waves (TilePipe; SPDP_A1_PIPE=0, SPDP_A0_PIPE=0: one wave each)
+    return 0;
+}
+
+// a problem's tiles / stripes as a pipeline of waves (TilePipe; SPDP_A1_PIPE=0, SPDP_A0_PIPE=0: one wave each)
+int DevRun::plan_pipe()
+{
+    const RunTraits& T = traits();
     pipe = TilePipe();
-    const bool a1 = flav >= 6 && flav <= 8;
-    if ((a1 || flav == 3 || flav == 4 || flav == 5) && n > 0) {
-        const char* e = getenv(a1 ? "SPDP_A1_PIPE" : "SPDP_A0_PIPE");
-        if (a1) pipe.plan_groups(h_probs, 4);           // -A1 engines: work item = (four problems, 16-row stripe), spdp_exact<., true>
-        else                                            // forwardS_ng / scorealoneS_ng: 64-row tiles; hirschbergS_ng: imd_intvl rows
-            for (int j = 0; j < n; ++j) {
-                const DevProblem& P = h_probs[j];
-                pipe.plan(j, P.a_right - (P.a_left + (P.flags & 1)), flav == 5 ? std::max(1, std::min(64, P.imd_intvl)) : 64);
-            }
-        const int mt = pipe.max_tiles;
-        const bool wanted = (!e || atoi(e) != 0) && mt >= 2 && !cut;
-        if (wanted && !pipe.reserve(POOL_OF_RUN, POOL_GPROG, n, a1 ? 2 + 7 * mt + max_n_im : (flav == 5 ? 2 + 9 * mt + max_n_im : 2 + 5 * mt))) {
-            ctx->err = "out of device memory"; return -1;
+    if (!T.pipe_tpw || n == 0) return 0;
+    if (T.family == FAM_A1) pipe.plan_groups(h_probs, 4);   // work item = (four problems, 16-row stripe), spdp_exact<., true>
+    else                                                    // forwardS_ng / scorealoneS_ng: 64-row tiles; hirschbergS_ng: imd_intvl rows
+        for (int j = 0; j < n; ++j) {
+            const DevProblem& P = h_probs[j];
+            pipe.plan(j, P.a_right - (P.a_left + (P.flags & 1)), T.kind == KIND_UDH ? std::max(1, std::min(64, P.imd_intvl)) : 64);
         }
-    }
+    const bool wanted = spdp_knob_on(T.family == FAM_A1 ? "SPDP_A1_PIPE" : "SPDP_A0_PIPE") && pipe.max_tiles >= 2 && !cut;
+    if (wanted && !pipe.reserve(pool(), POOL_GPROG, n, T.pipe_tpw, max_n_im)) { ctx->err = "out of device memory"; return -1; }
+    return 0;
+}
+
+int DevRun::build(const DevStore* st, const std::vector<RunItem>& items, RunFlavour flav)
+{
+    store = st; ctx = use_ctx ? use_ctx : st->ctx; flavour = flav; n = (int) items.size();
+    (void) hipSetDevice(ctx->device);
+    if (check()) return -1;
+    // hirschbergS1_wip with local ends (-LS): its own kernel (spdp_local_udh.hip)
+    if (flavour == RUN_WIP_UDH && st->sc.local) flavour = RUN_LOCAL_UDH;
+    const bool may_multi = traits().family == FAM_WIP && !st->sc.local;     // problems spread over the waves of a block
+    ItemShare tot;
+    if (lay_out(items, tot)) return -1;
+    fp_ok = fp_range_ok(st, items);
+    if (allocate(tot)) return -1;
+    sort_dispatch(may_multi);
+    if (plan_blocks(may_multi) || plan_pipe()) return -1;
     if (n) HIPCHK(hipMemcpyAsync(d_probs, h_probs.data(), sizeof(DevProblem) * n, hipMemcpyHostToDevice, strm()));
     return 0;
 }
 
+// the link walk (spdp_udh_cpos) behind a linear-space sweep; pipe_words: the sync words of a pipelined spdp_exact<2>, or null
+CposArgs DevRun::cpos_args(int strict, int local, const int* pipe_words) const
+{
+    CposArgs C{};
+    C.probs = (const DevProblem*) d_probs; C.n_probs = n; C.imd = (const int*) d_imd; C.res = (const DevResult*) d_res;
+    C.cpos = (int*) d_cpos; C.ranges = (int*) d_ranges; C.scores = (int*) d_scores;
+    C.cpos_stride = cpos_stride(); C.strict = strict; C.local = local;
+    C.edge = (int*) d_scores + n;
+    C.pipe = pipe_words; C.pipe_stride = pipe.stride; C.rlf_off = pipe.rlf_off;
+    return C;
+}
+
 int DevRun::launch()
 {
+    const RunTraits& T = traits();
     (void) hipSetDevice(ctx->device);
     if (n == 0) return 0;
     in_flight = true;
-    if (flavour >= 3) {
-        ScalarArgs S{};
-        HIPCHK(pipe.arm(strm(), n, S));
-        S.sc = (const DevScoring*) store->d_sc; S.probs = (const DevProblem*) d_probs; S.n_probs = n;
-        S.a_codes = (const uint8_t*) store->d_a; S.cols = (const int2*) store->d_cols;
-        S.aux = (const uint8_t*) store->d_aux; S.intpen = (const int16_t*) store->d_intpen;
-        S.ipen_runs = (const int16_t*) store->d_ipen_runs;
-        S.cip = (const int*) store->d_cip;
-        S.intpen_len = store->sc.intpen_len; S.ipen = store->sc.ipen;
-        memcpy(S.t53, store->sc.t53, sizeof S.t53);
-        S.work = (int*) d_bnd; S.vmf = (int3*) d_tb; S.res = (DevResult*) d_res;
-        S.skl = (int2*) d_skl; S.n_skl = (int*) d_nskl; S.skl_cap = skl_cap;
-        S.imd = (int*) d_imd; S.cpos = (int*) d_cpos; S.ranges = (int*) d_ranges; S.scores = (int*) d_scores;
-        S.cpos_stride = 10 * (max_n_im + 1);
-        HIPCHK(hipEventRecord(evb(), strm()));
-        S.minl = store->sc.minl ? store->sc.minl : store->sc.llmt;
-        S.noll = store->sc.noll; S.lgop = store->sc.lgop; S.lgep = store->sc.lgep; S.codonk1 = store->sc.codonk1;
-        if (flavour == 9) HIPCHK(spdp_launch_local_udh(&S, strm()));
-        else if (flavour >= 6) HIPCHK(spdp_launch_exact(flavour - 6, &S, strm()));
-        else if (flavour == 5) HIPCHK(spdp_launch_rowwave_udh(&S, strm()));
-        else HIPCHK(spdp_launch_rowwave(flavour == 3 ? (cut ? 2 : 1) : 0, &S, strm()));
-        HIPCHK(hipEventRecord(eve(), strm()));
-        if (flavour >= 8) {                 // hirschbergS1's / the local hirschbergS1_wip's link walk
-            CposArgs C{};
-            C.probs = S.probs; C.n_probs = n; C.imd = (const int*) d_imd; C.res = (const DevResult*) d_res;
-            C.cpos = (int*) d_cpos; C.ranges = (int*) d_ranges; C.scores = (int*) d_scores;
-            C.cpos_stride = 10 * (max_n_im + 1); C.strict = flavour == 8; C.local = store->sc.local ? 1 : 0;
-            C.edge = (int*) d_scores + n;
-            C.pipe = (flavour == 8 && pipe.on) ? pipe.d : nullptr;
-            C.pipe_stride = pipe.stride; C.rlf_off = 2 + 7 * pipe.max_tiles;
-            HIPCHK(spdp_launch_cpos(&C, strm()));
-        }
-        return 0;
+    if (T.launcher == BY_SWEEP ? launch_sweep() : launch_scalar()) return -1;
+    if (T.edge) {                           // hirschbergS1_wip's / hirschbergS1's / the local hirschbergS1_wip's link walk
+        const bool a1 = T.family == FAM_A1;
+        const CposArgs C = cpos_args(a1, store->sc.local ? 1 : 0, a1 && pipe.on ? pipe.d : nullptr);
+        HIPCHK(spdp_launch_cpos(&C, strm()));
     }
+    return 0;
+}
+
+// the -A0, -A1 and local engines
+int DevRun::launch_scalar()
+{
+    const RunTraits& T = traits();
+    ScalarArgs S{};
+    HIPCHK(pipe.arm(strm(), n, S));
+    S.sc = (const DevScoring*) store->d_sc; S.probs = (const DevProblem*) d_probs; S.n_probs = n;
+    S.a_codes = (const uint8_t*) store->d_a; S.cols = (const int2*) store->d_cols;
+    S.aux = (const uint8_t*) store->d_aux; S.intpen = (const int16_t*) store->d_intpen;
+    S.ipen_runs = (const int16_t*) store->d_ipen_runs; S.cip = (const int*) store->d_cip;
+    S.intpen_len = store->sc.intpen_len; S.ipen = store->sc.ipen;
+    memcpy(S.t53, store->sc.t53, sizeof S.t53);
+    S.work = (int*) d_bnd; S.vmf = (int3*) d_tb; S.res = (DevResult*) d_res;
+    S.skl = (int2*) d_skl; S.n_skl = (int*) d_nskl; S.skl_cap = skl_cap;
+    S.imd = (int*) d_imd; S.cpos = (int*) d_cpos; S.ranges = (int*) d_ranges; S.scores = (int*) d_scores;
+    S.cpos_stride = cpos_stride();
+    HIPCHK(hipEventRecord(evb(), strm()));
+    S.minl = store->sc.minl ? store->sc.minl : store->sc.llmt;
+    S.noll = store->sc.noll; S.lgop = store->sc.lgop; S.lgep = store->sc.lgep; S.codonk1 = store->sc.codonk1;
+    switch (T.launcher) {
+    case BY_LOCAL_UDH:   HIPCHK(spdp_launch_local_udh(&S, strm())); break;
+    case BY_EXACT:       HIPCHK(spdp_launch_exact(T.arg, &S, strm())); break;
+    case BY_ROWWAVE_UDH: HIPCHK(spdp_launch_rowwave_udh(&S, strm())); break;
+    default:             HIPCHK(spdp_launch_rowwave(cut ? 2 : T.arg, &S, strm())); break;    // (cut: RUN_A0_FORWARD only, lay_out)
+    }
+    HIPCHK(hipEventRecord(eve(), strm()));
+    return 0;
+}
+
+// the `_wip` sweeps
+int DevRun::launch_sweep()
+{
+    const RunTraits& T = traits();
     SweepArgs A;
     A.sc = (const DevScoring*) store->d_sc; A.probs = (const DevProblem*) d_probs; A.n_probs = n;
     A.a_codes = (const uint8_t*) store->d_a; A.cols = (const int2*) store->d_cols; A.bnd = (int*) d_bnd;
@@ -766,34 +805,25 @@ int DevRun::launch()
     HIPCHK(hipEventRecord(evb(), strm()));
     const int nq = std::max(1, std::min(store->sc.nquant, SPDP_MAX_QUANT));
     const int pen_cap = nq > 1 ? store->sc.qm_len[nq - 2] + 1 : 0;
-    // the fp32-issue form of the sweep (spdp_sweep_fp.hip) where it applies: non-local score-only / linear-space runs
-    // whose scores stay inside the exact fp32 integer range; SPDP_FP=0 keeps everything on spdp_kernels.hip
+    // the fp32-issue form of the sweep (spdp_sweep_fp.hip) where it applies: non-local runs whose scores stay inside the
+    // exact fp32 integer range; SPDP_FP=0 keeps everything on spdp_kernels.hip, SPDP_FP_FWD=0 the traceback sweep
     bool done = false;
-    const bool fp_fwd = !(getenv("SPDP_FP_FWD") && atoi(getenv("SPDP_FP_FWD")) == 0);       // SPDP_FP_FWD=0: the traceback sweep stays on spdp_kernels.hip
-    if (fp_ok && (flavour != 1 || fp_fwd) && !store->sc.local) {
-        const hipError_t e = spdp_launch_sweep_fp(flavour, 0, store->sc.spj ? 1 : 0, nq, pen_cap, store->sc.llmt, &A, grid, wpb, strm());
+    if (fp_ok && (T.kind != KIND_FORWARD || spdp_knob_on("SPDP_FP_FWD")) && !store->sc.local) {
+        const hipError_t e = spdp_launch_sweep_fp(T.arg, 0, store->sc.spj ? 1 : 0, nq, pen_cap, store->sc.llmt, &A, grid, wpb, strm());
         if (e == hipSuccess) done = true;
         else if (e != hipErrorNotSupported) HIPCHK(e);
     }
-    if (!done) HIPCHK(spdp_launch_sweep(flavour, store->sc.local ? 1 : 0, nq, pen_cap, &A, grid, wpb, strm()));
+    if (!done) HIPCHK(spdp_launch_sweep(T.arg, store->sc.local ? 1 : 0, nq, pen_cap, &A, grid, wpb, strm()));
     ++ctx->sweep_stats[done ? 0 : 1];
     if (cross_g > 0) ++ctx->sweep_stats[2];
     if (wpb == 16) ++ctx->sweep_stats[3];
     HIPCHK(hipEventRecord(eve(), strm()));
-    if (flavour == 1) {
+    if (T.records()) {
         WalkArgs W;
         W.probs = A.probs; W.n_probs = n; W.tb = (const uint8_t*) d_tb; W.res = (const DevResult*) d_res;
         W.skl = (int2*) d_skl; W.n_skl = (int*) d_nskl; W.skl_cap = skl_cap;
         { const char* sw = getenv("SPDP_WALK_SEQ"); W.seq = (sw && atoi(sw) != 0) ? 1 : 0; }
         HIPCHK(spdp_launch_walk(&W, strm()));
-    }
-    if (flavour == 2) {
-        CposArgs C{};
-        C.probs = A.probs; C.n_probs = n; C.imd = (const int*) d_imd; C.res = (const DevResult*) d_res;
-        C.cpos = (int*) d_cpos; C.ranges = (int*) d_ranges; C.scores = (int*) d_scores;
-        C.cpos_stride = 10 * (max_n_im + 1); C.strict = 0; C.local = 0;
-        C.edge = (int*) d_scores + n;
-        HIPCHK(spdp_launch_cpos(&C, strm()));
     }
     return 0;
 }
@@ -856,7 +886,7 @@ int DevRun::sync()
             mcell = std::max<int64_t>(mcell, h_probs[j].cells);
         }
         fprintf(stderr, "[spdp run] flavour %d n %d cells %.3g (largest %.3g, rows <= %d, width <= %d) pipe %d items %zu  %.2f ms  %.1f GCUPS\n",
-                flavour, n, (double) total_cells, (double) mcell, mr, mc, (int) pipe.on, pipe.items.size() / 2, kernel_ms,
+                (int) flavour, n, (double) total_cells, (double) mcell, mr, mc, (int) pipe.on, pipe.items.size() / 2, kernel_ms,
                 total_cells / (kernel_ms * 1e6));
     }
     return 0;
@@ -873,19 +903,18 @@ int DevRun::fetch_results(std::vector<DevResult>& out)
 
 int DevRun::fetch_skl(std::vector<int>& n_skl, std::vector<int64_t>& off, std::vector<SpdpSkl>& skl)
 {
-    const int flav = flavour;
     n_skl.assign(n, 0); off.assign(n + 1, 0);
     if (!n) { skl.clear(); return 0; }
     std::vector<int> cnt(n);                            // dispatch order
     HIPCHK(spdp_copy_sync(cnt.data(), d_nskl, sizeof(int) * n, hipMemcpyDeviceToHost, strm()));
     // Lists that did not fit their slot (skl_cap is sized for typical lists; an indel-rich slab can need more): the
     // walk is repeated for those few with slots of the longest list their problem can produce.  Only the `_wip`
-    // walk (flavour 1) can be repeated on its own; the scalar / -A1 engines walk inside their sweep kernel and
+    // walk (RUN_WIP_FORWARD) can be repeated on its own; the scalar / -A1 engines walk inside their sweep kernel and
     // report the overflow (-1) to the caller, who gives up that one query, not the batch.
     std::vector<int> over;
     for (int j = 0; j < n; ++j) if (cnt[j] == -1) over.push_back(j);
     std::vector<std::vector<SpdpSkl>> redo(over.size());
-    if (!over.empty() && flav == 1) {
+    if (!over.empty() && flavour == RUN_WIP_FORWARD) {
         const int m = (int) over.size();
         std::vector<DevResult> all_res(n), sub_res(m);
         std::vector<DevProblem> sub_probs(m);
@@ -950,13 +979,13 @@ int DevRun::fetch_skl(std::vector<int>& n_skl, std::vector<int64_t>& off, std::v
 int DevRun::fetch_udh(std::vector<int32_t>& scores, std::vector<int32_t>& cpos, std::vector<int32_t>& ranges,
                       std::vector<int32_t>* edge)
 {
-    const size_t st = (size_t) 10 * (max_n_im + 1);
+    const size_t st = cpos_stride();
     scores.resize(n); ranges.resize((size_t) 4 * n); cpos.resize(st * n);
     if (edge) edge->assign(n, 0);
     if (n) {
         std::vector<int32_t> ts(n), tr((size_t) 4 * n), tc(st * n);
         HIPCHK(spdp_copy_sync(ts.data(), d_scores, sizeof(int32_t) * n, hipMemcpyDeviceToHost, strm()));
-        if (edge && (flavour == 2 || flavour >= 8)) {
+        if (edge && traits().edge) {
             std::vector<int32_t> te(n);
             HIPCHK(spdp_copy_sync(te.data(), (int32_t*) d_scores + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, strm()));
             for (int j = 0; j < n; ++j) (*edge)[order[j]] = te[j];
@@ -981,18 +1010,21 @@ static std::vector<RunItem> items_of(const SpdpScoring* sc, const SpdpProblem* p
     return v;
 }
 
-int spdp_wip_scoreonly(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs,
-                       int n_probs, int32_t* scores)
+static int score_like(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs, int32_t* scores, RunFlavour flav)
 {
     if (!ctx) return -1;
     if (n_probs <= 0) return 0;
     DevStore st; DevRun run;
-    if (st.upload(ctx, sc, probs, n_probs)) return -1;
-    if (run.build(&st, items_of(sc, probs, n_probs), 0) || run.launch() || run.sync()) return -1;
     std::vector<DevResult> r;
-    if (run.fetch_results(r)) return -1;
+    if (st.upload(ctx, sc, probs, n_probs)) return -1;
+    if (run.build(&st, items_of(sc, probs, n_probs), flav) || run.launch() || run.sync() || run.fetch_results(r)) return -1;
     for (int i = 0; i < n_probs; ++i) scores[i] = r[i].score;
     return 0;
+}
+
+int spdp_wip_scoreonly(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs, int32_t* scores)
+{
+    return score_like(ctx, sc, probs, n_probs, scores, RUN_WIP_SCORE);
 }
 
 // HomScoreS_ng on an uploaded store (src/fwd2s1.cc:2696-2716): scoreonlyS1_wip on the stripe() band for
@@ -1001,37 +1033,23 @@ int spdp_wip_scoreonly(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProble
 static int homscore_on_store(SpdpContext* ctx, const DevStore& st, const SpdpProblem* probs, int n_probs, int32_t* scores)
 {
     const SpdpScoring* sc = &st.sc;
-    std::vector<RunItem> vec, sca, exa;
-    std::vector<int> vi, si, ei;
+    const RunFlavour leg_flav[3] = {RUN_WIP_SCORE, RUN_A0_SCORE, RUN_A1_SCORE};     // -A1: scoreonlyS1
+    std::vector<RunItem> items[3];
+    std::vector<int> at[3];
     int rc = 0;
     for (int i = 0; i < n_probs; ++i) {
         scores[i] = SPDP_NEVSEL;
-        RunItem it = spdp_item_of(probs[i], i, sc->sh);
-        const int m = it.a_right - it.a_left;
-        if (it.w.width < 3) { rc = 1; continue; }
-        if (sc->scalar_engines == 1 || m < 4) {
-            if (!st.has_exact) { rc = 1; continue; }
-            sca.push_back(it); si.push_back(i);
-        } else if (sc->scalar_engines == 2) {           // -A1: scoreonlyS1
-            if (!st.has_exact) { rc = 1; continue; }
-            exa.push_back(it); ei.push_back(i);
-        } else { vec.push_back(it); vi.push_back(i); }
+        const RunItem it = spdp_item_of(probs[i], i, sc->sh);
+        const int leg = (sc->scalar_engines == 1 || it.a_right - it.a_left < 4) ? 1 : (sc->scalar_engines == 2 ? 2 : 0);
+        if (it.w.width < 3 || (leg && !st.has_exact)) { rc = 1; continue; }
+        items[leg].push_back(it); at[leg].push_back(i);
     }
-    std::vector<DevResult> r;
-    if (!vec.empty()) {
+    for (int leg = 0; leg < 3; ++leg) {
         DevRun run;
-        if (run.build(&st, vec, 0) || run.launch() || run.sync() || run.fetch_results(r)) return -1;
-        for (size_t k = 0; k < vec.size(); ++k) scores[vi[k]] = r[k].score;
-    }
-    if (!sca.empty()) {
-        DevRun run;
-        if (run.build(&st, sca, 4) || run.launch() || run.sync() || run.fetch_results(r)) return -1;
-        for (size_t k = 0; k < sca.size(); ++k) scores[si[k]] = r[k].score;
-    }
-    if (!exa.empty()) {
-        DevRun run;
-        if (run.build(&st, exa, 6) || run.launch() || run.sync() || run.fetch_results(r)) return -1;
-        for (size_t k = 0; k < exa.size(); ++k) scores[ei[k]] = r[k].score;
+        std::vector<DevResult> r;
+        if (items[leg].empty()) continue;
+        if (run.build(&st, items[leg], leg_flav[leg]) || run.launch() || run.sync() || run.fetch_results(r)) return -1;
+        for (size_t k = 0; k < r.size(); ++k) scores[at[leg][k]] = r[k].score;
     }
     return rc;
 }
@@ -1046,55 +1064,48 @@ int spdp_homscore_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* 
     return homscore_on_store(ctx, st, probs, n_probs, scores);
 }
 
-int spdp_wip_forward(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs,
-                     int n_probs, SpdpAlignment* out);
-
-int spdp_wip_udh(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
-                 int n_im, int32_t* scores, int32_t* cpos, int32_t* ranges)
+// a linear-space engine on whole problems: n_im intermediate rows each, imd_intvl apart (-A0; 0: the engine's own spacing);
+// flags: DevResult::pad[0] per problem, or null
+static int udh_like(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs, RunFlavour flav, int n_im,
+                    int imd_intvl, int32_t* scores, int32_t* cpos, int32_t* ranges, int32_t* flags)
 {
-    if (!ctx) return -1;
-    if (n_probs <= 0) return 0;
-    DevStore st; DevRun run;
-    if (st.upload(ctx, sc, probs, n_probs)) return -1;
-    std::vector<RunItem> items = items_of(sc, probs, n_probs);
-    for (auto& it : items) it.n_im = n_im;
-    if (run.build(&st, items, 2) || run.launch() || run.sync()) return -1;
-    std::vector<int32_t> s, c, r;
-    if (run.fetch_udh(s, c, r)) return -1;
-    memcpy(scores, s.data(), sizeof(int32_t) * n_probs);
-    memcpy(ranges, r.data(), sizeof(int32_t) * 4 * n_probs);
-    memcpy(cpos, c.data(), sizeof(int32_t) * c.size());
-    return 0;
-}
-
-int spdp_scalar_udh(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
-                    int n_im, int imd_intvl, int32_t* scores, int32_t* cpos, int32_t* ranges, int32_t* flags)
-{
-    if (!ctx || !sc || !probs || !scores || !cpos || !ranges || !flags || n_im < 1 || imd_intvl < 1) return -1;
     if (n_probs <= 0) return 0;
     DevStore st; DevRun run;
     if (st.upload(ctx, sc, probs, n_probs)) return -1;
     std::vector<RunItem> items = items_of(sc, probs, n_probs);
     for (auto& it : items) {
         it.n_im = n_im; it.imd_intvl = imd_intvl;
-        if (it.a_left + (int64_t) n_im * imd_intvl > it.a_right + imd_intvl) { ctx->err = "intermediate rows beyond the query range"; return -1; }
+        if (imd_intvl > 0 && it.a_left + (int64_t) n_im * imd_intvl > it.a_right + imd_intvl) { ctx->err = "intermediate rows beyond the query range"; return -1; }
     }
-    // test hook: the same call on hirschbergS1 (the -A1 linear-space engine, spdp_exact<2> + spdp_udh_cpos), which the ABI
-    // otherwise reaches through alignS_ng only; imd_intvl is then the engine's own (a_right - a_left + n_im) / (n_im + 1)
-    const int flav = getenv("SPDP_UDH_ENGINE_A1") ? 8 : 5;
     if (run.build(&st, items, flav) || run.launch() || run.sync()) return -1;
     std::vector<int32_t> s, c, r;
     std::vector<DevResult> res;
-    if (run.fetch_udh(s, c, r) || run.fetch_results(res)) return -1;
+    if (run.fetch_udh(s, c, r) || (flags && run.fetch_results(res))) return -1;
     memcpy(scores, s.data(), sizeof(int32_t) * n_probs);
     memcpy(ranges, r.data(), sizeof(int32_t) * 4 * n_probs);
     memcpy(cpos, c.data(), sizeof(int32_t) * c.size());
-    for (int i = 0; i < n_probs; ++i) flags[i] = res[i].pad[0];
+    for (int i = 0; flags && i < n_probs; ++i) flags[i] = res[i].pad[0];
     return 0;
 }
 
+int spdp_wip_udh(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
+                 int n_im, int32_t* scores, int32_t* cpos, int32_t* ranges)
+{
+    return ctx ? udh_like(ctx, sc, probs, n_probs, RUN_WIP_UDH, n_im, 0, scores, cpos, ranges, nullptr) : -1;
+}
+
+int spdp_scalar_udh(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
+                    int n_im, int imd_intvl, int32_t* scores, int32_t* cpos, int32_t* ranges, int32_t* flags)
+{
+    if (!ctx || !sc || !probs || !scores || !cpos || !ranges || !flags || n_im < 1 || imd_intvl < 1) return -1;
+    // test hook: the same call on hirschbergS1 (the -A1 linear-space engine, spdp_exact<2> + spdp_udh_cpos), which the ABI
+    // otherwise reaches through alignS_ng only; imd_intvl is then the engine's own (a_right - a_left + n_im) / (n_im + 1)
+    const RunFlavour flav = getenv("SPDP_UDH_ENGINE_A1") ? RUN_A1_UDH : RUN_A0_UDH;
+    return udh_like(ctx, sc, probs, n_probs, flav, n_im, imd_intvl, scores, cpos, ranges, flags);
+}
+
 static int forward_like(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
-                        SpdpAlignment* out, int flav)
+                        SpdpAlignment* out, RunFlavour flav)
 {
     if (!ctx) return -1;
     for (int i = 0; i < n_probs; ++i) { out[i].score = SPDP_NEVSEL; out[i].n_skl = 0; out[i].skl = nullptr; out[i].flags = 0; out[i].reserved = 0; }
@@ -1122,27 +1133,18 @@ static int forward_like(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProbl
 int spdp_scalar_forward(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs,
                         int n_probs, SpdpAlignment* out)
 {   // Aln2s1::forwardS_ng through trcbkalignS_ng (scalar exact engine)
-    return forward_like(ctx, sc, probs, n_probs, out, 3);
+    return forward_like(ctx, sc, probs, n_probs, out, RUN_A0_FORWARD);
 }
 
-int spdp_scalar_scorealone(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs,
-                           int n_probs, int32_t* scores)
+int spdp_scalar_scorealone(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs, int32_t* scores)
 {   // Aln2s1::scorealoneS_ng = HomScoreS_ng under -A0
-    if (!ctx) return -1;
-    if (n_probs <= 0) return 0;
-    DevStore st; DevRun run;
-    if (st.upload(ctx, sc, probs, n_probs)) return -1;
-    if (run.build(&st, items_of(sc, probs, n_probs), 4) || run.launch() || run.sync()) return -1;
-    std::vector<DevResult> r;
-    if (run.fetch_results(r)) return -1;
-    for (int i = 0; i < n_probs; ++i) scores[i] = r[i].score;
-    return 0;
+    return score_like(ctx, sc, probs, n_probs, scores, RUN_A0_SCORE);
 }
 
 int spdp_wip_forward(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs,
                      int n_probs, SpdpAlignment* out)
 {
-    return forward_like(ctx, sc, probs, n_probs, out, 1);
+    return forward_like(ctx, sc, probs, n_probs, out, RUN_WIP_FORWARD);
 }
 
 void spdp_free_alignments(SpdpAlignment* out, int n)

@@ -30,7 +30,6 @@
         }                                                                                \
     } while (0)
 
-enum { H_POOL = 5, HU_POOL = 6 };           // ctx->pool[] slot groups: inputs + traceback runs / linear-space runs
 enum { HP_SC = 0, HP_A, HP_COLS, HP_AUX, HP_PROBS, HP_BND, HP_TB, HP_RES, HP_SKL, HP_NSKL, HP_PACK, HP_OFF, HP_INTPEN, HP_PIPE };
 #include "spdp_gencode.h"
 int spdh_signals_run(SpdpContext* ctx, const SpdpSignalModelH* m, const std::vector<SigJobH>& jobs, SignalArgsH args, int pack);   // spdp_signals_api.cpp
@@ -507,7 +506,7 @@ static int pipe_plan(SpdpContext* ctx, const std::vector<DevProblemH>& probs, bo
             pp.plan((int) j, P.a_right - (P.a_left + (P.a_exgl ? 1 : 0)), udh ? std::max(1, std::min(64, P.imd_intvl)) : 64);
         }
     if (!wanted || pp.max_tiles < 2) return 0;
-    if (!pp.reserve(ctx->pool[udh ? HU_POOL : H_POOL], udh ? HU_PIPE : HP_PIPE, (int) probs.size(), 2 + (exact ? 7 : 9) * pp.max_tiles + 3 * max_im)) {
+    if (!pp.reserve(ctx->pool[udh ? HU_POOL : H_POOL], udh ? HU_PIPE : HP_PIPE, (int) probs.size(), exact ? SPDP_PIPE_TPW_H_A1 : SPDP_PIPE_TPW_H_A0, 3 * max_im)) {
         ctx->err = "device allocation failed (tile / stripe pipeline of the aa x genome engines)";
         return -1;
     }

@@ -402,11 +402,9 @@ struct Aligner {
         // forward sweep starts on the side stream as soon as the first classification is done (an EST batch
         // has a handful of stragglers in the linear-space engine; that launch is latency-bound and would
         // otherwise hold up everything).  SPDP_OVERLAP=0 restores the single-stream order.
-        DevRun side;
-        side.use_ctx = ctx;
+        DevRun side(ctx);
         std::vector<TbItem> side_tbs;
-        const char* ov = getenv("SPDP_OVERLAP");
-        bool may_overlap = ctx->stream2 != nullptr && !(ov && atoi(ov) == 0);
+        bool may_overlap = ctx->stream2 != nullptr && spdp_knob_on("SPDP_OVERLAP");
         bool first_round = true;
         while (!pending.empty()) {
             std::vector<LspItem> cur;
@@ -419,7 +417,7 @@ struct Aligner {
                 std::vector<RunItem> items;
                 for (const TbItem& t : side_tbs) { items.push_back(run_item(parent(t.job), t.r, t.w, 0)); items.back().vmf_scale = 1 << 20; }   // (a few rows each)
                 side.side = true;
-                if (side.build(st, items, 1) || side.launch()) return -1;
+                if (side.build(st, items, RUN_WIP_FORWARD) || side.launch()) return -1;
                 lap("side fwd build+launch");
             }
             may_overlap = false;                        // first round only
@@ -429,11 +427,10 @@ struct Aligner {
                 items.push_back(run_item(parent(u.job), u.r, u.w, u.n_imd));
                 items.back().imd_intvl = u.imd_intvl;
             }
-            DevRun run;
-            run.use_ctx = ctx;
+            DevRun run(ctx);
             run.beside = !side_tbs.empty();
             const bool a0 = sc.scalar_engines == 1;
-            if (run.build(st, items, a0 ? 5 : (sc.scalar_engines == 2 ? 8 : 2))) return -1;
+            if (run.build(st, items, a0 ? RUN_A0_UDH : (sc.scalar_engines == 2 ? RUN_A1_UDH : RUN_WIP_UDH))) return -1;
             lap("udh build");
             if (first_round && gate_in && gate_in->wait() == 1) HIPCHK(hipStreamWaitEvent(run.strm(), gate_in->ev, 0));
             if (run.launch()) return -1;
@@ -453,7 +450,7 @@ struct Aligner {
             std::vector<DevResult> ures;
             if (a0 && run.fetch_results(ures)) return -1;
             lap("udh fetch");
-            const int stride = 10 * (run.max_n_im + 1);
+            const int stride = run.cpos_stride();
             for (size_t k = 0; k < udh.size(); ++k) {
                 const UdhItem& u = udh[k];
                 const int scr = scores[k];
@@ -476,13 +473,11 @@ struct Aligner {
         // forwardS_ng (-A0, and any sub-problem below 8 rows) and forwardS1 (-A1) keep their traceback as Vmf records,
         // up to two per cell: a whole batch of slabs can ask for more memory than the card has, so they run in
         // groups whose record space stays below SPDP_VMF_GB (default 32) gigabytes
-        auto run_vmf = [&](std::vector<TbItem>& list, int flav, const char* what) -> int {
+        auto run_vmf = [&](std::vector<TbItem>& list, RunFlavour flav, const char* what) -> int {
             size_t limit = (size_t) 32 << 30;
             if (const char* e = getenv("SPDP_VMF_GB")) limit = (size_t) std::max(1, atoi(e)) << 30;
-            auto recs_of = [](const TbItem& t, int scale) {
-                const size_t rows = t.r.ar - t.r.al + 1, cols = t.r.br - t.r.bl + 1;
-                const size_t band = rows * std::min<size_t>(cols, (size_t) t.w.width);
-                return std::min(2 * rows * cols + 64, std::max(band / 2, 64 * rows) * (size_t) scale + 64);
+            auto bytes_of = [](const TbItem& t, int scale) {
+                return (size_t) vmf_capacity(t.r.ar - t.r.al + 1, t.r.br - t.r.bl + 1, t.w.width, scale) * sizeof(int3);
             };
             std::vector<size_t> todo(list.size());
             for (size_t k = 0; k < list.size(); ++k) todo[k] = k;
@@ -490,8 +485,8 @@ struct Aligner {
                 std::vector<size_t> again;
                 for (size_t lo = 0; lo < todo.size(); ) {
                     size_t hi = lo, sum = 0;
-                    while (hi < todo.size() && (hi == lo || sum + recs_of(list[todo[hi]], scale) * sizeof(int3) <= limit))
-                        sum += recs_of(list[todo[hi++]], scale) * sizeof(int3);
+                    while (hi < todo.size() && (hi == lo || sum + bytes_of(list[todo[hi]], scale) <= limit))
+                        sum += bytes_of(list[todo[hi++]], scale);
                     std::vector<RunItem> items;
                     for (size_t k = lo; k < hi; ++k) {
                         const TbItem& t = list[todo[k]];
@@ -499,8 +494,7 @@ struct Aligner {
                         items.back().vmf_scale = scale;
                         items.back().cut_l = t.cut_l; items.back().cut_r = t.cut_r;
                     }
-                    DevRun run;
-                    run.use_ctx = ctx;
+                    DevRun run(ctx);
                     if (run.build(st, items, flav) || run.launch() || run.sync()) return -1;
                     kernel_ms += run.kernel_ms; kernel_cells += run.total_cells;
                     stats[3] += run.kernel_ms; stats[4] += (double) run.total_cells; stats[5] += (double) items.size();
@@ -525,15 +519,15 @@ struct Aligner {
             }
             return 0;
         };
-        if (!stbs.empty() && run_vmf(stbs, 3, "forwardS_ng traceback failed")) return -1;
-        if (!ctbs.empty() && run_vmf(ctbs, 3, "forwardS_ng (cut range) traceback failed")) return -1;
-        if (!xtbs.empty() && run_vmf(xtbs, 7, "forwardS1 traceback failed")) return -1;
+        if (!stbs.empty() && run_vmf(stbs, RUN_A0_FORWARD, "forwardS_ng traceback failed")) return -1;
+        if (!ctbs.empty() && run_vmf(ctbs, RUN_A0_FORWARD, "forwardS_ng (cut range) traceback failed")) return -1;
+        if (!xtbs.empty() && run_vmf(xtbs, RUN_A1_FORWARD, "forwardS1 traceback failed")) return -1;
         // all (remaining) trcbkalignS_ng calls of all queries: one forward sweep + one walk (beside the side run, if any)
         // A few tall slabs among many short ones (the recursion on a long cDNA leaves slabs of thousands of rows whose band
         // is narrow enough for the traceback): the launch would end with its tallest problem on the four waves of one
         // block.  They go to the side stream as a launch of their own -- all of them tall, so each gets a 16-wave block
         // (DevRun::build) -- beside the launch of the rest.  SPDP_SPLIT_FWD=0: one launch.
-        if (side_tbs.empty() && ctx->stream2 != nullptr && tbs.size() > 1 && !(getenv("SPDP_SPLIT_FWD") && atoi(getenv("SPDP_SPLIT_FWD")) == 0)) {
+        if (side_tbs.empty() && ctx->stream2 != nullptr && tbs.size() > 1 && spdp_knob_on("SPDP_SPLIT_FWD")) {
             const int tall = 4 * 32 * SPDP_NELEM;               // >= 32 passes: DevRun::build's condition for 16-wave blocks
             std::vector<TbItem> rest;
             for (const TbItem& t : tbs) (t.r.ar - t.r.al >= tall ? side_tbs : rest).push_back(t);
@@ -543,57 +537,46 @@ struct Aligner {
                 std::vector<RunItem> items;
                 for (const TbItem& t : side_tbs) items.push_back(run_item(parent(t.job), t.r, t.w, 0));
                 side.side = true;
-                if (side.build(st, items, 1) || side.launch()) return -1;
+                if (side.build(st, items, RUN_WIP_FORWARD) || side.launch()) return -1;
                 lap("tall fwd build+launch");
             }
         }
-        if (!tbs.empty()) {
-            std::vector<RunItem> items;
-            for (const TbItem& t : tbs) items.push_back(run_item(parent(t.job), t.r, t.w, 0));
-            DevRun run;
-            run.use_ctx = ctx;
-            run.beside = !side_tbs.empty();
-            if (run.build(st, items, 1)) return -1;
-            lap("fwd build");
-            if (run.launch() || run.sync()) return -1;
-            lap("fwd launch+sync (+walk)");
-            kernel_ms += run.kernel_ms; kernel_cells += run.total_cells;
-            stats[3] += run.kernel_ms; stats[4] += (double) run.total_cells; stats[5] += (double) items.size();
-            stats[7] += (double) run.tb_bytes;
+        // the scores and records of a finished `_wip` forward run into the jobs of its items
+        auto collect = [&](DevRun& r, const std::vector<TbItem>& list, const char* fetched) -> int {
+            kernel_ms += r.kernel_ms; kernel_cells += r.total_cells;
+            stats[3] += r.kernel_ms; stats[4] += (double) r.total_cells; stats[5] += (double) list.size();
+            stats[7] += (double) r.tb_bytes;
             std::vector<DevResult> res;
             std::vector<int> nskl;
             std::vector<int64_t> off;
             std::vector<SpdpSkl> skl;
-            if (run.fetch_results(res) || run.fetch_skl(nskl, off, skl)) return -1;
-            lap("fwd fetch");
-            for (size_t k = 0; k < tbs.size(); ++k) {
-                const TbItem& t = tbs[k];
+            if (r.fetch_results(res) || r.fetch_skl(nskl, off, skl)) return -1;
+            if (fetched) lap(fetched);
+            for (size_t k = 0; k < list.size(); ++k) {
+                const TbItem& t = list[k];
                 if (nskl[k] == -1) { jobs[t.job].failed = true; ++overflowed; continue; }    // record list beyond its slot: this query only
                 if (nskl[k] < 0) { ctx->err = "traceback walk failed"; return -1; }
                 set_score(t.job, t.top, res[k].score);
                 const SpdpSkl* s = skl.data() + off[k];
                 jobs[t.job].rec.insert(jobs[t.job].rec.end(), s, s + nskl[k]);
             }
+            return 0;
+        };
+        if (!tbs.empty()) {
+            std::vector<RunItem> items;
+            for (const TbItem& t : tbs) items.push_back(run_item(parent(t.job), t.r, t.w, 0));
+            DevRun run(ctx);
+            run.beside = !side_tbs.empty();
+            if (run.build(st, items, RUN_WIP_FORWARD)) return -1;
+            lap("fwd build");
+            if (run.launch() || run.sync()) return -1;
+            lap("fwd launch+sync (+walk)");
+            if (collect(run, tbs, "fwd fetch")) return -1;
         }
         if (!side_tbs.empty()) {                        // collect the side run (its own pool: the runs above went on beside it)
             if (side.sync()) return -1;
             lap("side fwd sync");
-            kernel_ms += side.kernel_ms; kernel_cells += side.total_cells;
-            stats[3] += side.kernel_ms; stats[4] += (double) side.total_cells; stats[5] += (double) side_tbs.size();
-            stats[7] += (double) side.tb_bytes;
-            std::vector<DevResult> res;
-            std::vector<int> nskl;
-            std::vector<int64_t> off;
-            std::vector<SpdpSkl> skl;
-            if (side.fetch_results(res) || side.fetch_skl(nskl, off, skl)) return -1;
-            for (size_t k = 0; k < side_tbs.size(); ++k) {
-                const TbItem& t = side_tbs[k];
-                if (nskl[k] == -1) { jobs[t.job].failed = true; ++overflowed; continue; }    // record list beyond its slot: this query only
-                if (nskl[k] < 0) { ctx->err = "traceback walk failed"; return -1; }
-                set_score(t.job, t.top, res[k].score);
-                const SpdpSkl* sk = skl.data() + off[k];
-                jobs[t.job].rec.insert(jobs[t.job].rec.end(), sk, sk + nskl[k]);
-            }
+            if (collect(side, side_tbs, nullptr)) return -1;
         }
         lap("assemble records");
         return 0;
@@ -668,7 +651,7 @@ int spdp_batch_homscore(SpdpBatch* bt, int32_t* scores, float* kernel_ms)
         std::vector<RunItem> items;
         for (size_t i = 0; i < bt->probs.size(); ++i)
             items.push_back(spdp_item_of(bt->probs[i], (int) i, bt->store.sc.sh));
-        if (bt->score.build(&bt->store, items, 0)) return -1;
+        if (bt->score.build(&bt->store, items, RUN_WIP_SCORE)) return -1;
     }
     if (bt->score.launch() || bt->score.sync()) return -1;
     if (kernel_ms) *kernel_ms = bt->score.kernel_ms;

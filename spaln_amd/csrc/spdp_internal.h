@@ -234,7 +234,10 @@ struct DevPool {
     void   release();
 };
 enum { POOL_PROBS = 0, POOL_BND, POOL_TB, POOL_IMD, POOL_RES, POOL_SKL, POOL_NSKL, POOL_CPOS,
-       POOL_RANGES, POOL_SCORES, POOL_SKLPACK, POOL_SKLOFF, POOL_GPROG, POOL_FLAV_STRIDE = 0 };
+       POOL_RANGES, POOL_SCORES, POOL_SKLPACK, POOL_SKLOFF, POOL_GPROG };
+
+// an on / off knob of the environment: unset or non-zero = on.  Read on every call (the tests flip knobs between calls)
+static inline bool spdp_knob_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }
 
 // a blocking copy.  hipMemcpy goes through the null stream, which first waits for every blocking stream of the process.  For the
 // request batches of the seeded path -- several dispatcher lanes at work, a 16-byte read-back of the short class would wait
@@ -269,6 +272,7 @@ struct TilePipe {
     std::vector<int> items;                 // (problem or group, tile) pairs in dispatch order
     int max_tiles = 1;                      // most tiles of one problem
     int stride = 0;                         // sync words per problem
+    int rlf_off = 0;                        // of these, where the words of the intermediate rows start
     size_t words = 0;                       // sync words ahead of the item list
     int* d = nullptr;                       // words, then items (owned by the pool reserve() took it from)
     bool on = false;
@@ -286,10 +290,12 @@ struct TilePipe {
             add(q, ns);
         }
     }
-    // the device words of n problems; false = out of device memory
-    bool reserve(DevPool& pool, int slot, int n, int stride_)
+    // the device words of n problems of an engine with tpw words per tile (SPDP_PIPE_TPW_*) and `extra` words for its
+    // intermediate rows; false = out of device memory
+    bool reserve(DevPool& pool, int slot, int n, int tpw, int extra)
     {
-        stride = stride_;
+        rlf_off = SPDP_PIPE_HDR + tpw * max_tiles;
+        stride = rlf_off + extra;
         words = ((size_t) n * stride + 2 + 1) & ~(size_t) 1;
         d = (int*) pool.get(slot, sizeof(int) * (words + items.size()));
         return on = d != nullptr;
@@ -315,9 +321,11 @@ struct TilePipe {
     }
 };
 
+// SpdpContext::pool: runs that may be in flight together never share one.  The first five: DevRun's (RUN_TRAITS below); H_POOL / HU_POOL: the
+// aa x genome path's inputs + traceback runs / linear-space runs; R_POOL: rescoring; SIDE_POOL: a DevRun on the side stream, of any flavour
+enum CtxPool { WIP_SCORE_POOL = 0, WIP_FORWARD_POOL, WIP_UDH_POOL, EXACT_FORWARD_POOL, EXACT_POOL, H_POOL, HU_POOL, R_POOL, SIDE_POOL, N_CTX_POOLS };
 struct SpdpContext {
-    DevPool pool[9];                 // one pool per engine flavour (they coexist in a pipeline); [5], [6] = aa x genome path, [7] = rescoring,
-                                     // [8] = the forward run on the side stream (coexists with a regular forward run)
+    DevPool pool[N_CTX_POOLS];
     int device = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;
@@ -330,7 +338,7 @@ struct SpdpContext {
     int64_t seed_stats[12] = {0};      // spdp_seeded_stats
     std::vector<std::vector<SpdpPhaseMark>> seed_marks;    // spdp_seeded_phase_marks: per query of the last spdp_align_h_seeded call
     int64_t rerun_stats[2] = {0, 0};   // launches repeated because a cross-CU group / a tile pipeline gave up (spdp_rerun_stats)
-    // launches of the `_wip` sweeps (flavours 0 .. 2 of DevRun::launch, repeats included): served by spdp_sweep_fp, served by
+    // launches of the `_wip` sweeps (the FAM_WIP flavours of DevRun::launch, repeats included): served by spdp_sweep_fp, served by
     // spdp_sweep, with cross-CU groups, as 16-wave blocks (spdp_sweep_stats; atomic: a side-stream run launches from its own thread)
     std::atomic<int64_t> sweep_stats[4] = {};
     void*  stage_ptr[3] = {nullptr, nullptr, nullptr};   // pinned host staging (grow-only): [0], [1] DevStore::upload, [2] the regions and
@@ -392,21 +400,56 @@ struct RunItem {
     int cut_l = 0, cut_r = 0;   // scalar forward only: forwardS_ng's cut range (cut_r > cut_l), see spdp_rowwave<1, false, true>
 };
 
-// descriptors + work buffers of one engine flavour over a DevStore:
-// 0 score, 1 forward, 2 udh (the _wip sweeps); 3 scalar exact forward, 4 scalar exact score,
-// 5 scalar udh, 6 -A1 score-only (both share pool 4 with the scalar score run: they never coexist),
-// 7 -A1 forward (shares pool 3 with the scalar forward run), 8 -A1 udh (pool 4), 9 local udh (-LS; pool 4)
+// The engines a DevRun drives.  SPDP_TRACE_RUNS prints the number; DESIGN.md section 5 has the table with kernels and outputs.
+enum RunFlavour : int { RUN_WIP_SCORE = 0, RUN_WIP_FORWARD, RUN_WIP_UDH, RUN_A0_FORWARD, RUN_A0_SCORE, RUN_A0_UDH,
+                        RUN_A1_SCORE, RUN_A1_FORWARD, RUN_A1_UDH, RUN_LOCAL_UDH, RUN_N_FLAVOURS };
+enum RunFamily : uint8_t { FAM_WIP, FAM_A0, FAM_A1, FAM_LOCAL };
+enum RunKind : uint8_t { KIND_SCORE, KIND_FORWARD, KIND_UDH };
+enum RunLauncher : uint8_t { BY_SWEEP, BY_ROWWAVE, BY_ROWWAVE_UDH, BY_EXACT, BY_LOCAL_UDH };
+struct RunTraits {
+    RunFamily   family;
+    RunKind     kind;
+    CtxPool     pool;       // of a run on the main stream: flavours that share one are never in flight together
+    bool        vmf;        // the traceback is kept as Vmf records (tb = int3 records, DevProblem::imd_off = the problem's budget)
+    bool        edge;       // spdp_udh_cpos walks the links after the sweep and leaves CposArgs::edge
+    uint8_t     bw;         // ints per entry of the boundary / work buffer
+    uint8_t     pipe_tpw;   // tile pipeline: sync words per tile (SPDP_PIPE_TPW_*), 0 = the engine has none
+    RunLauncher launcher;
+    int         arg;        // its flavour / forward / mode argument
+    constexpr bool records() const { return kind == KIND_FORWARD; }     // a record list per problem (skl, n_skl)
+    constexpr bool rows() const { return kind == KIND_UDH; }            // intermediate rows in, cpos / ranges / scores out
+};
+inline constexpr RunTraits RUN_TRAITS[RUN_N_FLAVOURS] = {
+    //                    family     kind          pool                vmf    edge  bw  pipe_tpw              launcher
+    /* RUN_WIP_SCORE   */ {FAM_WIP,   KIND_SCORE,   WIP_SCORE_POOL,     false, false, 2, 0,                    BY_SWEEP,       0},
+    /* RUN_WIP_FORWARD */ {FAM_WIP,   KIND_FORWARD, WIP_FORWARD_POOL,   false, false, 2, 0,                    BY_SWEEP,       1},
+    /* RUN_WIP_UDH     */ {FAM_WIP,   KIND_UDH,     WIP_UDH_POOL,       false, true,  4, 0,                    BY_SWEEP,       2},
+    /* RUN_A0_FORWARD  */ {FAM_A0,    KIND_FORWARD, EXACT_FORWARD_POOL, true,  false, 1, SPDP_PIPE_TPW_A0,     BY_ROWWAVE,     1},   // (2 over cut ranges)
+    /* RUN_A0_SCORE    */ {FAM_A0,    KIND_SCORE,   EXACT_POOL,         false, false, 1, SPDP_PIPE_TPW_A0,     BY_ROWWAVE,     0},
+    /* RUN_A0_UDH      */ {FAM_A0,    KIND_UDH,     EXACT_POOL,         false, false, 1, SPDP_PIPE_TPW_A0_UDH, BY_ROWWAVE_UDH, 0},
+    /* RUN_A1_SCORE    */ {FAM_A1,    KIND_SCORE,   EXACT_POOL,         false, false, 1, SPDP_PIPE_TPW_A1,     BY_EXACT,       0},
+    /* RUN_A1_FORWARD  */ {FAM_A1,    KIND_FORWARD, EXACT_FORWARD_POOL, true,  false, 1, SPDP_PIPE_TPW_A1,     BY_EXACT,       1},
+    /* RUN_A1_UDH      */ {FAM_A1,    KIND_UDH,     EXACT_POOL,         false, true,  1, SPDP_PIPE_TPW_A1,     BY_EXACT,       2},
+    /* RUN_LOCAL_UDH   */ {FAM_LOCAL, KIND_UDH,     EXACT_POOL,         false, true,  1, 0,                    BY_LOCAL_UDH,   0},
+};
+
+// Vmf record budget of one forwardS_ng / forwardS1 call over rows x cols cells in a band of `width` (spdp_api.cpp)
+int64_t vmf_capacity(int64_t rows, int64_t cols, int64_t width, int64_t scale);
+
+// descriptors + work buffers of one run of one engine (RunFlavour) over a DevStore
+struct ItemShare;
 struct DevRun {
     SpdpContext* ctx = nullptr;
     SpdpContext* use_ctx = nullptr;         // set before build: the lane to run on (default: the store's context)
     const DevStore* store = nullptr;
-    int flavour = 0, n = 0;
+    RunFlavour flavour = RUN_WIP_SCORE;
+    int n = 0;
     int n_multi = 0;                        // leading problems run as multi-wave pipelines
     int wpb = 4;                            // waves per block of the sweep launch (16: one huge problem per CU)
     int cross_g = 0;                        // > 0: every problem spread over this many 16-wave blocks (CUs)
     bool fp_ok = false;                     // scores stay inside the exact fp32 range: spdp_sweep_fp.hip may run it
     void* d_gprog = nullptr;                // progress / barrier words of the cross-CU pipelines
-    bool cut = false;                       // flavour 3 with cut ranges on every item (set by build)
+    bool cut = false;                       // RUN_A0_FORWARD with cut ranges on every item (set by build)
     TilePipe pipe;                          // -A0 tiles / -A1 stripes of a problem as separate waves: shares POOL_GPROG with d_gprog
     int max_n_im = 0, max_skl = 0;
     int64_t total_cells = 0, tb_bytes = 0;
@@ -414,7 +457,7 @@ struct DevRun {
     std::vector<int> order;                 // dispatch slot -> caller index
     void *d_probs = nullptr, *d_bnd = nullptr, *d_tb = nullptr, *d_imd = nullptr, *d_res = nullptr,
          *d_skl = nullptr, *d_nskl = nullptr, *d_cpos = nullptr,
-         *d_ranges = nullptr, *d_scores = nullptr;         // all owned by ctx->pool[flavour]
+         *d_ranges = nullptr, *d_scores = nullptr;         // all owned by pool()
     int skl_cap = 0;
     float kernel_ms = 0.f;
     bool side = false;                      // run on ctx->stream2 (set before build)
@@ -424,18 +467,31 @@ struct DevRun {
     hipStream_t strm() const { return side ? ctx->stream2 : ctx->stream; }
     hipEvent_t evb() const { return side ? ctx->ev2 : ctx->ev0; }
     hipEvent_t eve() const { return side ? ctx->ev3 : ctx->ev1; }
-    DevRun() = default;
+    explicit DevRun(SpdpContext* lane = nullptr) : use_ctx(lane) {}
     DevRun(const DevRun&) = delete;
     DevRun& operator=(const DevRun&) = delete;
     ~DevRun() { release(); }
-    int build(const DevStore* st, const std::vector<RunItem>& items, int flav);
-    int launch();                       // async on ctx->stream: sweep (+ walk / cpos)
+    const RunTraits& traits() const { return RUN_TRAITS[flavour]; }
+    DevPool& pool() const { return ctx->pool[side ? SIDE_POOL : traits().pool]; }
+    void* take(int slot, size_t bytes);                         // pool().get, or null with ctx->err set
+    int cpos_stride() const { return 10 * (max_n_im + 1); }     // ints of a problem's cpos output: max_n_im + 1 Dim10 rows
+    int build(const DevStore* st, const std::vector<RunItem>& items, RunFlavour flav);
+    // the steps of build(), in its order
+    int check();
+    int lay_out(const std::vector<RunItem>& items, ItemShare& tot);
+    int allocate(const ItemShare& tot);
+    void sort_dispatch(bool may_multi);
+    int plan_blocks(bool may_multi);    // n_multi, wpb, cross_g and the gprog words
+    int plan_pipe();
+    int launch();                       // async on ctx->stream: launch_sweep (+ walk) or launch_scalar, then the link walk (cpos_args)
+    int launch_sweep(), launch_scalar();
+    CposArgs cpos_args(int strict, int local, const int* pipe_words) const;
     int sync();                         // waits, fills kernel_ms
     int fetch_results(std::vector<DevResult>& out);
     // forward: records of problem i are skl[off[i] .. off[i] + n_skl[i])
     int fetch_skl(std::vector<int>& n_skl, std::vector<int64_t>& off, std::vector<SpdpSkl>& skl);
     int fetch_udh(std::vector<int32_t>& scores, std::vector<int32_t>& cpos, std::vector<int32_t>& ranges,
-                  std::vector<int32_t>* edge = nullptr);     // edge: CposArgs::edge per problem (flavours 2, 8, 9), zeros otherwise
+                  std::vector<int32_t>* edge = nullptr);     // edge: CposArgs::edge per problem (RunTraits::edge), zeros otherwise
     void release();
 };
 

@@ -23,7 +23,6 @@
         }                                                                                \
     } while (0)
 
-enum { R_POOL = 7 };
 enum { RP_PROBS = 0, RP_SKL, RP_SOFF, RP_SCNT, RP_ROFF, RP_HDR, RP_REC };
 
 // the rescoring walk over a batch; `out` (records of spdp_skl_rng_s) and `edits` (format != 0: spdp_skl_edits_s) may each be null
