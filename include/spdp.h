@@ -941,9 +941,10 @@ int spdp_blk_index_write(const SpdpBlkIndexHost* h, const char* path);
  * positions 1-based on the forward strand, left > right on the reverse strand: Seq::SiteNo, src/seq.h).
  * One call = spdp_blk_find + one batched signal launch + one seeded call + one rescoring call per chunk of loci.
  * ori = a->inex.ori as spaln_job sets it (src/spaln.cc:1153-1156): 1 = the query as given (-S1), 3 = both orientations (the
- * default for a cDNA without a poly-A tail: alignS_ng(.., 3) -- the walk on the pair as given and on the reverse-complemented
- * query against the other strand of the locus, both with Exinon::both_ori signals; the reverse one stays only if it scores
- * strictly higher). */
+ * program's default for every cDNA, q_mns = 3: PolyA::rmpolyA returns 3 then whatever tail it finds; alignS_ng(.., 3) -- the
+ * walk on the pair as given and on the reverse-complemented query against the other strand of the locus, both with
+ * Exinon::both_ori signals; the reverse one stays only if it scores strictly higher).  These entries take the queries as they
+ * are: no tail is looked for.  spdp_map_align_s_prep (below, "query preparation") does what the program does first. */
 typedef struct SpdpMapExon { int32_t q_left, q_right, g_left, g_right; } SpdpMapExon;
 typedef struct SpdpMapGene {
     int32_t chr, rvs;                /* -1 / 0 when the query has no alignment; rvs: the strand the gene lies on              */
@@ -1007,6 +1008,51 @@ int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpB
                            const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
                            const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
                            int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds);
+
+/* ---- query preparation: poly-A tails, poly-T heads and the orientation of a cDNA query ---------------------------------------
+ * What spaln_job does to every cDNA query before the block search (src/spaln.cc:1154-1166): PolyA::rmpolyA (src/seq.cc:1402-1456).
+ * A poly-A tail is scored from the 3' end, a poly-T head from the 5' end (+1 for the base, -5 for anything else); of each the best
+ * position whose score exceeds polya_thr is remembered, and a scan ends once its score has fallen more than polya_thr below its
+ * best.  The better of the two stays, the A tail on ties.  An A tail sets tlen and clips right to it.  A T head clips left, and
+ * the query is reverse-complemented IN PLACE (ambiguity codes as complcod turns them): it goes on as its own sense strand with an
+ * A tail, its range mirrored (Seq::rev_attr).
+ *   q_mns      1 or 3, as -S sets it (1: the query as given, no T head is looked for; 3: the default).  2 is refused.  The
+ *              program also forces 1 for a query that carries intron positions (Seq::sigII); the library has no such queries.
+ *   polya_thr  PolyA::thr: 12 is the program's default (-pa#); <= 0: no scan, every record says "no tail".
+ * The record of a query holds the values as they stand AFTER normalisation: pol 0 = no tail, 1 = A tail, 2 = T head (the codes
+ * have been reverse-complemented); tlen; left (always 0) and right (= tlen); ori = rmpolyA's return value, the orientation the
+ * aligner is called with (= q_mns).  The T-head quirk of the program is kept: the last T of the head stays inside the range. */
+typedef struct SpdpQueryPrep { int32_t q_mns; int32_t polya_thr; } SpdpQueryPrep;
+typedef struct SpdpQueryTail { int32_t pol, tlen, left, right, ori; int32_t reserved[3]; } SpdpQueryTail;
+/* the rule in its sequential form, on the host (no device, no context): what the device entries are held to.  codes_out (may be
+ * NULL, may be codes): the normalised codes, laid out by offs as codes is.  0, or -1 (a refused prep, a null argument). */
+int spdp_polya_scan_host(const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
+                         SpdpQueryTail* tails, uint8_t* codes_out);
+/* the device form (spdp_polya.hip: one wave per query, both scans as chunked wave scans): upload, kernel, download */
+int spdp_polya_scan(SpdpContext* ctx, const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
+                    SpdpQueryTail* tails, uint8_t* codes_out, float* kernel_ms);
+/* ... on queries that lie on the device (the layout spdp_blk_vote_resident takes: d_offs[0] = 0): d_codes is normalised in place,
+ * the records stay on the device (d_tails: n records).  Without kernel_ms the call does not wait: work queued on the context
+ * afterwards reads the normalised queries. */
+int spdp_polya_scan_resident(SpdpContext* ctx, uint8_t* d_codes, const int64_t* d_offs, int32_t n, const SpdpQueryPrep* prep,
+                             SpdpQueryTail* d_tails, float* kernel_ms);
+/* spdp_map_align_s / _multi with the preparation in front: `spaln -Q7 genome query.fa` on queries as a FASTA file holds them.
+ * prep replaces ori (NULL is refused); tails (may be NULL): the n records.  The block search, the signals and the walks read
+ * the normalised queries in the records' ranges; the forward extension of an HSP ends at tlen (Wlp::eval, src/wln.cc:367, 394),
+ * on the reverse leg of ori = 3 too, where the program copies tlen unchanged (Seq::copyseq, src/seq.cc:1123) and the bound thus
+ * cuts the transcript's end; exon positions are those of the query AS GIVEN, as -O4 prints them (descending for a T-head query
+ * aligned as normalised, ascending again when its reverse leg won).  q_rev keeps its meaning: the reverse leg of ori = 3 won.
+ * polya_thr <= 0: the results of spdp_map_align_s / _multi with ori = q_mns.  The group twins take no preparation yet. */
+int spdp_map_align_s_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                          const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                          const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                          const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
+                          SpdpMapGene* genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails);
+int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep, int32_t all_out,
+                                int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails);
 
 /* ---- device groups, continued ------------------------------------------------------------------------------------------ */
 /* the same sharding for the calls of the seeded path, rescoring and the block vote (rounds 3 / 4).  The HSP source of a

@@ -473,3 +473,166 @@ def map_align_h_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmod
     """spdp_map_align_h_multi: the same for protein queries against the translated index (arguments as map_align_h's)"""
     return _multi_call(index, "spdp_map_align_h_multi", genome_codes, chr_off,
                        (C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rescore)), queries, (int(bool(all_out)),))
+
+
+# ---- query preparation (include/spdp.h "query preparation"): poly-A tails, poly-T heads, the orientation of a cDNA query
+class QueryPrep(C.Structure):            # SpdpQueryPrep
+    _fields_ = [("q_mns", C.c_int32), ("polya_thr", C.c_int32)]
+
+
+class QueryTail(C.Structure):            # SpdpQueryTail
+    _fields_ = [(k, C.c_int32) for k in ("pol", "tlen", "left", "right", "ori")] + [("reserved", C.c_int32 * 3)]
+
+
+TAIL_FIELDS = ("pol", "tlen", "left", "right", "ori")
+
+
+def _packed(queries, lead: int = 0):
+    """the queries one behind the other, `lead` bytes in front of the first: (codes, offs)"""
+    n = len(queries)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    offs[0] = lead
+    offs[1:] = lead + np.cumsum([len(q) for q in queries], dtype=np.int64)
+    codes = np.zeros(int(offs[n]), dtype=np.uint8)
+    if n:
+        codes[lead:] = np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries])
+    return codes, offs
+
+
+def _tails_out(tails, codes_out, offs, n):
+    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
+    return rec, [codes_out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)]
+
+
+def _hip_runtime():
+    """the HIP runtime this process has loaded with the library (not a second one)"""
+    for ln in open("/proc/self/maps"):
+        if "libamdhip64" in ln:
+            hip = C.CDLL(ln.split()[-1])
+            hip.hipMalloc.argtypes = [C.c_void_p, C.c_size_t]
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            hip.hipFree.argtypes = [C.c_void_p]
+            return hip
+    raise RuntimeError("the HIP runtime is not loaded: create an Engine first")
+
+
+def polya_scan_host(lib, queries, q_mns: int = 3, polya_thr: int = 12, lead: int = 0):
+    """spdp_polya_scan_host: PolyA::rmpolyA in its sequential form, no device.  Returns (records as an (n, 5) int32 array of
+    pol, tlen, left, right, ori; the normalised queries)."""
+    n = len(queries)
+    codes, offs = _packed(queries, lead)
+    prep = QueryPrep(int(q_mns), int(polya_thr))
+    tails = (QueryTail * max(n, 1))()
+    out = np.full(codes.size, 255, dtype=np.uint8)
+    lib.spdp_polya_scan_host.restype = C.c_int
+    lib.spdp_polya_scan_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if lib.spdp_polya_scan_host(codes.ctypes.data, offs.ctypes.data, n, C.byref(prep), tails, out.ctypes.data):
+        raise RuntimeError("spdp_polya_scan_host: refused (q_mns must be 1 or 3)")
+    return _tails_out(tails, out, offs, n)
+
+
+def polya_scan(eng, queries, q_mns: int = 3, polya_thr: int = 12, lead: int = 0, resident: bool = False):
+    """spdp_polya_scan (resident: spdp_polya_scan_resident on device arrays made here): the device form.
+    Returns (records, the normalised queries, kernel ms)."""
+    lib = eng.lib
+    n = len(queries)
+    codes, offs = _packed(queries, lead)
+    prep = QueryPrep(int(q_mns), int(polya_thr))
+    ms = C.c_float()
+    if not resident:
+        tails = (QueryTail * max(n, 1))()
+        out = np.full(codes.size, 255, dtype=np.uint8)
+        lib.spdp_polya_scan.restype = C.c_int
+        lib.spdp_polya_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = lib.spdp_polya_scan(eng.ctx, codes.ctypes.data, offs.ctypes.data, n, C.byref(prep), tails, out.ctypes.data, C.byref(ms))
+        eng._check(rc, "spdp_polya_scan")
+        return _tails_out(tails, out, offs, n) + (ms.value,)
+    # device arrays of the caller's own, through the HIP runtime the library is linked with
+    hip = _hip_runtime()
+    bufs = [C.c_void_p() for _ in range(3)]
+    sizes = (max(codes.size, 16), offs.size * 8, max(n, 1) * C.sizeof(QueryTail))
+    try:
+        for b, sz in zip(bufs, sizes):
+            if hip.hipMalloc(C.byref(b), C.c_size_t(sz)):
+                raise RuntimeError("hipMalloc failed")
+        if hip.hipMemcpy(bufs[0], codes.ctypes.data, C.c_size_t(codes.size), 1) or hip.hipMemcpy(bufs[1], offs.ctypes.data, C.c_size_t(offs.size * 8), 1):
+            raise RuntimeError("hipMemcpy failed")
+        lib.spdp_polya_scan_resident.restype = C.c_int
+        lib.spdp_polya_scan_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = lib.spdp_polya_scan_resident(eng.ctx, bufs[0], bufs[1], n, C.byref(prep), bufs[2], C.byref(ms))
+        eng._check(rc, "spdp_polya_scan_resident")
+        out = np.zeros(codes.size, dtype=np.uint8)
+        tails = (QueryTail * max(n, 1))()
+        if (codes.size and hip.hipMemcpy(out.ctypes.data, bufs[0], C.c_size_t(codes.size), 2)) or hip.hipMemcpy(tails, bufs[2], C.c_size_t(sizes[2]), 2):
+            raise RuntimeError("hipMemcpy failed")
+    finally:
+        for b in bufs:
+            if b:
+                hip.hipFree(b)
+    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
+    return rec, [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)], ms.value
+
+
+def _gene(G, exons):
+    ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
+          for j in range(G.n_exons)]
+    return dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex)
+
+
+def _prep_call(index, fn, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns, polya_thr, middle, outs):
+    """the inputs the two _prep entries share, the call, the records: middle = the integers between prep and the outputs"""
+    from . import abi
+    lib, eng = index.lib, index.eng
+    n = len(queries)
+    codes, offs = _packed(queries)
+    g = Genome()
+    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+    go = np.ascontiguousarray(chr_off, dtype=np.int64)
+    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
+    rp = abi.RescoreParams(*(int(x) for x in rescore))
+    prep = QueryPrep(int(q_mns), int(polya_thr))
+    tails = (QueryTail * max(n, 1))()
+    sec = (C.c_double * 4)()
+    f = getattr(lib, fn)
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_void_p] + [C.c_int32] * len(middle) + [C.c_void_p] * (len(outs) + 2)
+    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp),
+           codes.ctypes.data, offs.ctypes.data, n, C.byref(prep), *middle, *outs, sec, tails)
+    if rc < 0:
+        eng._check(rc, fn)
+    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
+    return list(sec), rc, rec
+
+
+def map_align_prep(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, q_mns: int = 3,
+                   polya_thr: int = 12):
+    """spdp_map_align_s_prep: map_align with PolyA::rmpolyA in front -- what `spaln -Q7` does to queries as a FASTA file holds
+    them.  Returns (genes as map_align's, seconds, return code, records as polya_scan's)."""
+    n = len(queries)
+    genes = (MapGene * max(n, 1))()
+    exons = C.POINTER(MapExon)()
+    sec, rc, rec = _prep_call(index, "spdp_map_align_s_prep", genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns, polya_thr,
+                              (), (genes, C.byref(exons)))
+    out = [None if genes[i].chr < 0 else _gene(genes[i], exons) for i in range(n)]
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(exons)
+    return out, sec, rc, rec
+
+
+def map_align_multi_prep(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries,
+                         q_mns: int = 3, polya_thr: int = 12, all_out: bool = False):
+    """spdp_map_align_s_multi_prep: map_align_multi with PolyA::rmpolyA in front.  Returns (lists as map_align_multi's, seconds,
+    return code, records as polya_scan's)."""
+    n = len(queries)
+    gene_off = np.zeros(n + 1, dtype=np.int64)
+    genes = C.POINTER(MapGene)()
+    exons = C.POINTER(MapExon)()
+    sec, rc, rec = _prep_call(index, "spdp_map_align_s_multi_prep", genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns,
+                              polya_thr, (int(bool(all_out)),), (gene_off.ctypes.data, C.byref(genes), C.byref(exons)))
+    out = [[_gene(genes[k], exons) for k in range(int(gene_off[i]), int(gene_off[i + 1]))] for i in range(n)]
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(genes)
+    libc.free(exons)
+    return out, sec, rc, rec

@@ -278,6 +278,7 @@ struct HspBatch {                                       // what a call's searche
     SpdpContext* ctx; SpdpBlkIndex* ix; const SpdpGenome* genome; const SpdpWilipModel* model; const SpdpScoring* sc;
     const spdp_loci::Params* P;
     const uint8_t* codes; const int64_t* offs; const int32_t* left; const int32_t* right;       // the call's queries (host)
+    const int32_t* tlen;                                // per query Seq::tlen, or null: the queries' lengths
     uint8_t* d_codes = nullptr;
     ~HspBatch() { if (d_codes) (void) hipFree(d_codes); }
 
@@ -317,7 +318,7 @@ struct HspBatch {                                       // what a call's searche
         spdp_region::materialize(genome->codes, genome->chr_off, t.r.chr, t.r.base, t.r.len, t.r.rvs != 0, P->bbt == 3, reg);
         const int a_len = (int) (offs[q + 1] - offs[q]);
         const spdp_hsp::Seqs s = {codes + offs[q], a_len, left[q], right[q], P->a_exgl, P->a_exgr, reg.data(), t.r.len, 0, t.r.len,
-                                  P->bbt == 3 ? 3 : 1, nullptr, nullptr, nullptr};
+                                  P->bbt == 3 ? 3 : 1, nullptr, nullptr, nullptr, tlen ? tlen[q] : -1};
         const spdp_hsp::GapCosts gc = {sc->intpen, sc->intpen_len, sc->gop, sc->gep, sc->lgop, sc->lgep, sc->codonk1};
         spdp_hsp::search(model, s, gc, -1, t.units);
     }
@@ -333,7 +334,7 @@ struct HspBatch {                                       // what a call's searche
             HspTask& T = ht[k];
             T.a_off = offs[q] - offs[0]; T.a_len = (int32_t) (offs[q + 1] - offs[q]); T.a_left = left[q]; T.a_right = right[q];
             T.g_off = genome->chr_off[tasks[k].r.chr] + tasks[k].r.base; T.b_len = tasks[k].r.len; T.rvs = tasks[k].r.rvs;
-            T.a_exgl = P->a_exgl; T.a_exgr = P->a_exgr; T.pad = 0;
+            T.a_exgl = P->a_exgl; T.a_exgr = P->a_exgr; T.a_tlen = tlen ? tlen[q] : T.a_len;
             longest = std::max(longest, T.a_right - T.a_left);
         }
         HspArgs A;
@@ -383,7 +384,7 @@ struct HspBatch {                                       // what a call's searche
 
 static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                     const SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
-                    const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                    const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, const int32_t* tlen, int32_t n,
                     SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status)
 {
     SpdpBlkIndex* ix = const_cast<SpdpBlkIndex*>(cix);
@@ -398,7 +399,7 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
     const spdp_loci::Chromosomes G = {genome->chr_off, genome->n_chr, hix->chr};
     const spdp_loci::RandomScore rnd = {hix->rscrtab, hix->rbscoef, hix->rbscons, hix->gdb};
     (void) hipSetDevice(ctx->device);
-    HspBatch B = {ctx, ix, genome, model, sc, &P, codes, offs, left, right};
+    HspBatch B = {ctx, ix, genome, model, sc, &P, codes, offs, left, right, tlen};
     if (B.prepare(n)) return -1;
     int out_cap = 4096;                                 // (a record that does not fit makes the round run again with room for it)
     const bool verbose = getenv("SPDP_FIND_VERBOSE") != nullptr;
@@ -524,9 +525,10 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
     return 0;
 }
 
-extern "C" int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+// spdp_blk_find with Seq::tlen of every query (null: its length): the HSP searches end their forward extension there
+int spdp_blk_find_tlen(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                              const SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
-                             const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                             const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, const int32_t* tlen, int32_t n,
                              SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status)
 {
     if (!ctx) return -1;
@@ -538,7 +540,7 @@ extern "C" int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const Spd
     }
     if ((model->dvsp == 0) != (hix->drna != 0)) { ctx->err = "spdp_blk_find: the block table is incompatible with the query type (src/blksrc.cc:2186)"; return -1; }
     if (ix->ctx != ctx) { ctx->err = "spdp_blk_find: the index belongs to another context"; return -1; }
-    try { return blk_find(ctx, ix, hix, genome, model, sc, prm, codes, offs, left, right, n, loci, n_loci, hsps, status); }
+    try { return blk_find(ctx, ix, hix, genome, model, sc, prm, codes, offs, left, right, tlen, n, loci, n_loci, hsps, status); }
     catch (...) {                                       // (nothing of C++ crosses the C boundary; the worker threads have been joined)
         if (*loci) { free(*loci); *loci = nullptr; }
         if (*hsps) { free(*hsps); *hsps = nullptr; }
@@ -546,4 +548,12 @@ extern "C" int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const Spd
         ctx->err = "spdp_blk_find: out of host memory (or no thread could be started)";
         return -1;
     }
+}
+
+extern "C" int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                             const SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
+                             const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status)
+{
+    return spdp_blk_find_tlen(ctx, ix, hix, genome, model, sc, prm, codes, offs, left, right, nullptr, n, loci, n_loci, hsps, status);
 }

@@ -145,7 +145,7 @@ __device__ bool stretch_and_trim(const HspArgs& A, const HspTask& T, const Level
     const int b_stop = bbt == 3 ? B.len - 1 : B.len;
     const int from = as;
     int len = 0, nid = 0, best = scr, w_from = 0, w_len = 0, w_nid = 0, restart = 0;
-    while (++as < T.a_len && (bs += bbt) < b_stop) {
+    while (++as < T.a_tlen && (bs += bbt) < b_stop) {
         const int ca = a[as], cb = B.at(bs);
         if ((as >= a_end || bs >= b_end) && S.conv[ca & 31] != S.conv[cb & 31]) break;
         ++len;

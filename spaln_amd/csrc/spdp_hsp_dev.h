@@ -16,7 +16,7 @@ struct HspTask {
     int32_t a_len, a_left, a_right;     // the query and its active range
     int32_t b_len, rvs;                 // the region: b_len residues, read as the other strand when rvs
     int32_t a_exgl, a_exgr;             // free query ends (end bonuses)
-    int32_t pad;
+    int32_t a_tlen;                     // the transcript's length (Seq::tlen): the forward extension of an HSP ends there; a_len without a tail
 };
 
 struct HspArgs {

@@ -17,6 +17,7 @@ struct Seqs {                                           // the two sequences as 
     const uint8_t* b; int b_len, b_left, b_right;
     int bbt;                                            // 1: nucleotide query, 3: protein query against tron codes
     const int16_t* sigS; const int16_t* sigE; const int16_t* sigT;     // protein only: the Exinon's start / coding / stop signals by position, or null
+    int a_tlen = -1;                                    // Seq::tlen of a cDNA whose poly-A tail was found: the forward extension ends there; < 0: a_len
 };
 
 struct Search {
@@ -142,9 +143,9 @@ struct Search {
         }
         if (as < 0) bs -= bbt;
         const int a_end = std::min(jx + jlen, P->a_right), b_end = std::min(jy + bbt * jlen, P->b_right);
-        const int b_stop = prot ? P->b_len - 1 : P->b_len, from = as;
+        const int b_stop = prot ? P->b_len - 1 : P->b_len, from = as, a_stop = P->a_tlen >= 0 ? P->a_tlen : P->a_len;
         int len = 0, nid = 0, best = scr, w_from = 0, w_len = 0, w_nid = 0, restart = 0;
-        while (++as < P->a_len && (bs += bbt) < b_stop) {       // forwards: through the seed, then while the classes agree
+        while (++as < a_stop && (bs += bbt) < b_stop) {       // forwards: through the seed, then while the classes agree
             const int ca = P->a[as], cb = P->b[bs];
             if ((as >= a_end || bs >= b_end) && cls(ca) != cls(cb)) break;
             ++len;
@@ -156,7 +157,7 @@ struct Search {
         }
         jx += w_from; jy += bbt * w_from;
         if (M->crs == 0 && prot) scr -= std::min(w_len - w_nid, 3) * L.vthr;
-        if (as == P->a_len && exinon && sig(P->sigT, bb) > 0) scr += L.vthr / 2;
+        if (as == a_stop && exinon && sig(P->sigT, bb) > 0) scr += L.vthr / 2;
         else {
             const int rend = L.tpl - P->a_right + jx + w_len;
             if (P->a_exgr && rend > 0) scr += M->end_bonus * std::min(rend, L.tpl);

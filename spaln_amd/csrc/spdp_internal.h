@@ -336,6 +336,9 @@ struct SpdpContext {
     std::string err;
     std::vector<SpdpContext*> lanes;  // further lanes of this context (spdp_lane): chunks of a batch run side by side
     int64_t seed_stats[12] = {0};      // spdp_seeded_stats
+    // Seq::tlen of the problems of the seeded calls made while it is set (spdp_map_align_s_prep; problem i of spdp_align_s_seeded,
+    // forward problems then reverse ones of _ori3): the walks' own HSP searches end their forward extension there.  Null: a_len
+    const int32_t* seed_a_tlen = nullptr;
     std::vector<std::vector<SpdpPhaseMark>> seed_marks;    // spdp_seeded_phase_marks: per query of the last spdp_align_h_seeded call
     int64_t rerun_stats[2] = {0, 0};   // launches repeated because a cross-CU group / a tile pipeline gave up (spdp_rerun_stats)
     // launches of the `_wip` sweeps (the FAM_WIP flavours of DevRun::launch, repeats included): served by spdp_sweep_fp, served by

@@ -22,6 +22,11 @@
 #include <vector>
 
 int spdh_signals_run(SpdpContext* ctx, const SpdpSignalModelH* m, const std::vector<SigJobH>& jobs, SignalArgsH args, int pack);   // spdp_signals_api.cpp
+const char* spdp_prep_refused(const SpdpQueryPrep* prep);                                                                          // spdp_polya_api.cpp
+int spdp_blk_find_tlen(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,              // spdp_blk_api.cpp
+                       const SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
+                       const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, const int32_t* tlen, int32_t n,
+                       SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status);
 
 namespace {
 
@@ -181,11 +186,18 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
                                 const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
                                 const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
                                 const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                                const LocusSink& sink, double* seconds)
+                                const LocusSink& sink, double* seconds,
+                                const SpdpQueryPrep* prep = nullptr, bool prepares = false, SpdpQueryTail* tails_out = nullptr)
 {
     if (!ctx) return -1;
     if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
         ctx->err = "spdp_map_align_s: null argument"; return -1;
+    }
+    // the _prep entries: the orientation is the preparation's (rmpolyA returns q_mns for every query: 3 whatever it finds, 1 under
+    // -S1 where no T head is looked for -- so a batch never mixes orientations)
+    if (prepares) {
+        if (const char* why = spdp_prep_refused(prep)) { ctx->err = std::string("spdp_map_align_s_prep: ") + why; return -1; }
+        ori = prep->q_mns;
     }
     if (ori != 1 && ori != 3) { ctx->err = "spdp_map_align_s: ori must be 1 (the query as given) or 3 (both orientations)"; return -1; }
     if (!sp->wilip) { ctx->err = "spdp_map_align_s: SpdpSeedParams.wilip missing (the HSP searches of this call are the library's own)"; return -1; }
@@ -194,8 +206,25 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> ql(n, 0), qr(n);
     for (int i = 0; i < n; ++i) qr[i] = (int32_t) (offs[i + 1] - offs[i]);
+    // ---- the preparation (PolyA::rmpolyA, spdp_polya.hip): tails found, antisense queries turned; from here on `codes` are the
+    // normalised queries and every reader of a query's range or length takes them from its record
+    std::vector<SpdpQueryTail> tail;                    // empty: no preparation, or none that scans (polya_thr <= 0)
+    std::vector<uint8_t> normal;
+    std::vector<int32_t> qt;                            // Seq::tlen per query
+    if (prepares && prep->polya_thr > 0) {
+        tail.resize(n); normal.resize((size_t) offs[n]);
+        if (spdp_polya_scan(ctx, codes, offs, n, prep, tail.data(), normal.data(), nullptr)) return -1;
+        codes = normal.data();
+        qt.resize(n);
+        for (int i = 0; i < n; ++i) { ql[i] = tail[i].left; qr[i] = tail[i].right; qt[i] = tail[i].tlen; }
+        if (tails_out) memcpy(tails_out, tail.data(), sizeof(SpdpQueryTail) * (size_t) n);
+    } else if (prepares && tails_out && spdp_polya_scan_host(codes, offs, n, prep, tails_out, nullptr)) {
+        ctx->err = "spdp_map_align_s_prep: bad query offsets"; return -1;
+    }
+    const bool tailed = !tail.empty();
     SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
-    if (spdp_blk_find(ctx, ix, hix, genome, sp->wilip, sc, fprm, codes, offs, ql.data(), qr.data(), n, &loci, &n_loci, &hsps, nullptr)) return -1;
+    if (spdp_blk_find_tlen(ctx, ix, hix, genome, sp->wilip, sc, fprm, codes, offs, ql.data(), qr.data(), tailed ? qt.data() : nullptr, n,
+                           &loci, &n_loci, &hsps, nullptr)) return -1;
     struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
     sec[0] = since(t0);
 
@@ -292,6 +321,10 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             P.sig5 = sig5 + at[j]; P.sig3 = sig3 + at[j];
             P.cano5 = cano5 + at[j]; P.cano3 = cano3 + at[j]; P.dinc = dinc + at[j];
             P.a_left = 0; P.a_right = P.a_len; P.b_left = slot_left(j); P.b_right = slot_right(j);
+            if (tailed) {                               // (the reverse leg: Seq::comrev mirrors the range, Seq::rev_attr)
+                const SpdpQueryTail& t = tail[L.query];
+                P.a_left = j < m ? t.left : P.a_len - t.right; P.a_right = j < m ? t.right : P.a_len - t.left;
+            }
             P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
             if (j < m) { hl[k] = hsps + L.hsp_off; hn[k] = L.n_hsp; }
         }
@@ -300,8 +333,15 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         t0 = std::chrono::steady_clock::now();
         std::vector<SpdpAlignment> aln(m);
         std::vector<int32_t> orient(m, 0);
+        // Seq::tlen of every problem for the walks' own HSP searches; the reverse leg keeps the forward one's (alignS_ng turns the
+        // query in place, which leaves tlen alone: there the bound cuts the transcript's end, the tail sits at the front)
+        std::vector<int32_t> ptl;
+        if (tailed) { ptl.resize(ns); for (int j = 0; j < ns; ++j) ptl[j] = tail[loci[c0 + (j < m ? j : j - m)].query].tlen; }
+        struct TlenSet { SpdpContext* c; ~TlenSet() { c->seed_a_tlen = nullptr; } } tlen_set{ctx};
+        ctx->seed_a_tlen = tailed ? ptl.data() : nullptr;
         const int rc = both ? spdp_align_s_seeded_ori3(ctx, sc, &spx, probs.data(), probs.data() + m, m, hl.data(), hn.data(), low.data(), nullptr, aln.data(), orient.data())
                             : spdp_align_s_seeded(ctx, sc, &spx, probs.data(), m, hl.data(), hn.data(), low.data(), nullptr, aln.data());
+        ctx->seed_a_tlen = nullptr;
         if (rc < 0) return -1;
         if (both) for (int k = 0; k < m; ++k) if (orient[k]) probs[k] = probs[m + k];        // rescoring reads the pair that was aligned
         if (rc > 0) ++partial;
@@ -331,7 +371,10 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             for (int e = 0; e < res[k].n_exons; ++e) {
                 const SpdpExon& x = res[k].exons[e];
                 if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
-                if (orient[k]) ex.push_back({a_len - x.rleft, a_len - x.rright + 1, site(x.left), site(x.right - 1)});     // positions of the query as given
+                // positions of the query as given (Seq::SiteNo with inex.sens reversed): the reverse leg turned it, and so did the
+                // preparation of a query with a T head -- both: as given again
+                const bool turned = (orient[k] != 0) != (tailed && tail[L.query].pol == 2);
+                if (turned) ex.push_back({a_len - x.rleft, a_len - x.rright + 1, site(x.left), site(x.right - 1)});
                 else ex.push_back({x.rleft + 1, x.rright, site(x.left), site(x.right - 1)});
             }
             sink(L, std::move(o));
@@ -583,6 +626,53 @@ extern "C" int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, 
     }
     catch (const std::bad_alloc&) {
         ctx->err = "spdp_map_align_h_multi: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
+        return -1;
+    }
+}
+
+// ---- the cDNA entries with the query preparation in front (include/spdp.h "query preparation")
+extern "C" int spdp_map_align_s_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                     const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                     const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                     const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
+                                     SpdpMapGene* genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails)
+{
+    if (!ctx) return -1;
+    if (!genes || !exons) { ctx->err = "spdp_map_align_s_prep: null argument"; return -1; }
+    *exons = nullptr;
+    try {
+        BestSink best(std::max(n, 0));
+        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
+        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, 0, std::ref(best), seconds, prep, true, tails);
+        if (rc < 0 || n <= 0) return rc;
+        return best.finish(ctx, "spdp_map_align_s_prep", n, genes, exons) ? -1 : rc;
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = "spdp_map_align_s_prep: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
+        if (*exons) { free(*exons); *exons = nullptr; }
+        return -1;
+    }
+}
+
+extern "C" int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                           const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep, int32_t all_out,
+                                           int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails)
+{
+    if (!ctx) return -1;
+    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_s_multi_prep: null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr;
+    if (check_multi(ctx, "spdp_map_align_s_multi_prep", hix, fprm)) return -1;
+    try {
+        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
+        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, 0, std::ref(multi), seconds, prep, true, tails);
+        if (rc < 0) return rc;
+        return multi.finish(ctx, "spdp_map_align_s_multi_prep", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = "spdp_map_align_s_multi_prep: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
         free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
         return -1;
     }

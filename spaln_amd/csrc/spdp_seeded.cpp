@@ -88,6 +88,7 @@ struct DeviceBackend : DpBackend {
         return park(cut ? 2 : 1, s, w, cut, rec);      // (the cDNA engines have no intron switch)
     }
     const SpdpWilipModel* wm = nullptr; const SpdpProblem* prob = nullptr; const SpdpScoring* scp = nullptr; int codonk1 = 0;
+    int a_tlen = -1;                            // Seq::tlen of the query (SpdpContext::seed_a_tlen), < 0: its length
     bool wilip(int level, const Span& s, std::vector<Unit>& units) override
     {
         if ((!src || !src->units) && wm) {      // the library's own HSP search (spdp_hsp_host.h)
@@ -110,7 +111,7 @@ struct DeviceBackend : DpBackend {
     {
         {
             const spdp_hsp::Seqs pr = {prob->a, prob->a_len, s.al, s.ar, s.a_exgl, s.a_exgr, prob->b, prob->b_len, s.bl, s.br, 1,
-                                        nullptr, nullptr, nullptr};
+                                        nullptr, nullptr, nullptr, a_tlen};
             const spdp_hsp::GapCosts gc = {scp->intpen, scp->intpen_len, scp->gop, scp->gep, scp->lgop, scp->lgep, codonk1};
             std::vector<spdp_hsp::Unit> us;
             spdp_hsp::search(wm, pr, gc, level, us);
@@ -232,6 +233,7 @@ static int seeded_core(SpdpContext* ctx, const SpdpScoring* sc, const SpdpSeedPa
                 DeviceBackend be;
                 be.fiber = &fb; be.query = q; be.src = src; be.n_wilip = &n_wilip; be.ns_cb = &ns_cb;
                 be.wm = sp->wilip; be.prob = &probs[q]; be.scp = sc; be.codonk1 = sp->codonk1;       // (the walk's own GapPenalty reads it there)
+                be.a_tlen = ctx->seed_a_tlen ? ctx->seed_a_tlen[q] : -1;
                 if (two) { be.cache = &cache; be.pass = pass; be.slow = &is_slow; be.n_hit = &n_hit; be.n_miss = &n_miss; }
                 SeedWalk w;
                 const int nh = (hsps && n_hsps && hsps[q]) ? n_hsps[q] : 0;

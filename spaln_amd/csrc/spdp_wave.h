@@ -30,6 +30,19 @@ __device__ __forceinline__ int row_ror1(int src) { return __builtin_amdgcn_mov_d
 // lane k <- lane k - 1 of its 16-lane group (through LDS hardware: where the value is not wave-shaped enough for DPP)
 __device__ __forceinline__ int up16(int v) { return __shfl_up(v, 1, 16); }
 __device__ __forceinline__ int lane_id() { return (int) threadIdx.x; }      // (kernels of one wave per block)
+// inclusive scans over the 64 lanes of a wave; lane: the caller's lane in its wave
+__device__ __forceinline__ int wave_scan_add(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d); if (lane >= d) v += u; }
+    return v;
+}
+__device__ __forceinline__ int wave_scan_max(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d); if (lane >= d) v = max(v, u); }
+    return v;
+}
 
 // a problem record every lane has read from the same address: its words, said to be wave-uniform, live in SGPRs -- and so
 // does everything computed from them (ranges, array bases, loop bounds)

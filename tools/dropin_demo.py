@@ -64,7 +64,12 @@ def make_dataset(td, args):
             parts = []
             for k, g in enumerate(genes[c * per:(c + 1) * per]):
                 spacer = int(getattr(args, "spacer", 0) or 0)                     # (--spacer: a larger genome around the same genes)
-                parts += [synth.random_dna(rng, int(rng.integers(3000, 20000)) if not spacer else int(rng.integers(spacer // 2, spacer))), g.window]
+                window = g.window
+                planted = int(getattr(args, "planted_a", 0) or 0) if getattr(args, "tails", False) else 0
+                if planted and k % 3 == 0 and not args.protein:     # (--tails: A's behind the last exon, for an untrimmed tail to extend into)
+                    window = window.copy()
+                    window[g.exons[-1][1]:g.exons[-1][1] + planted] = ord("A")
+                parts += [synth.random_dna(rng, int(rng.integers(3000, 20000)) if not spacer else int(rng.integers(spacer // 2, spacer))), window]
                 if prng is not None:                          # cDNA: 4 - 10 % substitutions and some indels; protein: 5 %, no indels (ORFs stay)
                     copy = synth.mutate(prng, g.window, 0.05, 0.0) if args.protein else \
                         synth.mutate(prng, g.window, float(prng.choice([0.04, 0.07, 0.1])), 0.002)

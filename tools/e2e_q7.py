@@ -22,7 +22,18 @@ Several loci per query (`spaln -M N`; opt-in, the output without these flags is 
                 the library runs spdp_map_align_s_multi / _h_multi: every query's ORDERED list of printed loci and their exon
                 tables is compared (identical_locus_lists), and the best-only call is timed beside it
   --all-out     -pw: no output threshold
-  --paralogs    every gene of the genome twice, the copy diverged (some on the other strand): paralogs to report"""
+  --paralogs    every gene of the genome twice, the copy diverged (some on the other strand): paralogs to report
+
+Queries as a FASTA file of mRNAs and ESTs holds them (opt-in):
+  --tails       a third of the queries gets a poly-A tail of 13 - 40 residues (in half of them one other residue 14 or more
+                positions from the end, which the tail survives), a third gets a tail and is then reverse-complemented -- an
+                antisense read with a poly-T head (--ori 3; under --ori 1 it keeps the A tail), a third is left alone; behind the
+                last exon of every third gene the genome holds 20 A's (--planted-a), so that an untrimmed tail has something to
+                extend into.  The program is run as before; the library goes through spdp_map_align_s_prep (_multi_prep with
+                --max-out), which does what the program's PolyA::rmpolyA does first.  The JSON line adds `tails` (queries per
+                class), `tail_records_equal_host` (the records of the device scan against spdp_polya_scan_host) and
+                `untrimmed_differs`: the tailed queries whose table from the entry WITHOUT the preparation differs from the
+                program's."""
 import argparse
 import ctypes as C
 import json
@@ -124,6 +135,28 @@ def reference_loci(text):
 def loci_of(genes, chr_names):
     """a _multi entry's lists -> the layout of reference_loci"""
     return [[(chr_names[g["chr"]], "-" if g["rvs"] else "+", [tuple(e) for e in g["exons"]]) for g in lst] for lst in genes]
+
+
+def add_tails(path, ori):
+    """--tails: q.fa rewritten in place; -> per query its class (0: A tail, 1: T head -- an A tail under ori 1 --, 2: as it was)"""
+    rng = np.random.default_rng(20261402)
+    lines = open(path).read().split("\n")
+    comp = str.maketrans("ACGTacgt", "TGCAtgca")
+    cls = []
+    for k, i in enumerate(range(1, len(lines), 2)):
+        if not lines[i]:
+            continue
+        cls.append(k % 3)
+        if k % 3 == 2:
+            continue
+        n = int(rng.integers(13, 41))
+        tail = ["A"] * n
+        if int(rng.integers(0, 2)) and n >= 16:                 # one other residue, 14 or more A's behind it
+            tail[int(rng.integers(0, n - 14))] = "CGT"[int(rng.integers(0, 3))]
+        seq = lines[i] + "".join(tail)
+        lines[i] = seq.translate(comp)[::-1] if k % 3 == 1 and ori == 3 else seq
+    open(path, "w").write("\n".join(lines))
+    return cls
 
 
 def multi_opts(args):
@@ -288,18 +321,25 @@ def main():
                     help="N > 0: spaln -M N against spdp_map_align_s_multi / _h_multi -- every query's ordered list of loci is compared")
     ap.add_argument("--all-out", action="store_true", help="with --max-out: -pw (no output threshold) for both programs")
     ap.add_argument("--paralogs", action="store_true", help="every gene of the genome twice, the copy diverged")
+    ap.add_argument("--tails", action="store_true", help="poly-A tails and poly-T heads on two thirds of the queries; the library prepares them (spdp_map_align_s_prep)")
+    ap.add_argument("--prep", action="store_true", help="the library goes through spdp_map_align_s_prep on the queries as they are (--tails implies it)")
+    ap.add_argument("--planted-a", type=int, default=20, help="with --tails: the A's in the genome behind the last exon of every third gene")
     ap.add_argument("--dump-diff", default="", help="write the queries whose exon tables differ (name, both tables, the library's gene record) to this JSON file")
     args = ap.parse_args()
     if args.all_out and not args.max_out:
         ap.error("--all-out needs --max-out")
     if args.max_out and args.members > 1:
         ap.error("--max-out runs on one context (--members 1)")
+    args.prep = args.prep or args.tails
+    if args.prep and (args.protein or args.members > 1):
+        ap.error("--tails / --prep: cDNA queries on one context")
     if args.protein:
         return main_protein(args)
     t_all = time.perf_counter()
     with tempfile.TemporaryDirectory(prefix="spdp_e2e_") as td:
         genome_nt, env = dropin_demo.make_dataset(td, args)
-        if args.ori == 3:                                        # antisense reads among the queries
+        tail_cls = add_tails(os.path.join(td, "q.fa"), args.ori) if args.tails else None
+        if args.ori == 3 and not args.tails:                     # antisense reads among the queries (--tails: its T-head third)
             lines = open(os.path.join(td, "q.fa")).read().split("\n")
             comp = str.maketrans("ACGTacgt", "TGCAtgca")
             for i in range(2, len(lines) - 1, 4):
@@ -341,10 +381,35 @@ def main():
         sp.wilip = C.addressof(model)
         fs = fq["rng_fstat_A0"] if "rng_fstat_A0" in fq else [0, 0, 0, 0, 0, 0, 3, 1]
         rescore = (fq["prm"]["codonk1"], minl, int(fs[6]), int(fs[7]))
+        tail_out = {}
+
+        def tail_fields(recs, old_tables):
+            """--tails: the three fields of the JSON line; old_tables: per query name what the entry without the preparation gave"""
+            host, _ = blocks.polya_scan_host(lib, queries, args.ori, 12)
+            tailed = [q_names[i] for i, c in enumerate(tail_cls) if c != 2]
+            return {"tails": {"a_tail": sum(1 for c in tail_cls if c == 0 or (c == 1 and args.ori == 1)),
+                              "t_head": sum(1 for c in tail_cls if c == 1 and args.ori == 3), "none": sum(1 for c in tail_cls if c == 2),
+                              "records": {"none": int((recs[:, 0] == 0).sum()), "a_tail": int((recs[:, 0] == 1).sum()), "t_head": int((recs[:, 0] == 2).sum())}},
+                    "tail_records_equal_host": bool(np.array_equal(recs, host)),
+                    "untrimmed_differs": sum(1 for k in tailed if old_tables.get(k) != want_of(k))}
         if args.max_out:
-            multi = lambda: blocks.map_align_multi(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori, all_out=args.all_out)  # noqa: E731
-            best = lambda: blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)  # noqa: E731
+            if args.prep:
+                def multi():
+                    lists, phases, rc, recs = blocks.map_align_multi_prep(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, q_mns=args.ori,
+                                                                          polya_thr=12, all_out=args.all_out)
+                    tail_out["recs"] = recs
+                    return lists, phases, rc
+                best = lambda: blocks.map_align_prep(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, q_mns=args.ori, polya_thr=12)  # noqa: E731
+            else:
+                multi = lambda: blocks.map_align_multi(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori, all_out=args.all_out)  # noqa: E731
+                best = lambda: blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)  # noqa: E731
             out = run_multi(args, r.stdout, q_names, chr_names, multi, best, load_s)
+            if args.tails:
+                wl = reference_loci(r.stdout)
+                want_of = lambda k: wl.get(k)  # noqa: E731
+                old, _, _ = blocks.map_align_multi(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori, all_out=args.all_out)
+                out.update(tail_fields(tail_out["recs"], {q_names[i]: v for i, v in enumerate(loci_of(old, chr_names)) if v}))
+                out["identical_exon_tables"] = out["identical_locus_lists"]
             out.update({"what": "every locus `spaln -Q7 %s-O4 -M%d%s` prints against spdp_map_align_s_multi" % ("-S1 " if args.ori == 1 else "", args.max_out,
                                                                                                              " -pw" if args.all_out else ""),
                         "ori": args.ori, "genome_nt": genome_nt, "reference_wall_s": round(ref_s, 2), "reference_threads": args.threads,
@@ -400,7 +465,11 @@ def main():
             grp.close()
         for _ in range(0 if args.members > 1 else 2):
             t0 = time.perf_counter()
-            genes, phases, rc = blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)
+            if args.prep:
+                genes, phases, rc, tail_out["recs"] = blocks.map_align_prep(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, q_mns=args.ori,
+                                                                            polya_thr=12)
+            else:
+                genes, phases, rc = blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)
             runs.append((time.perf_counter() - t0, phases))
         lib_s, phases = runs[-1]
         got = {q_names[i]: g["exons"] for i, g in enumerate(genes) if g is not None}
@@ -414,7 +483,7 @@ def main():
             gi = {q_names[i]: g for i, g in enumerate(genes)}
             json.dump([{"name": k, "reference": want[k], "library": gi.get(k)} for k in diff], open(args.dump_diff, "w"), indent=1)
         out = {"what": "block search -> HSPs -> seeded alignment -> exon table inside the library against `spaln -Q7 %s-O4`" % ("-S1 " if args.ori == 1 else ""),
-               "queries": args.queries, "fragment_nt": args.frag or None, "ori": args.ori, "members": args.members, "query_reversed": sum(1 for g in genes if g is not None and g["q_rev"]), "genome_nt": genome_nt, "reference_aligned": len(want), "library_aligned": len(got),
+               "queries": args.queries, "fragment_nt": args.frag or None, "ori": args.ori, "entry": "spdp_map_align_s_prep" if args.prep else "spdp_map_align_s", "members": args.members, "query_reversed": sum(1 for g in genes if g is not None and g["q_rev"]), "genome_nt": genome_nt, "reference_aligned": len(want), "library_aligned": len(got),
                "identical_exon_tables": n_same, "different": len(diff),
                "reference_wall_s": round(ref_s, 2), "reference_threads": args.threads,
                "reference_queries_per_s": round(len(want) / ref_s, 1),
@@ -426,6 +495,10 @@ def main():
                "loci_aligned": n_loci, "return_code": rc, "wall_s": round(time.perf_counter() - t_all, 1),
                "note": "reference wall = its whole process (index + genome read, 16 threads); library = index + genome load "
                        "+ ONE spdp_map_align_s call on a warm context (the first call of the context beside it)"}
+        if args.tails:
+            want_of = lambda k: want.get(k)  # noqa: E731
+            old, _, _ = blocks.map_align(dix, gen, off, sc, sp, sigmodel, prm, rescore, queries, ori=args.ori)
+            out.update(tail_fields(tail_out["recs"], {q_names[i]: g["exons"] for i, g in enumerate(old) if g is not None}))
         print(json.dumps(out))
         dix.free()
         eng.close()
