@@ -322,6 +322,19 @@ void spdp_rerun_stats(SpdpContext* ctx, int64_t* out, int reset);
  * laid out as cross-CU pass groups, out[3] as 16-wave blocks (with or without groups).  For tests and diagnosis: which
  * kernel and which geometry a call really used. */
 void spdp_sweep_stats(SpdpContext* ctx, int64_t out[4], int reset);
+/* the chunk pipeline of the align calls on this context since the last reset (a big batch runs as chunks whose linear-space
+ * sweeps follow each other on the GPU): out[0] calls, out[1] chunks, then how the gates between consecutive chunks were
+ * opened: out[2] by the sweep's "all blocks started" signal (the next sweep is launched at once), out[3] by the event behind
+ * the sweep (the next sweep waits for it on the device), out[4] with nothing to wait for (the chunk had no linear-space round,
+ * or failed); out[5] gates opened exactly once (every request to open counts, but for the "nothing to wait for" a chunk ends
+ * with on a gate it has opened before).  After a sound call out[2] + out[3] + out[4] = out[5] = out[1] - out[0]. */
+void spdp_chunk_stats(SpdpContext* ctx, int64_t out[6], int reset);
+/* How a batch of n problems is cut into chunks (host only, no device work): cells[i] = DP cells of problem i (spdp_cells).
+ * Chunks are contiguous in caller order; chunk c + 1 is meant to hold `ratio` (0 < ratio <= 1) times the cells of chunk c,
+ * no chunk holds fewer than max(64, min_chunk) problems, and there are at most max_chunks of them (fewer where the problems
+ * do not allow it: a later chunk never holds more cells than the one before it by more than the batch's largest problem).
+ * bounds[] needs max_chunks + 1 entries; chunk c = problems bounds[c] .. bounds[c + 1] - 1.  Returns the number of chunks. */
+int spdp_chunk_plan(const int64_t* cells, int n, int max_chunks, double ratio, int min_chunk, int* bounds);
 
 /* stdskl (m_unit 1) / stdskl3 (m_unit 3), src/gaps.cc:140-227: corner list of n path records in any order;
  * out[] needs 2 n + 1 entries, returns the number written.  Host only (no device work). */

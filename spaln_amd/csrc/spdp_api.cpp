@@ -172,6 +172,8 @@ void spdp_destroy(SpdpContext* ctx)
     (void) hipSetDevice(ctx->device);
     for (DevPool& p : ctx->pool) p.release();
     for (int k = 0; k < 3; ++k) if (ctx->stage_ptr[k]) (void) hipHostFree(ctx->stage_ptr[k]);
+    if (ctx->d_started) (void) hipFree(ctx->d_started);
+    if (ctx->sig_host) (void) hipHostFree(ctx->sig_host);
     (void) hipEventDestroy(ctx->ev0);
     (void) hipEventDestroy(ctx->ev1);
     (void) hipEventDestroy(ctx->ev2);
@@ -179,6 +181,19 @@ void spdp_destroy(SpdpContext* ctx)
     if (ctx->stream2) (void) hipStreamDestroy(ctx->stream2);
     (void) hipStreamDestroy(ctx->stream);
     delete ctx;
+}
+
+int SpdpContext::start_signal()
+{
+    SpdpContext* ctx = this;
+    if (d_started && sig_host_dev) return 0;
+    if (!d_started) HIPCHK(hipMalloc((void**) &d_started, 256));
+    if (!sig_host) {
+        HIPCHK(hipHostMalloc((void**) &sig_host, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        *sig_host = 0;
+    }
+    HIPCHK(hipHostGetDevicePointer((void**) &sig_host_dev, sig_host, 0));
+    return 0;
 }
 
 void* SpdpContext::staging(int k, size_t bytes)
@@ -800,6 +815,16 @@ int DevRun::launch_sweep()
     A.a_codes = (const uint8_t*) store->d_a; A.cols = (const int2*) store->d_cols; A.bnd = (int*) d_bnd;
     A.tb = (uint8_t*) d_tb; A.imd = (int*) d_imd; A.res = (DevResult*) d_res; A.n_multi = n_multi;
     A.cross_g = cross_g; A.gprog = (int*) d_gprog;
+    // the start signal rides on the plain 4-wave launch of the linear-space sweep only (cooperative and 16-wave launches,
+    // and every other flavour, leave the pointers null: those kernels do not look at them)
+    A.started = nullptr; A.started_host = nullptr;
+    signal_armed = signal_start && flavour == RUN_WIP_UDH && cross_g == 0 && wpb == 4 && !store->sc.local;
+    if (signal_armed) {
+        if (ctx->start_signal()) return -1;
+        HIPCHK(hipMemsetAsync(ctx->d_started, 0, sizeof(unsigned), strm()));
+        __atomic_store_n(ctx->sig_host, 0, __ATOMIC_RELEASE);
+        A.started = ctx->d_started; A.started_host = ctx->sig_host_dev;
+    }
     int grid = cross_g > 0 ? n * cross_g : n_multi + (n - n_multi + wpb - 1) / wpb;
     if (cross_g > 0 && getenv("SPDP_CROSS_TEST_SHORT")) --grid;    // test hook: one block never arrives -> the fallback runs
     HIPCHK(hipEventRecord(evb(), strm()));
@@ -847,6 +872,12 @@ extern "C" void spdp_sweep_stats(SpdpContext* ctx, int64_t* out, int reset)
         for (SpdpContext* l : ctx->lanes)                   // chunks of a batch run on the context's lanes
             out[k] += reset ? l->sweep_stats[k].exchange(0) : l->sweep_stats[k].load();
     }
+}
+
+extern "C" void spdp_chunk_stats(SpdpContext* ctx, int64_t* out, int reset)
+{
+    if (!ctx || !out) return;
+    for (int k = 0; k < 6; ++k) out[k] = reset ? ctx->chunk_stats[k].exchange(0) : ctx->chunk_stats[k].load();
 }
 
 int DevRun::sync()

@@ -29,6 +29,7 @@
 #include <thread>
 
 #include "spdp_internal.h"
+#include "spdp_chunk_plan.h"
 
 namespace {
 
@@ -172,17 +173,36 @@ void trim_skl(std::vector<SpdpSkl>& s, const SpdpProblem& p)
 void trim_skl_of(std::vector<SpdpSkl>& s, const SpdpProblem& p) { trim_skl(s, p); }
 namespace {
 
-// Chunks of one batch run as a software pipeline on lanes of the context (own streams and pools): chunk c starts
+// Chunks of one batch run as a software pipeline on two lanes of the context (own streams and pools): chunk c starts
 // its first linear-space sweep when that of chunk c - 1 has finished, so the host work, the slab tracebacks and the
 // walk of one chunk run beside the big sweep of the next instead of leaving the GPU idle between launches.
+// "Has finished" is stricter than needed: once every block of chunk c - 1's sweep has STARTED (SweepArgs::started), the
+// next sweep can be launched with no dependency at all -- its blocks take the slots the last blocks of the sweep before
+// it leave, where a wait for the event drains the GPU first.  The chunk's thread sees that signal in host memory and
+// opens the gate with GATE_LAUNCH_NOW; a launch that cannot carry the signal, or whose signal was not seen before
+// the sweep ended, opens it with GATE_EVENT as before.
+enum GateState : int { GATE_SHUT = 0, GATE_EVENT = 1, GATE_NONE = 2, GATE_LAUNCH_NOW = 3 };
 struct ChunkGate {
     std::mutex m;
     std::condition_variable cv;
-    int state = 0;                              // 0: not there yet, 1: event recorded, 2: nothing to wait for
+    int state = GATE_SHUT;                      // GATE_EVENT: wait for `ev` on the device; GATE_NONE: nothing to wait for
+    int opened = 0;                             // open() calls, the closing GATE_NONE of Aligner::run on an open gate apart
     hipEvent_t ev = nullptr;
-    void open(int st_) { { std::lock_guard<std::mutex> g(m); if (state == 0) state = st_; } cv.notify_all(); }
-    int wait() { std::unique_lock<std::mutex> g(m); cv.wait(g, [&] { return state != 0; }); return state; }
+    void open(int st_)
+    {
+        {
+            std::lock_guard<std::mutex> g(m);
+            if (state == GATE_SHUT || st_ != GATE_NONE) ++opened;
+            if (state == GATE_SHUT) state = st_;
+        }
+        cv.notify_all();
+    }
+    int wait() { std::unique_lock<std::mutex> g(m); cv.wait(g, [&] { return state != GATE_SHUT; }); return state; }
 };
+
+// the default plan of a big batch (align_on_store): chosen from the grid in profiles/chunk_handover_c2.txt
+constexpr int    kDefaultChunks = 2;
+constexpr double kDefaultChunkRatio = 1.0;
 
 struct Aligner {
     SpdpContext* ctx;                           // the lane this chunk runs on
@@ -365,10 +385,23 @@ struct Aligner {
         t_mark = now;
     }
 
+    // the launch's "all blocks started" word, looked at until it is set or the sweep has ended (its end event bounds the
+    // wait: a word that never comes costs nothing but the old behaviour)
+    static bool started(const DevRun& run)
+    {
+        if (!run.signal_armed) return false;
+        const int* word = run.ctx->sig_host;
+        for (unsigned look = 0; !__atomic_load_n(word, __ATOMIC_ACQUIRE); ++look) {
+            if (look % 16 == 15 && hipEventQuery(run.eve()) != hipErrorNotReady) return __atomic_load_n(word, __ATOMIC_ACQUIRE) != 0;
+            std::this_thread::sleep_for(std::chrono::microseconds(30));
+        }
+        return true;
+    }
+
     int run()
     {
         const int rc = run_chunk();
-        if (gate_out) gate_out->open(2);        // no linear-space round (or an error): the next chunk need not wait
+        if (gate_out) gate_out->open(GATE_NONE);        // no linear-space round (or an error): the next chunk need not wait
         if (!rc && out) for (int i = 0; i < n; ++i) finish(i, out + i);     // stdskl / trimskl, beside the other chunks
         return rc;
     }
@@ -432,11 +465,12 @@ struct Aligner {
             const bool a0 = sc.scalar_engines == 1;
             if (run.build(st, items, a0 ? RUN_A0_UDH : (sc.scalar_engines == 2 ? RUN_A1_UDH : RUN_WIP_UDH))) return -1;
             lap("udh build");
-            if (first_round && gate_in && gate_in->wait() == 1) HIPCHK(hipStreamWaitEvent(run.strm(), gate_in->ev, 0));
+            if (first_round && gate_in && gate_in->wait() == GATE_EVENT) HIPCHK(hipStreamWaitEvent(run.strm(), gate_in->ev, 0));
+            run.signal_start = first_round && gate_out;
             if (run.launch()) return -1;
             if (first_round && gate_out) {
                 HIPCHK(hipEventRecord(gate_out->ev, run.strm()));
-                gate_out->open(1);
+                gate_out->open(started(run) ? GATE_LAUNCH_NOW : GATE_EVENT);
             }
             first_round = false;
             if (run.sync()) return -1;
@@ -620,6 +654,12 @@ struct SpdpBatch {
     double stats[SPDP_N_STATS] = {0};
 };
 
+int spdp_chunk_plan(const int64_t* cells, int n, int max_chunks, double ratio, int min_chunk, int* bounds)
+{
+    if (!cells || !bounds) return 0;
+    return spdp_chunk_plan_of(cells, n, std::max(1, max_chunks), ratio, min_chunk, bounds);
+}
+
 SpdpBatch* spdp_batch_upload(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n)
 {
     if (!ctx || n <= 0) return nullptr;
@@ -667,48 +707,82 @@ static int align_on_store(SpdpContext* ctx, const DevStore* st, const SpdpProble
                           SpdpAlignment* out, float* kernel_ms, int64_t* kernel_cells,
                           double* stats = nullptr, bool raw = false, const SpdpRequests* req = nullptr)
 {
-    // big batches run as chunks on lanes of the context, a software pipeline (ChunkGate); SPDP_CHUNKS=1 turns it off
-    int n_chunks = n >= 4096 ? 2 : 1;
-    if (const char* e = getenv("SPDP_CHUNKS")) n_chunks = std::max(1, std::min(atoi(e), 8));
-    n_chunks = std::min(n_chunks, std::max(1, n / 64));
+    // big batches run as chunks on two lanes of the context, a software pipeline (ChunkGate); SPDP_CHUNKS=<n>: at most n
+    // chunks, 1 turns it off; SPDP_CHUNK_RATIO=<r>: chunk c + 1 holds r times the DP cells of chunk c (spdp_chunk_plan.h).
+    // Without SPDP_CHUNKS a chunk holds at least one residency round of problems (five 4-wave blocks per CU).
+    int max_chunks = n >= 4096 ? kDefaultChunks : 1, min_chunk = 5 * std::max(1, ctx->n_cu);
+    double ratio = kDefaultChunkRatio;
+    if (const char* e = getenv("SPDP_CHUNKS")) { max_chunks = std::max(1, std::min(atoi(e), 8)); min_chunk = SPDP_CHUNK_LEAST; }
+    if (const char* e = getenv("SPDP_CHUNK_RATIO")) ratio = atof(e);
     // a request batch runs on the dispatcher lane that took it, as ONE chunk: chunk lanes are spdp_lane(ctx, c), and for
     // the seeded dispatchers those are the contexts their sibling dispatchers run on from their own threads
-    if (req) n_chunks = 1;
+    if (req) max_chunks = 1;
+    std::vector<int> bounds((size_t) max_chunks + 1, 0);
+    int n_chunks = 1;
+    bounds[1] = n;
+    if (max_chunks > 1 && n >= 2 * SPDP_CHUNK_LEAST) {
+        std::vector<int64_t> cells(n);
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int i = 0; i < n; ++i) {
+            SpdpWindow w;
+            spdp_stripe(&probs[i], st->sc.sh, &w);
+            cells[i] = spdp_cells(&probs[i], &w);
+        }
+        n_chunks = spdp_chunk_plan_of(cells.data(), n, max_chunks, ratio, min_chunk, bounds.data());
+        if (getenv("SPDP_TIMING"))
+            fprintf(stderr, "[spdp timing] %-28s %8.2f ms  (%d chunks)\n", "chunk plan (cells + bounds)",
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_chunks);
+    }
+    const int n_lanes = std::min(n_chunks, 2);  // lane L runs chunks L, L + 2, .. one after the other; the gates chain c -> c + 1
     std::vector<Aligner> al(n_chunks);
     std::vector<ChunkGate> gates(n_chunks);
     std::vector<int> rc(n_chunks, 0);
     for (int c = 0; c < n_chunks; ++c) {
         Aligner& a = al[c];
-        a.ctx = spdp_lane(ctx, c);
+        a.ctx = spdp_lane(ctx, c % 2);
         if (!a.ctx) { ctx->err = "cannot create a lane context"; return -1; }
         a.st = st;
-        a.base = (int) ((int64_t) n * c / n_chunks);
-        a.n = (int) ((int64_t) n * (c + 1) / n_chunks) - a.base;
+        a.base = bounds[c];
+        a.n = bounds[c + 1] - bounds[c];
         a.probs = probs + a.base;
         a.out = out ? out + a.base : nullptr;
         a.raw = raw;
         a.req = req;
-        if (n_chunks > 1) {
+        if (c + 1 < n_chunks) {                 // (the last chunk has nobody to open a gate for)
             if (hipEventCreateWithFlags(&gates[c].ev, hipEventDisableTiming) != hipSuccess) {
                 for (int k = 0; k < c; ++k) if (gates[k].ev) (void) hipEventDestroy(gates[k].ev);
                 ctx->err = "hipEventCreate"; return -1;
             }
             a.gate_out = &gates[c];
-            a.gate_in = c > 0 ? &gates[c - 1] : nullptr;
         }
+        a.gate_in = c > 0 ? &gates[c - 1] : nullptr;
     }
+    // a lane's chunks in turn; after a failure the gates of its remaining chunks are opened, so that no other lane waits
+    auto run_lane = [&](int lane) {
+        bool failed = false;
+        for (int c = lane; c < n_chunks; c += n_lanes) {
+            if (!failed) failed = (rc[c] = al[c].run()) != 0;
+            else { rc[c] = -1; if (al[c].gate_out) al[c].gate_out->open(GATE_NONE); }     // (the lane's err is the failed chunk's)
+        }
+    };
     std::vector<std::thread> workers;
-    for (int c = 1; c < n_chunks; ++c)
-        workers.emplace_back([&, c, lane_copies = t_lane_copies]() { (void) hipSetDevice(ctx->device); t_lane_copies = lane_copies; rc[c] = al[c].run(); });
-    rc[0] = al[0].run();
+    for (int l = 1; l < n_lanes; ++l)
+        workers.emplace_back([&, l, lane_copies = t_lane_copies]() { (void) hipSetDevice(ctx->device); t_lane_copies = lane_copies; run_lane(l); });
+    run_lane(0);
     for (std::thread& t : workers) t.join();
+    ctx->chunk_stats[0] += 1; ctx->chunk_stats[1] += n_chunks;
+    for (int c = 0; c + 1 < n_chunks; ++c) {
+        const int how = gates[c].state;
+        ctx->chunk_stats[how == GATE_LAUNCH_NOW ? 2 : how == GATE_EVENT ? 3 : 4] += 1;
+        if (gates[c].opened == 1) ctx->chunk_stats[5] += 1;
+    }
     for (int c = 0; c < n_chunks; ++c) if (gates[c].ev) (void) hipEventDestroy(gates[c].ev);
     int unsupported = 0, overflowed = 0;
     float kms = 0.f; int64_t kc = 0;
     double st_sum[SPDP_N_STATS] = {0};
     for (int c = 0; c < n_chunks; ++c) {
         if (rc[c]) {                            // alignments other chunks have already handed over do not outlive the failed call
-            if (c > 0) ctx->err = al[c].ctx->err;
+            if (al[c].ctx != ctx) ctx->err = al[c].ctx->err;
             if (out) spdp_free_alignments(out, n);
             return -1;
         }

@@ -28,7 +28,23 @@ struct SweepArgs {
     // cross-CU pass pipelines (CROSS kernels): every problem is spread over cross_g blocks
     int               cross_g;    // blocks per problem (0: off)
     int*              gprog;      // per problem: cross_g * WPB progress words, then 2 barrier words; zeroed per launch
+    // "every block of this launch has started" (the chunk pipeline of spdp_host.cpp hands the GPU to the next chunk's sweep
+    // on it): blocks count themselves in `started` (device, zeroed per launch), the last to arrive sets *started_host (mapped
+    // pinned host memory).  Nothing on the device reads either word; both null: no signal (every launch but a gated UDH one)
+    unsigned*         started;
+    int*              started_host;
 };
+
+#if defined(__HIPCC__)
+// at the entry of a sweep kernel, ahead of any return: one relaxed add per block, and one plain store by the last arrival
+__device__ __forceinline__ void spdp_signal_started(const SweepArgs& A)
+{
+    if (A.started != nullptr && threadIdx.x == 0) {
+        const unsigned before = __hip_atomic_fetch_add(A.started, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (before + 1 == gridDim.x) __hip_atomic_store(A.started_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+#endif
 
 #define HIPCHK(call)                                                                     \
     do {                                                                                 \
@@ -244,7 +260,9 @@ static inline bool spdp_knob_on(const char* name) { const char* e = getenv(name)
 // for the long class's multi-millisecond sweep -- the copy waits for its OWN stream only (t_lane_copies, set by
 // spdp_run_requests / spdh_run_requests for the duration of the call).  Everywhere else the null-stream form stays: in the
 // chunked ladder of spdp_align_s it keeps one chunk's slab sweeps from starting under the other chunk's linear-space sweep,
-// which changes nothing end to end (290 ms a step either way) but is how the kernels of the headline step were profiled.
+// which changed nothing end to end when it was tried (290 ms a step either way, round 3) and is how the kernels of the headline
+// step were profiled.  It is also why more than two chunks lose there (profiles/chunk_handover_c2.txt): a chunk's post-work
+// waits for the sweep after it, and the lane's next sweep for that post-work.
 extern thread_local bool t_lane_copies;
 struct LaneCopies { bool was; LaneCopies() : was(t_lane_copies) { t_lane_copies = true; } ~LaneCopies() { t_lane_copies = was; } };
 static inline hipError_t spdp_copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s)
@@ -344,6 +362,15 @@ struct SpdpContext {
     // launches of the `_wip` sweeps (the FAM_WIP flavours of DevRun::launch, repeats included): served by spdp_sweep_fp, served by
     // spdp_sweep, with cross-CU groups, as 16-wave blocks (spdp_sweep_stats; atomic: a side-stream run launches from its own thread)
     std::atomic<int64_t> sweep_stats[4] = {};
+    // the "all blocks started" words of a gated sweep launch (SweepArgs::started / started_host): one pair per lane, allocated
+    // on the first such launch; sig_host is mapped pinned memory the chunk's thread polls, sig_host_dev its device address
+    unsigned* d_started = nullptr;
+    int*      sig_host = nullptr;
+    int*      sig_host_dev = nullptr;
+    int       start_signal();           // allocates the words once: 0, or -1 with err set
+    // chunk pipeline of the align calls on this context (spdp_chunk_stats): calls, chunks, gates opened by the start
+    // signal / by the recorded event / with nothing to wait for, gates opened exactly once
+    std::atomic<int64_t> chunk_stats[6] = {};
     void*  stage_ptr[3] = {nullptr, nullptr, nullptr};   // pinned host staging (grow-only): [0], [1] DevStore::upload, [2] the regions and
     size_t stage_cap[3] = {0, 0, 0};                     // signal arrays of spdp_map_align_s
     void*  staging(int k, size_t bytes);
@@ -465,6 +492,8 @@ struct DevRun {
     float kernel_ms = 0.f;
     bool side = false;                      // run on ctx->stream2 (set before build)
     bool in_flight = false;                 // launched, not yet waited for
+    bool signal_start = false;              // set before launch: arm the "all blocks started" signal where the launch can carry it
+    bool signal_armed = false;              // set by launch_sweep: this launch carries it (ctx->sig_host)
     bool beside = false;                    // another kernel fills the GPU meanwhile: keep to 4-wave blocks (a 16-wave
                                             // block finds no CU with room while small blocks keep refilling them)
     hipStream_t strm() const { return side ? ctx->stream2 : ctx->stream; }

@@ -52,7 +52,7 @@ enum { NQ_FLAT = 0, NQ_TABLE = 1, NQ_CHAIN = 2 };
 // c * WPB + wv, + cross_g * WPB, ..; progress words live in global memory and the boundary array is
 // accessed with memory-side coherent loads / stores.  All blocks of the launch must be resident (grid
 // <= number of CUs; 16-wave blocks take a whole CU each).
-template <int FL, bool LOCAL, int NQM, int WPB, bool CROSS = false>
+template <int FL, bool LOCAL, int NQM, int WPB, bool CROSS = false, bool SIG = false>      // SIG: a gated launch (SweepArgs::started)
 __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
 {
     constexpr int BW = (FL == FL_UDH) ? 4 : 2;          // ints per boundary entry
@@ -67,6 +67,7 @@ __global__ __launch_bounds__(WPB * 64) void spdp_sweep(SweepArgs A)
     // flush (replaces a rotate + shift DPP pair per value and step: spdp_sweep_fp.hip has the measurements)
     __shared__ int  s_out[WPB][4][16 * BW + BW];
 
+    if constexpr (SIG) spdp_signal_started(A);          // (spdp_internal.h)
     const DevScoring* __restrict__ sc = A.sc;
     for (int i = threadIdx.x; i < 32 * 32; i += blockDim.x) s_mtx[i] = sc->mtx[i];
     const int nquant = sc->nquant;
@@ -611,6 +612,16 @@ static void launch_nq(int nqm, dim3 grd, int wpb, hipStream_t stream, const Swee
         }
     }
     const dim3 blk(256);
+    if constexpr (!LOCAL && FL == FL_UDH) {
+        if (A.started != nullptr) {             // a gated launch of the chunk pipeline: the signalling instantiation
+            switch (nqm) {
+            case NQ_FLAT:  hipLaunchKernelGGL((spdp_sweep<FL, LOCAL, NQ_FLAT, 4, false, true>), grd, blk, 0, stream, A); break;
+            case NQ_TABLE: hipLaunchKernelGGL((spdp_sweep<FL, LOCAL, NQ_TABLE, 4, false, true>), grd, blk, 0, stream, A); break;
+            default:       hipLaunchKernelGGL((spdp_sweep<FL, LOCAL, NQ_CHAIN, 4, false, true>), grd, blk, 0, stream, A); break;
+            }
+            return;
+        }
+    }
     switch (nqm) {
     case NQ_FLAT:  hipLaunchKernelGGL((spdp_sweep<FL, LOCAL, NQ_FLAT, 4>), grd, blk, 0, stream, A); break;
     case NQ_TABLE: hipLaunchKernelGGL((spdp_sweep<FL, LOCAL, NQ_TABLE, 4>), grd, blk, 0, stream, A); break;

@@ -81,7 +81,9 @@ template <bool B> struct BoolTag { static constexpr bool value = B; };
 // WPB / CROSS / work mapping / progress words: exactly as spdp_sweep (spdp_kernels.hip).
 // SPJ: splice signals on (PwdB::DvsP != 0): with it off there is no donor / acceptor state at all.
 // A 4-wave block of one CU asks for five waves per SIMD: <= 32 KB of LDS and <= 96 VGPRs.
-template <int FL, int WPB, bool CROSS, bool SPJ>
+// SIG: the instantiation a gated launch of the chunk pipeline runs (SweepArgs::started); every other launch runs the kernel
+// without the entry block, whose few instructions cost the SPJ form five spilled registers in its pass loop
+template <int FL, int WPB, bool CROSS, bool SPJ, bool SIG = false>
 __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB == 4 && !CROSS ? 5 : 1))) void spdp_sweep_fp(SweepArgs A)
 {
     // FL_FORWARD (round 4): the traceback flavour -- one code byte per cell in the layout spdp_walk reads (spdp_kernels.hip:
@@ -117,6 +119,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     __shared__ int    s_io[WPB][4][16 * BW + BW];
     __shared__ int    s_prog_lds[WPB];
 
+    if constexpr (SIG) spdp_signal_started(A);          // (spdp_internal.h)
     const DevScoring* __restrict__ sc = A.sc;
     if (threadIdx.x < 32) {
         const int c = threadIdx.x;
@@ -684,6 +687,12 @@ static hipError_t launch_fp(dim3 grd, int wpb, hipStream_t stream, const SweepAr
     }
     // SPDP_LDS_PAD=<bytes>: extra dynamic LDS per block, i.e. fewer resident blocks per CU (occupancy experiments)
     static const int lds_pad = getenv("SPDP_LDS_PAD") ? atoi(getenv("SPDP_LDS_PAD")) : 0;
+    if constexpr (FL == FL_UDH) {
+        if (wpb != 16 && A.started != nullptr) {
+            hipLaunchKernelGGL((spdp_sweep_fp<FL, 4, false, SPJ, true>), grd, dim3(256), lds_pad, stream, A);
+            return hipGetLastError();
+        }
+    }
     if (wpb == 16) hipLaunchKernelGGL((spdp_sweep_fp<FL, 16, false, SPJ>), grd, dim3(1024), 0, stream, A);
     else           hipLaunchKernelGGL((spdp_sweep_fp<FL, 4, false, SPJ>), grd, dim3(256), lds_pad, stream, A);
     return hipGetLastError();

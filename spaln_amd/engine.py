@@ -35,7 +35,7 @@ EXPORTS = [
     "spdp_align_s_seeded", "spdp_align_s_seeded_ori3", "spdp_seeded_stats",
     "spdp_blk_index_create", "spdp_blk_index_destroy", "spdp_blk_vote", "spdp_blk_vote_resident",
     "spdp_blk_search_opts_default", "spdp_blk_index_read", "spdp_blk_index_host_desc", "spdp_blk_index_host_free",
-    "spdp_rerun_stats", "spdp_sweep_stats",
+    "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan",
 ]
 
 
@@ -112,9 +112,11 @@ def load_library() -> C.CDLL:
     lib.spdp_group_last_error.restype = C.c_char_p
     lib.spdp_group_last_error.argtypes = [C.c_void_p]
     lib.spdp_group_last_shards.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    for f in ("spdp_rerun_stats", "spdp_sweep_stats"):
+    for f in ("spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats"):
         getattr(lib, f).restype = None
         getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.spdp_chunk_plan.restype = C.c_int
+    lib.spdp_chunk_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
     lib.spdp_stripe.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.spdp_cells.argtypes = [C.c_void_p, C.c_void_p]
     for f in ("spdp_group_homscore_s", "spdp_group_align_s", "spdp_group_homscore_h", "spdp_group_align_h"):
@@ -341,6 +343,13 @@ class Engine:
         int32 spdp_sweep, laid out as cross-CU groups, as 16-wave blocks]"""
         out = np.zeros(4, dtype=np.int64)
         self.lib.spdp_sweep_stats(self.ctx, out.ctypes.data, int(bool(reset)))
+        return out
+
+    def chunk_stats(self, reset: bool = False) -> np.ndarray:
+        """spdp_chunk_stats: the chunk pipeline of the align calls since the last reset [calls, chunks, gates opened by the
+        start signal, by the event, with nothing to wait for, gates opened exactly once]"""
+        out = np.zeros(6, dtype=np.int64)
+        self.lib.spdp_chunk_stats(self.ctx, out.ctypes.data, int(bool(reset)))
         return out
 
     # ---- SimdAln2s1 `_wip` engines ------------------------------------------------
