@@ -1067,6 +1067,57 @@ int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const 
                                 const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep, int32_t all_out,
                                 int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails);
 
+/* ---- dispersed loci: the parts of a query that lie in different places (`spaln -pr`, algmode.mlt = 1) -----------------------------
+ * Chimeric clones, fusion transcripts, fused proteins, a gene split over two contigs of a draft assembly: the program aligns the
+ * query, looks at which stretch of it was covered, and searches the genome again with what is left over on each side (quick4,
+ * src/spaln.cc:1114-1134).  At most three searches per query, not recursive: the first on the query's own range org, then -- when
+ * the block search found anything -- [org.left, cov.left) if cov.left - org.left > MinSegLen, then [cov.right, org.right) if
+ * org.right - cov.right > MinSegLen, cov being the range the query has after the first search.  spdp_dispersed_rests is that rule
+ * alone, on the host, without a context: it writes the rests left first, rests[2 k] .. rests[2 k + 1], and returns their number
+ * (0, 1 or 2; -1: a null argument).
+ * Every search is blkaln with MaxOut = 1 (src/spaln.cc:846-1014): of the loci the block search lists for the range the one with the
+ * highest fstat.val is reported, the first on ties, if at least one locus was aligned with a score above sp->vthr (the selection of
+ * the _multi entries with max_out = 1 and the threshold on).  With algmode.mlt = 1 blkaln also NARROWS the query as it goes: after
+ * every locus that aligned and passed the threshold the query's range becomes [first exon's rleft, last exon's rright) of that
+ * locus, and the next locus of the list is aligned on that range, with the HSPs the block search found on the range before.  cov
+ * is what the last such locus left -- not necessarily what the reported locus covers -- and the parts of a query need not be
+ * disjoint: the block search looks for words inside a rest's range, but an HSP is extended to the query's ends whatever the range
+ * (Wlp::eval, src/wln.cc:365-367, 394), so the locus of a rest may reach past the rest, in the program as here.
+ * The entries below do the same for a batch: a pass is the chain of spdp_map_align_s / _h run with one range per query
+ * (the first pass: all queries; the second: all rests of all queries in one batch -- a rest is a range of its query, positions
+ * are never re-based), and inside a pass the loci are aligned by rounds, so that a locus sees the range its predecessors left (a
+ * query's later loci go along with the first one and are aligned again only where the range changed; at most max_out2 rounds).
+ *   min_seg_len  the program's MinSegLen = SrchBlk::MinQuery() = 2 Ktuple + Nshift of the index (src/blksrc.cc:2015; the
+ *                descriptor does not hold Ktuple, so it is the caller's).  <= 0 is refused.
+ *   fprm->max_out must be 1 (-pr together with -M N is another mode: refused).
+ *   prep         (cDNA; may be NULL) as in spdp_map_align_s_prep: it replaces ori, the first search's range is the record's
+ *                [left, right), tails (may be NULL) takes the records.  All positions come back as those of the query as given.
+ * Out, in the shape of the _multi entries: query i reports (*genes)[gene_off[i] .. gene_off[i + 1]), at most three, in the
+ * program's print order (first search, left rest, right rest); (*part)[k] (malloc'ed: free() it as *genes and *exons) says
+ * which search gave gene k: 0 the first, 1 the left rest, 2 the right rest; SpdpMapGene.n_loci counts the loci aligned in that
+ * search.  covered (2 n values, may be NULL): cov of every query after its first search, covered[2 i] .. covered[2 i + 1], in
+ * positions of the query as given (0-based, half open); the query's own range when nothing aligned.  "Left" and "right" are those
+ * of the query as the program holds it: for a query the preparation turned (a T head) part 1 lies on the right of the query as given.
+ * seconds: the four phases summed over passes and rounds.  Nothing is launched for a refused call.
+ * ori = 3: every locus picks its orientation on its own, as in the sibling entries, and when the reverse leg wins the range is
+ * narrowed in the coordinates of the query as given.  The program differs there as it does for -M N: after a locus aligned with
+ * the query reverse-complemented it leaves the query in that state (src/fwd2s1.cc:2766-2777) and goes on -- further loci, cov and
+ * the rests -- with ranges that belong to the other orientation; that state is not reproduced.  Not served either: a rest of a
+ * rest (the program has no such recursion), Seq::sigII queries, the group twins. */
+int spdp_dispersed_rests(const int32_t org[2], const int32_t cov[2], int32_t min_seg_len, int32_t rests[4]);
+int spdp_map_align_s_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                               const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                               const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                               const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, const SpdpQueryPrep* prep,
+                               int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                               int32_t* covered, double* seconds, SpdpQueryTail* tails);
+int spdp_map_align_h_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                               const struct SpdpScoringH* sc, const SpdpSeedParams* sp, const struct SpdpSignalModelH* sigmodel,
+                               const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
+                               const uint8_t* codes, const int64_t* offs, int32_t n, int32_t min_seg_len,
+                               int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                               int32_t* covered, double* seconds);
+
 /* ---- device groups, continued ------------------------------------------------------------------------------------------ */
 /* the same sharding for the calls of the seeded path, rescoring and the block vote (rounds 3 / 4).  The HSP source of a
  * seeded call is asked with the CALLER's query numbers, from the worker threads of every member.  spdp_group_blk_vote takes

@@ -636,3 +636,76 @@ def map_align_multi_prep(index: "BlockIndex", genome_codes, chr_off, sc, sp, sig
     libc.free(genes)
     libc.free(exons)
     return out, sec, rc, rec
+
+
+# ---- dispersed loci (include/spdp.h "dispersed loci"): what `spaln -pr` prints of a query whose parts lie in different places
+def _dispersed_out(n, gene_off, genes, exons, part, covered):
+    out = [[dict(_gene(genes[k], exons), part=int(part[k])) for k in range(int(gene_off[i]), int(gene_off[i + 1]))] for i in range(n)]
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    for p in (genes, exons, part):
+        libc.free(p)
+    return out, covered.reshape(n, 2)
+
+
+def map_align_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, min_seg_len: int,
+                        ori: int = 1, prep=None):
+    """spdp_map_align_s_dispersed: per query the locus of its first search and of the searches on what that left uncovered on
+    each side (at most three, in the program's print order).  min_seg_len: the program's MinSegLen = 2 Ktuple + Nshift of the
+    index; prm.max_out must be 1.  prep = (q_mns, polya_thr): PolyA::rmpolyA in front, as map_align_prep (it replaces ori).
+    Returns (per query a list of dicts shaped as map_align's plus part = 0 / 1 / 2: first search / left rest / right rest;
+    covered: (n, 2) int32, the range every query has after its first search; seconds; return code; records as polya_scan's or None)."""
+    from . import abi
+    lib, eng = index.lib, index.eng
+    n = len(queries)
+    codes, offs = _packed(queries)
+    g = Genome()
+    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+    go = np.ascontiguousarray(chr_off, dtype=np.int64)
+    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
+    rp = abi.RescoreParams(*(int(x) for x in rescore))
+    qp = QueryPrep(int(prep[0]), int(prep[1])) if prep is not None else None
+    tails = (QueryTail * max(n, 1))() if prep is not None else None
+    gene_off = np.zeros(n + 1, dtype=np.int64)
+    genes, exons, part = C.POINTER(MapGene)(), C.POINTER(MapExon)(), C.POINTER(C.c_int32)()
+    covered = np.zeros(2 * max(n, 1), dtype=np.int32)
+    sec = (C.c_double * 4)()
+    f = lib.spdp_map_align_s_dispersed
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp),
+           codes.ctypes.data, offs.ctypes.data, n, int(ori), C.byref(qp) if qp is not None else None, int(min_seg_len),
+           gene_off.ctypes.data, C.byref(genes), C.byref(exons), C.byref(part), covered.ctypes.data, sec, tails)
+    if rc < 0:
+        eng._check(rc, "spdp_map_align_s_dispersed")
+    rec = None
+    if prep is not None:
+        rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
+    out, cov = _dispersed_out(n, gene_off, genes, exons, part, covered[:2 * n])
+    return out, cov, list(sec), rc, rec
+
+
+def map_align_h_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, min_seg_len: int):
+    """spdp_map_align_h_dispersed: the same for protein queries against the translated index (arguments as map_align_h's; positions
+    of the query in residues).  Returns (lists, covered, seconds, return code) as map_align_dispersed."""
+    lib, eng = index.lib, index.eng
+    n = len(queries)
+    codes, offs = _packed(queries)
+    g = Genome()
+    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+    go = np.ascontiguousarray(chr_off, dtype=np.int64)
+    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
+    gene_off = np.zeros(n + 1, dtype=np.int64)
+    genes, exons, part = C.POINTER(MapGene)(), C.POINTER(MapExon)(), C.POINTER(C.c_int32)()
+    covered = np.zeros(2 * max(n, 1), dtype=np.int32)
+    sec = (C.c_double * 4)()
+    f = lib.spdp_map_align_h_dispersed
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rescore),
+           codes.ctypes.data, offs.ctypes.data, n, int(min_seg_len), gene_off.ctypes.data, C.byref(genes), C.byref(exons), C.byref(part),
+           covered.ctypes.data, sec)
+    if rc < 0:
+        eng._check(rc, "spdp_map_align_h_dispersed")
+    out, cov = _dispersed_out(n, gene_off, genes, exons, part, covered[:2 * n])
+    return out, cov, list(sec), rc

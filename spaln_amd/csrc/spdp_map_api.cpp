@@ -47,6 +47,7 @@ struct LocusOut {
     bool aligned;                    // the walk gave a skeleton (Gsinfo::skl)
     SpdpMapGene g;                   // chr, rvs, q_rev, score (Gsinfo::scr), val (fstat.val; 0 -- vclear -- when not aligned)
     std::vector<SpdpMapExon> ex;     // its exons as -O4 prints them
+    int32_t rleft = 0, rright = 0;   // first exon's rleft, last exon's rright: the query range it covers, as the block search counts it
 };
 // called once per locus, in the block search's order (query by query, a query's loci as findblock listed them)
 using LocusSink = std::function<void(const SpdpLocus& L, LocusOut&& o)>;
@@ -126,6 +127,34 @@ struct BestSink {
 // whose walk failed or -- unless all_out (-pw) -- whose score is <= Vthr; ALL loci, the dropped ones too, are insertion-sorted by
 // fstat.val (descending, stable); the first min(n_out, MaxOut) positions of that order are printed, those without a skeleton
 // skipped.  So a locus dropped by the threshold keeps its place in the order and is printed when it lands in one of those slots.
+// (v: one query's loci in the block search's order -> the printed ones)
+void select_printed(std::vector<LocusOut>& v, int max_out, int all_out, int vthr, std::vector<SpdpMapGene>& genes, std::vector<std::vector<SpdpMapExon>>& ex)
+{
+    const int np = (int) v.size();
+    int n_out = 0, n_aligned = 0;
+    for (const LocusOut& o : v) {
+        n_aligned += o.aligned;
+        n_out += o.aligned && (all_out || o.g.score > vthr);
+    }
+    std::vector<int> odr(np);
+    std::iota(odr.begin(), odr.end(), 0);
+    for (int k = 1; k < np; ++k) {                         // (the reference's insertion sort: ties keep their order)
+        const int l = odr[k];
+        int m = k;
+        while (--m >= 0 && v[l].g.val > v[odr[m]].g.val) odr[m + 1] = odr[m];
+        odr[m + 1] = l;
+    }
+    n_out = std::min(n_out, max_out);
+    for (int k = 0; k < n_out; ++k) {
+        LocusOut& o = v[odr[k]];
+        if (!o.aligned) continue;
+        if (!all_out && o.g.score <= vthr) o.g.score = SPDP_NEVSEL;     // (dropped, printed all the same: its scr is NEVSEL by then)
+        o.g.n_loci = n_aligned;
+        genes.push_back(o.g);
+        ex.push_back(std::move(o.ex));
+    }
+}
+
 struct MultiSink {
     std::vector<std::vector<LocusOut>> all;
     int max_out, all_out, vthr;
@@ -134,32 +163,7 @@ struct MultiSink {
     int finish(SpdpContext* ctx, const char* who, int n, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons)
     {
         Reported r(n);
-        for (int i = 0; i < n; ++i) {
-            std::vector<LocusOut>& v = all[i];
-            const int np = (int) v.size();
-            int n_out = 0, n_aligned = 0;
-            for (const LocusOut& o : v) {
-                n_aligned += o.aligned;
-                n_out += o.aligned && (all_out || o.g.score > vthr);
-            }
-            std::vector<int> odr(np);
-            std::iota(odr.begin(), odr.end(), 0);
-            for (int k = 1; k < np; ++k) {                         // (the reference's insertion sort: ties keep their order)
-                const int l = odr[k];
-                int m = k;
-                while (--m >= 0 && v[l].g.val > v[odr[m]].g.val) odr[m + 1] = odr[m];
-                odr[m + 1] = l;
-            }
-            n_out = std::min(n_out, max_out);
-            for (int k = 0; k < n_out; ++k) {
-                LocusOut& o = v[odr[k]];
-                if (!o.aligned) continue;
-                if (!all_out && o.g.score <= vthr) o.g.score = SPDP_NEVSEL;     // (dropped, printed all the same: its scr is NEVSEL by then)
-                o.g.n_loci = n_aligned;
-                r.genes[i].push_back(o.g);
-                r.ex[i].push_back(std::move(o.ex));
-            }
-        }
+        for (int i = 0; i < n; ++i) select_printed(all[i], max_out, all_out, vthr, r.genes[i], r.ex[i]);
         return hand_out(ctx, who, r, n, gene_off, genes, exons);
     }
 };
@@ -182,14 +186,37 @@ int check_multi(SpdpContext* ctx, const char* who, const SpdpBlkIndexDesc* hix, 
 
 }  // namespace
 
-static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                                const LocusSink& sink, double* seconds,
-                                const SpdpQueryPrep* prep = nullptr, bool prepares = false, SpdpQueryTail* tails_out = nullptr)
+namespace {
+
+// The cDNA chain in its steps, and what one call holds between them: setup() checks the arguments and prepares the queries,
+// find() is the block search on one range per query, align() takes loci through regions + signals, the seeded walks and the
+// rescoring and hands each to the sink.  spdp_map_align_s and its siblings run the steps once; the dispersed entries run find()
+// per pass and align() per round.
+struct ChainS {
+    SpdpContext* ctx; const SpdpBlkIndex* ix; const SpdpBlkIndexDesc* hix; const SpdpGenome* genome; const SpdpScoring* sc;
+    const SpdpSeedParams* sp; const SpdpSignalModel* sigmodel; const SpdpBlkFindParams* fprm; const SpdpRescoreParams* rp;
+    const uint8_t* codes; const int64_t* offs; int32_t n; int32_t ori;     // (codes: the normalised queries once setup() has prepared them)
+    double sec[4] = {0, 0, 0, 0};
+    int partial = 0;
+    std::vector<int32_t> ql, qr;                        // every query's range
+    std::vector<SpdpQueryTail> tail;                    // empty: no preparation, or none that scans (polya_thr <= 0)
+    std::vector<uint8_t> normal;
+    std::vector<int32_t> qt;                            // Seq::tlen per query
+    bool tailed = false;
+    std::vector<uint8_t> codes_rc;                      // comrev() of every query (ori = 3), made by the first align()
+    const int32_t* tlen() const { return tailed ? qt.data() : nullptr; }
+    bool prep_turned(int q) const { return tailed && tail[q].pol == 2; }   // the preparation reverse-complemented query q
+
+    int setup(const SpdpQueryPrep* prep, bool prepares, SpdpQueryTail* tails_out);
+    int find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
+             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps);
+    int align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink);
+    int finish(double* seconds);
+};
+
+// -1: refused (ctx->err says why); 0: go on (n <= 0: there is nothing to do)
+int ChainS::setup(const SpdpQueryPrep* prep, bool prepares, SpdpQueryTail* tails_out)
 {
-    if (!ctx) return -1;
     if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
         ctx->err = "spdp_map_align_s: null argument"; return -1;
     }
@@ -201,16 +228,12 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     }
     if (ori != 1 && ori != 3) { ctx->err = "spdp_map_align_s: ori must be 1 (the query as given) or 3 (both orientations)"; return -1; }
     if (!sp->wilip) { ctx->err = "spdp_map_align_s: SpdpSeedParams.wilip missing (the HSP searches of this call are the library's own)"; return -1; }
-    double sec[4] = {0, 0, 0, 0};
     if (n <= 0) return 0;
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<int32_t> ql(n, 0), qr(n);
+    ql.assign(n, 0); qr.resize(n);
     for (int i = 0; i < n; ++i) qr[i] = (int32_t) (offs[i + 1] - offs[i]);
     // ---- the preparation (PolyA::rmpolyA, spdp_polya.hip): tails found, antisense queries turned; from here on `codes` are the
     // normalised queries and every reader of a query's range or length takes them from its record
-    std::vector<SpdpQueryTail> tail;                    // empty: no preparation, or none that scans (polya_thr <= 0)
-    std::vector<uint8_t> normal;
-    std::vector<int32_t> qt;                            // Seq::tlen per query
     if (prepares && prep->polya_thr > 0) {
         tail.resize(n); normal.resize((size_t) offs[n]);
         if (spdp_polya_scan(ctx, codes, offs, n, prep, tail.data(), normal.data(), nullptr)) return -1;
@@ -221,16 +244,28 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     } else if (prepares && tails_out && spdp_polya_scan_host(codes, offs, n, prep, tails_out, nullptr)) {
         ctx->err = "spdp_map_align_s_prep: bad query offsets"; return -1;
     }
-    const bool tailed = !tail.empty();
-    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
-    if (spdp_blk_find_tlen(ctx, ix, hix, genome, sp->wilip, sc, fprm, codes, offs, ql.data(), qr.data(), tailed ? qt.data() : nullptr, n,
-                           &loci, &n_loci, &hsps, nullptr)) return -1;
-    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
-    sec[0] = since(t0);
+    tailed = !tail.empty();
+    sec[0] += since(t0);
+    return 0;
+}
 
+// the block search for m queries laid out by cd / of (the call's own, or a pass's selection of them), each on its range
+int ChainS::find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
+                 SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = spdp_blk_find_tlen(ctx, ix, hix, genome, sp->wilip, sc, fprm, cd, of, left, right, tl, m, loci, n_loci, hsps, nullptr);
+    sec[0] += since(t0);
+    return rc;
+}
+
+// loci[k].query: a query of the call; rng (may be null): the query range locus k is aligned on, rng[2 k] .. rng[2 k + 1] of the
+// normalised query -- without it the query's own range.  The sink gets every locus, in the order given.
+int ChainS::align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink)
+{
+    auto t0 = std::chrono::steady_clock::now();
     const bool both = ori == 3;
-    std::vector<uint8_t> codes_rc;                      // comrev() of every query (ori = 3)
-    if (both) {
+    if (both && codes_rc.empty()) {
         codes_rc.resize((size_t) offs[n]);
         on_host_threads(n, [&](int q) {
             const int64_t a0 = offs[q], len = offs[q + 1] - offs[q];
@@ -246,7 +281,6 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     size_t chunk_positions = (size_t) 2048 << 20;
     for (const char* v : {"SPDP_MAP_CHUNK_MB", "SPDP_MAP_CHUNK_MPOS"})
         if (const char* e = getenv(v)) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    int partial = 0;
     (void) hipSetDevice(ctx->device);
     // chunks of loci: as few as the position limit allows, of equal size (a call's time is a chain of request latencies, not
     // device work: DESIGN.md 6g -- so the larger a chunk the better, and a short last chunk costs as much as a full one)
@@ -320,11 +354,10 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             P.b = reg + at[j]; P.b_len = L.len;
             P.sig5 = sig5 + at[j]; P.sig3 = sig3 + at[j];
             P.cano5 = cano5 + at[j]; P.cano3 = cano3 + at[j]; P.dinc = dinc + at[j];
-            P.a_left = 0; P.a_right = P.a_len; P.b_left = slot_left(j); P.b_right = slot_right(j);
-            if (tailed) {                               // (the reverse leg: Seq::comrev mirrors the range, Seq::rev_attr)
-                const SpdpQueryTail& t = tail[L.query];
-                P.a_left = j < m ? t.left : P.a_len - t.right; P.a_right = j < m ? t.right : P.a_len - t.left;
-            }
+            P.b_left = slot_left(j); P.b_right = slot_right(j);
+            // the query's range: the one given for this locus, else its own (the reverse leg: Seq::comrev mirrors it, Seq::rev_attr)
+            const int32_t al = rng ? rng[2 * (c0 + k)] : ql[L.query], ar = rng ? rng[2 * (c0 + k) + 1] : qr[L.query];
+            P.a_left = j < m ? al : P.a_len - ar; P.a_right = j < m ? ar : P.a_len - al;
             P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
             if (j < m) { hl[k] = hsps + L.hsp_off; hn[k] = L.n_hsp; }
         }
@@ -371,6 +404,9 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             for (int e = 0; e < res[k].n_exons; ++e) {
                 const SpdpExon& x = res[k].exons[e];
                 if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
+                // the query range covered, from the first exon's rleft to the last one's rright; the reverse leg's turned back
+                const int32_t xl = orient[k] ? a_len - x.rright : x.rleft, xr = orient[k] ? a_len - x.rleft : x.rright;
+                o.rleft = ex.empty() ? xl : std::min(o.rleft, xl); o.rright = ex.empty() ? xr : std::max(o.rright, xr);
                 // positions of the query as given (Seq::SiteNo with inex.sens reversed): the reverse leg turned it, and so did the
                 // preparation of a query with a T head -- both: as given again
                 const bool turned = (orient[k] != 0) != (tailed && tail[L.query].pol == 2);
@@ -384,9 +420,34 @@ static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         sec[3] += since(t0);
         c0 = c1;
     }
+    return 0;
+}
+
+int ChainS::finish(double* seconds)
+{
     if (seconds) memcpy(seconds, sec, sizeof sec);
     if (partial) { ctx->err = "spdp_map_align_s: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
     return 0;
+}
+
+}  // namespace
+
+static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
+                                const LocusSink& sink, double* seconds,
+                                const SpdpQueryPrep* prep = nullptr, bool prepares = false, SpdpQueryTail* tails_out = nullptr)
+{
+    if (!ctx) return -1;
+    ChainS R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori};
+    if (R.setup(prep, prepares, tails_out)) return -1;
+    if (n <= 0) return 0;
+    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
+    if (R.find(R.codes, offs, R.ql.data(), R.qr.data(), R.tlen(), n, &loci, &n_loci, &hsps)) return -1;
+    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
+    if (R.align(loci, n_loci, hsps, nullptr, sink)) return -1;
+    return R.finish(seconds);
 }
 
 extern "C" int spdp_map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
@@ -442,34 +503,58 @@ extern "C" int spdp_map_align_s_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, 
 // its SGPT6 signals, all loci of a chunk in one launch of spdp_signals_h -> spdp_align_h_seeded with the library's own HSP searches ->
 // the junction phases the walks chose written back (skl_rngH_ng reads them: spdp_seeded_phase_marks) -> spdp_skl_rng_h -> every locus
 // to the sink (the best one, or the list spaln -M prints).  What blkaln / genomicseq / spalign2 do per query (src/spaln.cc:846-1010, 1137-1152), for a batch.
-static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                       const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
-                       const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
-                       const uint8_t* codes, const int64_t* offs, int32_t n,
-                       const LocusSink& sink, double* seconds)
+namespace {
+
+// the protein chain in the same steps (ChainS): no orientation, no preparation
+struct ChainH {
+    SpdpContext* ctx; const SpdpBlkIndex* ix; const SpdpBlkIndexDesc* hix; const SpdpGenome* genome; const SpdpScoringH* sc;
+    const SpdpSeedParams* sp; const SpdpSignalModelH* sigmodel; const SpdpBlkFindParams* fprm; const SpdpRescoreParamsH* rp;
+    const uint8_t* codes; const int64_t* offs; int32_t n;
+    double sec[4] = {0, 0, 0, 0};
+    int partial = 0;
+    std::vector<int32_t> ql, qr;                        // every query's range
+    const int32_t* tlen() const { return nullptr; }
+    bool prep_turned(int) const { return false; }
+
+    int setup();
+    int find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
+             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps);
+    int align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink);
+    int finish(double* seconds);
+};
+
+int ChainH::setup()
 {
-    if (!ctx) return -1;
     if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
         ctx->err = "spdp_map_align_h: null argument"; return -1;
     }
     if (!sp->wilip || sp->wilip->dvsp != 1) { ctx->err = "spdp_map_align_h: SpdpSeedParams.wilip must be the protein model (dvsp = 1)"; return -1; }
     if (!sc->intpen || sc->intpen_len <= 0) { ctx->err = "spdp_map_align_h: SpdpScoringH.intpen missing"; return -1; }
-    double sec[4] = {0, 0, 0, 0};
     if (n <= 0) return 0;
-    auto t0 = std::chrono::steady_clock::now();
-    std::vector<int32_t> ql(n, 0), qr(n);
+    ql.assign(n, 0); qr.resize(n);
     for (int i = 0; i < n; ++i) qr[i] = (int32_t) (offs[i + 1] - offs[i]);
+    return 0;
+}
+
+int ChainH::find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t*, int32_t m,
+                 SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps)
+{
+    auto t0 = std::chrono::steady_clock::now();
     SpdpScoring chain_costs;                            // (the gap and intron prices the HSP chaining reads)
     memset(&chain_costs, 0, sizeof chain_costs);
     chain_costs.gop = sc->gop; chain_costs.gep = sc->gep; chain_costs.lgop = sc->lgop; chain_costs.lgep = sc->lgep; chain_costs.codonk1 = sc->codonk1;
     chain_costs.intpen = sc->intpen; chain_costs.intpen_len = sc->intpen_len;
-    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
-    if (spdp_blk_find(ctx, ix, hix, genome, sp->wilip, &chain_costs, fprm, codes, offs, ql.data(), qr.data(), n, &loci, &n_loci, &hsps, nullptr)) return -1;
-    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
-    sec[0] = since(t0);
+    const int rc = spdp_blk_find(ctx, ix, hix, genome, sp->wilip, &chain_costs, fprm, cd, of, left, right, m, loci, n_loci, hsps, nullptr);
+    sec[0] += since(t0);
+    return rc;
+}
+
+// as ChainS::align: rng (may be null) = the range of the query, in residues, locus k is aligned on
+int ChainH::align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink)
+{
+    auto t0 = std::chrono::steady_clock::now();
     size_t chunk_positions = (size_t) 512 << 20;        // 14 B per position on both sides of the bus
     if (const char* e = getenv("SPDP_MAP_CHUNK_MPOS")) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    int partial = 0;
     (void) hipSetDevice(ctx->device);
     for (int k = 0; k < n_loci; ++k) {
         const SpdpLocus& L = loci[k];
@@ -527,7 +612,8 @@ static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
             P.sig5 = s16[0] + at[j]; P.sig3 = s16[1] + at[j]; P.sigS = s16[2] + at[j]; P.sigT = s16[3] + at[j]; P.sigE = s16[4] + at[j];
             P.phs5 = phs5 + at[j]; P.phs3 = phs3 + at[j]; P.dinc = dinc + at[j];
             P.exin_left = L.left; P.exin_right = L.right;
-            P.a_left = 0; P.a_right = P.a_len; P.b_left = L.left; P.b_right = L.right;
+            P.a_left = rng ? rng[2 * (c0 + j)] : ql[L.query]; P.a_right = rng ? rng[2 * (c0 + j) + 1] : qr[L.query];
+            P.b_left = L.left; P.b_right = L.right;
             P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
             hl[j] = hsps + L.hsp_off; hn[j] = L.n_hsp;
         }
@@ -569,6 +655,8 @@ static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
                 const SpdpExon& x = res[j].exons[e];
                 if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
                 if (open < 0) open = e;
+                if (ex.empty() && open == e) o.rleft = x.rleft;                                   // the query range covered: every record counts
+                o.rright = x.rright;
                 if (x.iscr <= SPDP_NEVSEL) continue;
                 const SpdpExon& x0 = res[j].exons[open];
                 ex.push_back({x0.rleft + 1, x.rright, site(x0.left), site(x.right - 1)});
@@ -580,9 +668,33 @@ static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
         sec[3] += since(t0);
         c0 = c1;
     }
+    return 0;
+}
+
+int ChainH::finish(double* seconds)
+{
     if (seconds) memcpy(seconds, sec, sizeof sec);
     if (partial) { ctx->err = "spdp_map_align_h: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
     return 0;
+}
+
+}  // namespace
+
+static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                       const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
+                       const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+                       const uint8_t* codes, const int64_t* offs, int32_t n,
+                       const LocusSink& sink, double* seconds)
+{
+    if (!ctx) return -1;
+    ChainH R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n};
+    if (R.setup()) return -1;
+    if (n <= 0) return 0;
+    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
+    if (R.find(codes, offs, R.ql.data(), R.qr.data(), nullptr, n, &loci, &n_loci, &hsps)) return -1;
+    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
+    if (R.align(loci, n_loci, hsps, nullptr, sink)) return -1;
+    return R.finish(seconds);
 }
 
 extern "C" int spdp_map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
@@ -674,6 +786,195 @@ extern "C" int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex*
     catch (const std::bad_alloc&) {
         ctx->err = "spdp_map_align_s_multi_prep: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
         free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
+        return -1;
+    }
+}
+
+// ---- dispersed loci: quick4 around blkaln with algmode.mlt = 1 (`spaln -pr`; include/spdp.h "dispersed loci") ---------------------
+// quick4's rule alone (src/spaln.cc:1114-1134): which stretches of the query's range are searched again after its first search
+// left the range at cov.  Both comparisons are strict.
+extern "C" int spdp_dispersed_rests(const int32_t org[2], const int32_t cov[2], int32_t min_seg_len, int32_t rests[4])
+{
+    if (!org || !cov || !rests) return -1;
+    int k = 0;
+    if (cov[0] - org[0] > min_seg_len) { rests[0] = org[0]; rests[1] = cov[0]; ++k; }
+    if (org[1] - cov[1] > min_seg_len) { rests[2 * k] = cov[1]; rests[2 * k + 1] = org[1]; ++k; }
+    return k;
+}
+
+namespace {
+
+// one search of quick4: query q on [l, r) of its normalised form; part: 0 the first search, 1 the left rest, 2 the right rest
+struct Piece { int q; int32_t l, r; int part; };
+// what blkaln leaves of it: every locus as it was aligned, in the block search's order, and the range the query has afterwards
+struct PieceOut { std::vector<LocusOut> loci; int32_t l, r; };
+
+// One pass = blkaln for every piece: the block search on the pieces' ranges, then the loci by rounds.  blkaln aligns a query's
+// loci one after the other and narrows the query to what a locus covered once that locus passed the threshold (src/spaln.cc:914-918,
+// 950-954), so locus k + 1 is aligned on the range locus k left -- with the HSPs found on the range before.  A round aligns, for
+// every piece, all loci not yet settled on the piece's range as it stands; they are settled in order up to and including the
+// first one that changes the range, the others wait for the next round.  Most pieces have one locus, and a locus that covers the
+// whole range changes nothing: such pieces are done in one round (a round costs a chain of request latencies).
+template <class Chain>
+int dispersed_pass(Chain& R, const std::vector<Piece>& pieces, bool whole_call, int vthr, std::vector<PieceOut>& out)
+{
+    const int m = (int) pieces.size();
+    out.assign(m, PieceOut());
+    if (!m) return 0;
+    std::vector<int32_t> l(m), r(m), tl;
+    for (int p = 0; p < m; ++p) { out[p].l = l[p] = pieces[p].l; out[p].r = r[p] = pieces[p].r; }
+    // the queries of the pass as the block search takes them: the call's own (the first pass: piece p is query p), or the whole
+    // queries of the pieces one behind the other -- a rest is a range of its query, so every position keeps its meaning.  That is a
+    // host copy of each such query (twice for a query with two rests) and the upload of whole queries for what may be short
+    // rests: spdp_blk_find takes queries that lie one behind the other, and has no indirection that would let two pieces share one
+    const uint8_t* cd = R.codes; const int64_t* of = R.offs;
+    std::vector<uint8_t> sel; std::vector<int64_t> sel_off;
+    if (!whole_call) {
+        sel_off.assign(m + 1, 0);
+        for (int p = 0; p < m; ++p) sel_off[p + 1] = sel_off[p] + (R.offs[pieces[p].q + 1] - R.offs[pieces[p].q]);
+        sel.resize((size_t) sel_off[m]);
+        for (int p = 0; p < m; ++p) memcpy(sel.data() + sel_off[p], R.codes + R.offs[pieces[p].q], (size_t) (sel_off[p + 1] - sel_off[p]));
+        cd = sel.data(); of = sel_off.data();
+    }
+    if (R.tlen()) { tl.resize(m); for (int p = 0; p < m; ++p) tl[p] = R.tlen()[pieces[p].q]; }
+    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
+    if (R.find(cd, of, l.data(), r.data(), tl.empty() ? nullptr : tl.data(), m, &loci, &n_loci, &hsps)) return -1;
+    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
+    std::vector<int> end(m + 1, 0);                     // piece p's loci: loci[end[p] .. end[p + 1]), as findblock listed them
+    for (int k = 0; k < n_loci; ++k) ++end[loci[k].query + 1];
+    for (int p = 0; p < m; ++p) end[p + 1] += end[p];
+    for (int k = 0; k < n_loci; ++k) loci[k].query = pieces[loci[k].query].q;
+    std::vector<int> next(end.begin(), end.end() - 1);
+    int rounds = 0;
+    size_t aligned = 0;
+    for (;; ++rounds) {
+        std::vector<SpdpLocus> batch;
+        std::vector<int32_t> rng;
+        for (int p = 0; p < m; ++p)
+            for (int k = next[p]; k < end[p + 1]; ++k) { batch.push_back(loci[k]); rng.push_back(out[p].l); rng.push_back(out[p].r); }
+        if (batch.empty()) break;
+        aligned += batch.size();
+        std::vector<LocusOut> got;
+        got.reserve(batch.size());
+        if (R.align(batch.data(), (int) batch.size(), hsps, rng.data(), [&got](const SpdpLocus&, LocusOut&& o) { got.push_back(std::move(o)); })) return -1;
+        size_t j = 0;
+        for (int p = 0; p < m; ++p) {
+            const int waiting = end[p + 1] - next[p];
+            for (int i = 0; i < waiting; ++i) {
+                LocusOut& o = got[j + i];
+                const bool narrows = o.aligned && o.g.score > vthr && (o.rleft != out[p].l || o.rright != out[p].r);
+                const int32_t nl = o.rleft, nr = o.rright;
+                out[p].loci.push_back(std::move(o));
+                ++next[p];
+                if (narrows) { out[p].l = nl; out[p].r = nr; break; }       // (the loci behind it were aligned on a range that is gone)
+            }
+            j += waiting;
+        }
+    }
+    if (getenv("SPDP_MAP_VERBOSE")) fprintf(stderr, "[dispersed] pass of %d searches: %d loci, %d rounds, %zu alignments\n", m, n_loci, rounds, aligned);
+    return 0;
+}
+
+// quick4 for every query of the call (src/spaln.cc:1114-1134): the first search on the query's own range, then in one further
+// pass every rest that is longer than min_seg_len; per search the locus blkaln prints with MaxOut = 1
+template <class Chain>
+int dispersed(Chain& R, const char* who, int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+              int32_t* covered)
+{
+    const int n = R.n;
+    const int vthr = R.sp->vthr;
+    std::vector<Piece> first(n), rest;
+    for (int q = 0; q < n; ++q) first[q] = {q, R.ql[q], R.qr[q], 0};
+    std::vector<PieceOut> o1, o2;
+    if (dispersed_pass(R, first, true, vthr, o1)) return -1;
+    for (int q = 0; q < n; ++q) {
+        const int32_t org[2] = {R.ql[q], R.qr[q]}, cov[2] = {o1[q].l, o1[q].r};
+        // (blkaln's return value: 0 only when findblock found nothing -- the range is then as it was, and nothing is left over)
+        int32_t rests[4];
+        const int nr = o1[q].loci.empty() ? 0 : spdp_dispersed_rests(org, cov, min_seg_len, rests);
+        // (which rest it is stands in the rest itself: the left one begins where the query's range begins and ends where cov begins)
+        for (int k = 0; k < nr; ++k) rest.push_back({q, rests[2 * k], rests[2 * k + 1], rests[2 * k] == org[0] && rests[2 * k + 1] == cov[0] ? 1 : 2});
+        if (covered) {                                  // in the positions of the query as given: the preparation may have turned it
+            const int32_t len = (int32_t) (R.offs[q + 1] - R.offs[q]);
+            covered[2 * q] = R.prep_turned(q) ? len - cov[1] : cov[0];
+            covered[2 * q + 1] = R.prep_turned(q) ? len - cov[0] : cov[1];
+        }
+    }
+    if (dispersed_pass(R, rest, false, vthr, o2)) return -1;
+    Reported rep(n);
+    std::vector<std::vector<int32_t>> parts(n);
+    auto report = [&](const Piece& pc, PieceOut& po) {
+        const size_t before = rep.genes[pc.q].size();
+        select_printed(po.loci, 1, 0, vthr, rep.genes[pc.q], rep.ex[pc.q]);
+        parts[pc.q].resize(parts[pc.q].size() + (rep.genes[pc.q].size() - before), pc.part);
+    };
+    for (int q = 0; q < n; ++q) report(first[q], o1[q]);
+    for (size_t k = 0; k < rest.size(); ++k) report(rest[k], o2[k]);       // (a query's left rest stands before its right one)
+    if (hand_out(R.ctx, who, rep, n, gene_off, genes, exons)) return -1;
+    *part = (int32_t*) malloc(sizeof(int32_t) * std::max<size_t>((size_t) gene_off[n], 1));
+    if (!*part) { free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; R.ctx->err = std::string(who) + ": out of memory"; return -1; }
+    size_t k = 0;
+    for (int q = 0; q < n; ++q) for (int32_t v : parts[q]) (*part)[k++] = v;
+    return 0;
+}
+
+// what both dispersed entries refuse before anything is launched
+int check_dispersed(SpdpContext* ctx, const char* who, const SpdpBlkFindParams* fprm, const SpdpSeedParams* sp, int32_t min_seg_len)
+{
+    if (!fprm || !sp) { ctx->err = std::string(who) + ": null argument"; return -1; }
+    if (min_seg_len <= 0) { ctx->err = std::string(who) + ": min_seg_len must be > 0 (the program's MinSegLen = 2 Ktuple + Nshift of the index)"; return -1; }
+    if (fprm->max_out != 1) { ctx->err = std::string(who) + ": max_out must be 1 (-pr together with -M N is another mode)"; return -1; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int spdp_map_align_s_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                          const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                          const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                          const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, const SpdpQueryPrep* prep,
+                                          int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                                          int32_t* covered, double* seconds, SpdpQueryTail* tails)
+{
+    const char* who = "spdp_map_align_s_dispersed";
+    if (!ctx) return -1;
+    if (!gene_off || !genes || !exons || !part) { ctx->err = std::string(who) + ": null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr; *part = nullptr;
+    if (check_dispersed(ctx, who, fprm, sp, min_seg_len)) return -1;
+    try {
+        ChainS R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, std::max(n, 0), ori};
+        if (R.setup(prep, prep != nullptr, tails)) return -1;
+        if (dispersed(R, who, min_seg_len, gene_off, genes, exons, part, covered)) return -1;
+        return R.finish(seconds);
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = std::string(who) + ": out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; free(*part); *part = nullptr;
+        return -1;
+    }
+}
+
+extern "C" int spdp_map_align_h_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                          const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
+                                          const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+                                          const uint8_t* codes, const int64_t* offs, int32_t n, int32_t min_seg_len,
+                                          int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                                          int32_t* covered, double* seconds)
+{
+    const char* who = "spdp_map_align_h_dispersed";
+    if (!ctx) return -1;
+    if (!gene_off || !genes || !exons || !part) { ctx->err = std::string(who) + ": null argument"; return -1; }
+    *genes = nullptr; *exons = nullptr; *part = nullptr;
+    if (check_dispersed(ctx, who, fprm, sp, min_seg_len)) return -1;
+    try {
+        ChainH R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, std::max(n, 0)};
+        if (R.setup()) return -1;
+        if (dispersed(R, who, min_seg_len, gene_off, genes, exons, part, covered)) return -1;
+        return R.finish(seconds);
+    }
+    catch (const std::bad_alloc&) {
+        ctx->err = std::string(who) + ": out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
+        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; free(*part); *part = nullptr;
         return -1;
     }
 }

@@ -36,7 +36,20 @@ EXPORTS = [
     "spdp_blk_index_create", "spdp_blk_index_destroy", "spdp_blk_vote", "spdp_blk_vote_resident",
     "spdp_blk_search_opts_default", "spdp_blk_index_read", "spdp_blk_index_host_desc", "spdp_blk_index_host_free",
     "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan",
+    "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
 ]
+
+
+def dispersed_rests(lib, org, cov, min_seg_len: int):
+    """spdp_dispersed_rests: the stretches of a query `spaln -pr` searches again after its first search left the query's range
+    org = (left, right) at cov -- quick4's rule, on the host (no device, no context).  Returns [(left, right)], left rest first."""
+    o = (C.c_int32 * 2)(*(int(x) for x in org))
+    c = (C.c_int32 * 2)(*(int(x) for x in cov))
+    r = (C.c_int32 * 4)()
+    k = lib.spdp_dispersed_rests(o, c, int(min_seg_len), r)
+    if k < 0:
+        raise RuntimeError("spdp_dispersed_rests: null argument")
+    return [(r[2 * i], r[2 * i + 1]) for i in range(k)]
 
 
 def load_library() -> C.CDLL:
@@ -95,6 +108,8 @@ def load_library() -> C.CDLL:
     for f in ("spdp_submit_align_s", "spdp_submit_homscore_s", "spdp_submit_align_h", "spdp_submit_homscore_h"):
         getattr(lib, f).restype = C.c_void_p
         getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.spdp_dispersed_rests.restype = C.c_int
+    lib.spdp_dispersed_rests.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.spdp_poll.argtypes = [C.c_void_p]
     lib.spdp_wait.argtypes = [C.c_void_p]
     lib.spdp_lsp_s.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
