@@ -1160,6 +1160,63 @@ int spdp_group_map_align_h_multi(SpdpGroup* g, const SpdpBlkIndex* const* ix, co
                                  const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
                                  int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons);
 
+/* ======================================================================== */
+/* unspliced alignment (protein x protein; any two sequences of one alphabet): Aln2b1, src/fwd2b1.cc       */
+/*   VTYPE HomScoreB_ng(const Seq* seqs[], const PwdB* pwd)          src/fwd2b1.cc:1562                    */
+/*   SKL*  alignB_ng(const Seq* seqs[], const PwdB*, Gsinfo*)        src/fwd2b1.cc:1601                    */
+/*   VTYPE skl_rngB_ng(const Seq* seqs[], Gsinfo*, const PwdB*)      src/fwd2b1.cc:295                     */
+/* What the program runs for two protein files (AvsA, src/spaln.cc:675, 713); it reads its FIRST file as b */
+/* and its second as a.  DP row m in (a_left, a_right] is residue a[m-1], column n in (b_left, b_right] is */
+/* b[n-1]; diagonals are r = n - m.                                                                        */
+/* SpdpScoring and SpdpProblem are reused as they are.  Read: mtx_dim, mtx, gop, gep, lgop, lgep, noll,    */
+/* codonk1 (noll == 3), local, sh; the problems' sequences, ranges and exg* flags.  spj must be 0 and      */
+/* scalar_engines 1 (the -A0 engine; the int16 SIMD flavours -A1 .. -A3 of Aln2b1 are not reproduced: on   */
+/* proteins of 340 .. 700 residues they print lower scores than -A0, or nothing).  Anything else is        */
+/* refused with -1 and a message that names the field.  sig5 / sig3 and the exact-model inputs are not read.*/
+/* There is NO linear-space form.  The reference enters hirschbergB_ng when 2 x (band cells) reaches       */
+/* MaxVmfSpace (src/fwd2b1.cc:1280; at the default 32 MB: beyond about 4 000 x 4 000 residues), and that   */
+/* branch is not sound on proteins: with -V lowered so that it runs, -A0 printed a two-corner record of    */
+/* 237.6 instead of 411.3 at 111 x 120 and of 180.4 instead of 2 354.8 at 642 x 700, and nothing at        */
+/* 373 x 400.  Every problem here takes the direct traceback, whatever its size, within the trace budget.  */
+/* ======================================================================== */
+typedef struct SpdpUnsplicedParams {
+    float   tgapf;                   /* alprm.tgapf (-yt; 1.0 in the program): factor on gaps at a sequence's very ends   */
+    int64_t max_trace_bytes;         /* device bytes one chunk's traceback store may take; 0 = the library's default (4 GiB) */
+} SpdpUnsplicedParams;
+
+/* alignB_ng with algmode.qck = 0: stripe(), the direct part of lspB_ng (empty ranges, diagonalB_ng, otherwise
+ * trcbkalignB_ng = forwardB_ng + Vmf::traceback + the record fix-up), globalB_ng's header record and stdskl.  out[i].skl =
+ * header {m = 1, n = corners} + corners, not yet trimmed (skl_rngB_ng trims: spdp_skl_rng_b).  A local problem without a
+ * positive cell comes back with score SPDP_NEVSEL and n_skl = 0.  The batch runs in chunks whose traceback stores fit
+ * max_trace_bytes; a problem that alone exceeds it comes back "not computed" (score SPDP_NEVSEL, n_skl 0) and the call
+ * returns 1 after serving all others. */
+int spdp_align_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
+                 const SpdpProblem* probs, int n_probs, SpdpAlignment* out);
+/* HomScoreB_ng under -A0: stripe() + scorealoneB_ng (src/fwd2b1.cc:969).  No traceback store, no budget. */
+int spdp_homscore_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
+                    const SpdpProblem* probs, int n_probs, int32_t* scores);
+
+/* skl_rngB_ng on the host (a sequential walk over the corners): fstat and the alignment span.  gap and unp are sums of
+ * tgapf-weighted counts, floats as in the reference's FSTAT.  first .. first + n_trim are the corners trimskl leaves
+ * (indices into aln[i].skl): what the program prints.  Alignments of n_skl < 3 come back zeroed. */
+typedef struct SpdpRescoredB {
+    int32_t val;                     /* return value = fstat.val: the score the program prints (divided by alprm.scale) */
+    int32_t mch, mmc;
+    float   gap, unp;
+    int32_t span;
+    int32_t first, n_trim;
+} SpdpRescoredB;
+int spdp_skl_rng_b(const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpProblem* probs, int n_probs,
+                   const SpdpAlignment* aln, SpdpRescoredB* out);
+/* the Cigar / Vulgar / SAM records skl_rngB_ng pushes (src/fwd2b1.cc:317-388), one format per call; release with
+ * spdp_free_edits.  SAM fields as for a forward-strand hit. */
+int spdp_skl_edits_b(const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpProblem* probs, int n_probs,
+                     const SpdpAlignment* aln, int format, SpdpEdits* out);
+/* DP cells forwardB_ng visits for one problem in the band wdw */
+int64_t spdp_cells_b(const SpdpProblem* p, const SpdpWindow* wdw);
+/* device bytes of one problem's traceback store (what is held against max_trace_bytes) */
+int64_t spdp_trace_bytes_b(const SpdpProblem* p, const SpdpWindow* wdw);
+
 #ifdef __cplusplus
 }
 #endif

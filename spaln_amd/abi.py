@@ -310,6 +310,16 @@ class ProblemSet:
         return arr
 
 
+# ---- unspliced alignment (Aln2b1): Scoring / Problem / ProblemSet are reused as they are (sig5 = sig3 = None) ----------
+class UnsplicedParams(C.Structure):      # SpdpUnsplicedParams
+    _fields_ = [("tgapf", C.c_float), ("max_trace_bytes", C.c_int64)]
+
+
+class RescoredB(C.Structure):            # SpdpRescoredB
+    _fields_ = [("val", C.c_int32), ("mch", C.c_int32), ("mmc", C.c_int32), ("gap", C.c_float), ("unp", C.c_float),
+                ("span", C.c_int32), ("first", C.c_int32), ("n_trim", C.c_int32)]
+
+
 # ---- protein x genome (Fwd2h1 `_wip`) ------------------------------------------------------
 class ScoringH(C.Structure):
     _fields_ = [

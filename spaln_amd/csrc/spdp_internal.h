@@ -340,8 +340,9 @@ struct TilePipe {
 };
 
 // SpdpContext::pool: runs that may be in flight together never share one.  The first five: DevRun's (RUN_TRAITS below); H_POOL / HU_POOL: the
-// aa x genome path's inputs + traceback runs / linear-space runs; R_POOL: rescoring; SIDE_POOL: a DevRun on the side stream, of any flavour
-enum CtxPool { WIP_SCORE_POOL = 0, WIP_FORWARD_POOL, WIP_UDH_POOL, EXACT_FORWARD_POOL, EXACT_POOL, H_POOL, HU_POOL, R_POOL, SIDE_POOL, N_CTX_POOLS };
+// aa x genome path's inputs + traceback runs / linear-space runs; R_POOL: rescoring; SIDE_POOL: a DevRun on the side stream, of any flavour;
+// B_POOL: the unspliced aligner (spdp_b_api.cpp)
+enum CtxPool { WIP_SCORE_POOL = 0, WIP_FORWARD_POOL, WIP_UDH_POOL, EXACT_FORWARD_POOL, EXACT_POOL, H_POOL, HU_POOL, R_POOL, SIDE_POOL, B_POOL, N_CTX_POOLS };
 struct SpdpContext {
     DevPool pool[N_CTX_POOLS];
     int device = 0;

@@ -90,6 +90,38 @@ def scoring_h(nquant=None, **over) -> abi.ScoringH:
     return abi.make_scoring_h(**kw)
 
 
+# ---- protein x protein (the unspliced aligner, Aln2b1): PwdB set-up for DvsP = 3 ------------------------------------
+# What `spaln -Q0` applies to two protein files by default: u = 2, v = 9, u1 = 0.6, k1 = 7 (-yl3 only), thr = 35, scores
+# scaled by 10, band shoulder 100.  The substitution matrix and the gap terms were read off the program's printed scores
+# (tests/golden/make_b_goldens.py: all 1 x 1 pairs; pairs that differ by one block) and are kept with the other recorded
+# outputs, in tests/golden/b_aa_params.json; tests/test_unspliced_ref.py proves them with the rescoring identity.
+B_GOP, B_GEP, B_LGOP, B_LGEP, B_K1 = -90, -20, -188, -6, 7
+B_THR, B_SCALE, B_DIM = 350, 10, 23
+
+
+def matrix_b() -> np.ndarray:
+    """23 x 23 by the reference's amino-acid codes (A = 3 .. V = 22, synth.encode_protein); other codes score 0"""
+    import json
+    import os
+    from . import synth
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "b_aa_params.json")
+    with open(path) as f:
+        doc = json.load(f)
+    assert (doc["gop"], doc["gep"], doc["lgop"], doc["lgep"], doc["k1"], doc["scale"]) == (B_GOP, B_GEP, B_LGOP, B_LGEP, B_K1, B_SCALE)
+    code = synth.encode_protein(np.frombuffer(doc["alphabet"].encode(), dtype=np.uint8))
+    mtx = np.zeros((B_DIM, B_DIM), dtype=np.int32)
+    mtx[np.ix_(code, code)] = np.asarray(doc["mtx"], dtype=np.int32)
+    return mtx
+
+
+def scoring_b(noll=2, local=0, sh=SH, **over) -> abi.Scoring:
+    """the bundle of spdp_align_b / spdp_homscore_b for protein pairs (noll = 3: -yl3; local = 1: -LS)"""
+    kw = dict(mtx=matrix_b(), mtx_dim=B_DIM, gop=B_GOP, gep=B_GEP, lgop=B_LGOP, lgep=B_LGEP, noll=noll, spj=0, local=local, sh=sh,
+              scalar_engines=1, codonk1=B_K1)
+    kw.update(over)
+    return abi.make_scoring(**kw)
+
+
 # MakeBlk::prepacomp's per-class terms of the translated block index's word scores (src/blksrc.cc:844-877) for the reference's defaults
 # (twenty classes, -Xp20, -Xq1, its mdm tables) -- recorded from the compiled reference (`spaln_idxtap -W -KP`, oracle/ref_build/idx_tap.cc:
 # the "[idx_tap] acomp" line, exact hex floats); spdp_blk_index_build_p's acomp

@@ -37,6 +37,7 @@ EXPORTS = [
     "spdp_blk_search_opts_default", "spdp_blk_index_read", "spdp_blk_index_host_desc", "spdp_blk_index_host_free",
     "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan",
     "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
+    "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
 ]
 
 
@@ -63,6 +64,11 @@ def load_library() -> C.CDLL:
     lib.spdp_last_error.argtypes = [C.c_void_p]
     lib.spdp_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.spdp_cells.restype = C.c_int64
+    lib.spdp_cells_b.restype = lib.spdp_trace_bytes_b.restype = C.c_int64
+    lib.spdp_align_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+    lib.spdp_homscore_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+    lib.spdp_skl_rng_b.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.spdp_skl_edits_b.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.spdp_splice_signals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.spdp_splice_signals_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
@@ -689,6 +695,82 @@ class Engine:
         return scores, cpos, ranges
 
     # ---- aa x genome (SimdAln2h1 `_wip`) ------------------------------------------------
+    # ---- unspliced alignment (Aln2b1, protein x protein): include/spdp.h "unspliced alignment" -------------------------
+    def align_b(self, sc, up: abi.UnsplicedParams, ps, allow_partial=False):
+        """alignB_ng (-Q0, -A0): [(score, skl)] with skl = header row + corners as globalB_ng returns them (not yet trimmed:
+        skl_rng_b says which corners the program prints).  allow_partial: accept return value 1 (a problem above
+        up.max_trace_bytes came back with score NEVSEL and no corners).  last_call_s = seconds spent in the library."""
+        import time
+        n = len(ps)
+        arr = (abi.Alignment * n)()
+        probs = ps.array()
+        t0 = time.perf_counter()
+        rc = self.lib.spdp_align_b(self.ctx, C.byref(sc), C.byref(up), probs, n, arr)
+        self.last_call_s = time.perf_counter() - t0
+        if not (allow_partial and rc == 1):
+            self._check(rc, "spdp_align_b")
+        res = []
+        for i in range(n):
+            k = arr[i].n_skl
+            skl = np.ctypeslib.as_array(C.cast(arr[i].skl, C.POINTER(C.c_int32)), shape=(k, 2)).copy() if k else np.zeros((0, 2), dtype=np.int32)
+            res.append((int(arr[i].score), skl))
+        self.lib.spdp_free_alignments(arr, n)
+        return res
+
+    def homscore_b(self, sc, up: abi.UnsplicedParams, ps) -> np.ndarray:
+        """HomScoreB_ng under -A0 (scorealoneB_ng)"""
+        out = np.zeros(len(ps), dtype=np.int32)
+        self._check(self.lib.spdp_homscore_b(self.ctx, C.byref(sc), C.byref(up), ps.array(), len(ps), out.ctypes.data_as(C.c_void_p)),
+                    "spdp_homscore_b")
+        return out
+
+    def _alignment_array(self, alignments):
+        n = len(alignments)
+        keep = []
+        arr = (abi.Alignment * n)()
+        for i, skl in enumerate(alignments):
+            skl = np.ascontiguousarray(skl, dtype=np.int32).reshape(-1, 2)
+            keep.append(skl)
+            arr[i].score, arr[i].n_skl = 0, skl.shape[0]
+            arr[i].skl = C.cast(skl.ctypes.data, C.POINTER(abi.Skl))
+        return arr, keep
+
+    def skl_rng_b(self, sc, up: abi.UnsplicedParams, ps, alignments):
+        """skl_rngB_ng over finished alignments (as align_b returns them): per pair a dict val, mch, mmc, gap, unp, span and
+        first / n_trim -- rows first .. first + n_trim of the alignment are the corners the program prints (trimskl)"""
+        n = len(ps)
+        arr, keep = self._alignment_array(alignments)
+        out = (abi.RescoredB * n)()
+        if self.lib.spdp_skl_rng_b(C.byref(sc), C.byref(up), ps.array(), n, arr, out) != 0:
+            raise RuntimeError("spdp_skl_rng_b: refused (scoring bundle, problem or corner list)")
+        return [{f: getattr(out[i], f) for f, _ in abi.RescoredB._fields_} for i in range(n)]
+
+    def skl_edits_b(self, sc, up: abi.UnsplicedParams, ps, alignments, fmt):
+        """the Cigar / Vulgar / SAM records skl_rngB_ng pushes (fmt = abi.FMT_*): per pair (records (k x 3: op, alen, blen),
+        [sam_flag, sam_pos, sam_mapq, sam_left, sam_right])"""
+        n = len(ps)
+        arr, keep = self._alignment_array(alignments)
+        out = (abi.Edits * n)()
+        if self.lib.spdp_skl_edits_b(C.byref(sc), C.byref(up), ps.array(), n, arr, int(fmt), out) != 0:
+            raise RuntimeError("spdp_skl_edits_b: refused (scoring bundle, problem, corner list or format)")
+        res = []
+        for i in range(n):
+            k = out[i].n
+            rec = np.ctypeslib.as_array(C.cast(out[i].rec, C.POINTER(C.c_int32)), shape=(k, 3)).copy() if k else np.zeros((0, 3), dtype=np.int32)
+            res.append((rec, [out[i].sam_flag, out[i].sam_pos, out[i].sam_mapq, out[i].sam_left, out[i].sam_right]))
+        self.lib.spdp_free_edits(out, n)
+        return res
+
+    def cells_b(self, p: abi.Problem, sh: int) -> int:
+        w = abi.Window()
+        self.lib.spdp_stripe(C.byref(p), C.c_int(int(sh)), C.byref(w))
+        return int(self.lib.spdp_cells_b(C.byref(p), C.byref(w)))
+
+    def trace_bytes_b(self, p: abi.Problem, sh: int) -> int:
+        w = abi.Window()
+        self.lib.spdp_stripe(C.byref(p), C.c_int(int(sh)), C.byref(w))
+        return int(self.lib.spdp_trace_bytes_b(C.byref(p), C.byref(w)))
+
     def _alignments_h(self, fn, sc, ps, what):
         """[(score, records, flag)]: flag 0 ok, -1 the reference's fatal "Unexpected dir", -2 its
         traceback starts outside its bitmap, 1 the problem needs an engine that is not built."""
