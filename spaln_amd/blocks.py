@@ -296,42 +296,6 @@ def find_params_from_fixture(fx) -> BlkFindParams:
     return p
 
 
-def find(index: "BlockIndex", genome_codes, chr_off, model, sc, prm: BlkFindParams, queries, ranges=None):
-    """spdp_blk_find: the block search of every query up to its candidate loci.  Returns (per query a list of dicts
-    {chr, rvs, base, len, left, right, jscr, hsps (n + 1, 5)}, status array)."""
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    offs[1:] = np.cumsum([len(q) for q in queries])
-    codes = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
-    left = np.array([0 if ranges is None else ranges[i][0] for i in range(n)], dtype=np.int32)
-    right = np.array([len(queries[i]) if ranges is None else ranges[i][1] for i in range(n)], dtype=np.int32)
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    loci = C.POINTER(Locus)()
-    hsps = C.POINTER(C.c_int32)()
-    nl = C.c_int32()
-    status = np.zeros(n, dtype=np.int32)
-    lib.spdp_blk_find.restype = C.c_int
-    lib.spdp_blk_find.argtypes = [C.c_void_p] * 11 + [C.c_int32] + [C.c_void_p] * 4
-    rc = lib.spdp_blk_find(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.addressof(model), C.byref(sc), C.byref(prm),
-                           codes.ctypes.data, offs.ctypes.data, left.ctypes.data, right.ctypes.data, n,
-                           C.byref(loci), C.byref(nl), C.byref(hsps), status.ctypes.data)
-    eng._check(rc, "spdp_blk_find")
-    out = [[] for _ in range(n)]
-    for k in range(nl.value):
-        L = loci[k]
-        h = np.array([[hsps[5 * (L.hsp_off + j) + c] for c in range(5)] for j in range(L.n_hsp + 1)], dtype=np.int32)
-        out[L.query].append(dict(chr=L.chr, rvs=L.rvs, base=L.base, len=L.len, left=L.left, right=L.right, jscr=L.jscr, hsps=h))
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(loci)
-    libc.free(hsps)
-    return out, status
-
-
 class MapExon(C.Structure):
     _fields_ = [("q_left", C.c_int32), ("q_right", C.c_int32), ("g_left", C.c_int32), ("g_right", C.c_int32)]
 
@@ -339,152 +303,6 @@ class MapExon(C.Structure):
 class MapGene(C.Structure):
     _fields_ = [("chr", C.c_int32), ("rvs", C.c_int32), ("q_rev", C.c_int32), ("score", C.c_int32), ("val", C.c_int32), ("n_loci", C.c_int32),
                 ("n_exons", C.c_int32), ("exon_off", C.c_int64)]
-
-
-def map_align(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1):
-    """spdp_map_align_s: block search -> loci -> signals -> seeded alignment -> rescoring, one call for all queries.
-    rescore = (codonk1, minl, jneibr, lsg).  Returns (per query None or dict(chr, rvs, score, val, n_loci,
-    exons = [(q_left, q_right, g_left, g_right)]), seconds [find, regions + signals, align, rescore], return code)."""
-    from . import abi
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    offs[1:] = np.cumsum([len(q) for q in queries])
-    codes = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    rp = abi.RescoreParams(*(int(x) for x in rescore))
-    genes = (MapGene * n)()
-    exons = C.POINTER(MapExon)()
-    sec = (C.c_double * 4)()
-    lib.spdp_map_align_s.restype = C.c_int
-    lib.spdp_map_align_s.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
-    rc = lib.spdp_map_align_s(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel),
-                              C.byref(prm), C.byref(rp), codes.ctypes.data, offs.ctypes.data, n, int(ori), genes, C.byref(exons), sec)
-    if rc < 0:
-        eng._check(rc, "spdp_map_align_s")
-    out = []
-    for i in range(n):
-        G = genes[i]
-        if G.chr < 0:
-            out.append(None)
-            continue
-        ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
-              for j in range(G.n_exons)]
-        out.append(dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex))
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(exons)
-    return out, list(sec), rc
-
-
-def map_align_h(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries):
-    """spdp_map_align_h: the same for protein queries against the translated index.  sc: abi.ScoringH; rescore = abi.RescoreParamsH;
-    Returns as map_align."""
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    offs[1:] = np.cumsum([len(q) for q in queries])
-    codes = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    genes = (MapGene * n)()
-    exons = C.POINTER(MapExon)()
-    sec = (C.c_double * 4)()
-    lib.spdp_map_align_h.restype = C.c_int
-    lib.spdp_map_align_h.argtypes = [C.c_void_p] * 11 + [C.c_int32] + [C.c_void_p] * 3
-    rc = lib.spdp_map_align_h(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel),
-                              C.byref(prm), C.byref(rescore), codes.ctypes.data, offs.ctypes.data, n, genes, C.byref(exons), sec)
-    if rc < 0:
-        eng._check(rc, "spdp_map_align_h")
-    out = []
-    for i in range(n):
-        G = genes[i]
-        if G.chr < 0:
-            out.append(None)
-            continue
-        ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
-              for j in range(G.n_exons)]
-        out.append(dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex))
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(exons)
-    return out, list(sec), rc
-
-
-def _multi_call(index: "BlockIndex", fn: str, genome_codes, chr_off, args_before, queries, args_after):
-    """the call of a _multi entry and its lists: (per query a list of dicts shaped as map_align's, in print order), seconds, rc"""
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    offs[1:] = np.cumsum([len(q) for q in queries])
-    codes = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    gene_off = np.zeros(n + 1, dtype=np.int64)
-    genes = C.POINTER(MapGene)()
-    exons = C.POINTER(MapExon)()
-    sec = (C.c_double * 4)()
-    f = getattr(lib, fn)
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 11 + [C.c_int32] * (1 + len(args_after)) + [C.c_void_p] * 4
-    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), *args_before, codes.ctypes.data, offs.ctypes.data, n, *args_after,
-           gene_off.ctypes.data, C.byref(genes), C.byref(exons), sec)
-    if rc < 0:
-        eng._check(rc, fn)
-    out = []
-    for i in range(n):
-        lst = []
-        for k in range(int(gene_off[i]), int(gene_off[i + 1])):
-            G = genes[k]
-            ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
-                  for j in range(G.n_exons)]
-            lst.append(dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex))
-        out.append(lst)
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(genes)
-    libc.free(exons)
-    return out, list(sec), rc
-
-
-def map_align_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1,
-                    all_out: bool = False):
-    """spdp_map_align_s_multi: what `spaln -M N` prints of every query -- up to prm.max_out loci, highest fstat.val first, the
-    threshold sp.vthr applied unless all_out (-pw); a locus printed though the threshold dropped it has score abi.NEVSEL.  The
-    index must have been made for prm.max_out (ncand = max_out + 10).  ori = 3: every locus picks its orientation on its own; the
-    program aligns a query's further loci with the query left reverse-complemented after a locus that took that orientation, so
-    such a query's later loci can differ from spaln's (include/spdp.h).
-    Returns (per query a list of dicts shaped as map_align's, in print order; seconds; return code)."""
-    from . import abi
-    rp = abi.RescoreParams(*(int(x) for x in rescore))
-    return _multi_call(index, "spdp_map_align_s_multi", genome_codes, chr_off,
-                       (C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp)), queries, (int(ori), int(bool(all_out))))
-
-
-def map_align_h_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries,
-                      all_out: bool = False):
-    """spdp_map_align_h_multi: the same for protein queries against the translated index (arguments as map_align_h's)"""
-    return _multi_call(index, "spdp_map_align_h_multi", genome_codes, chr_off,
-                       (C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rescore)), queries, (int(bool(all_out)),))
-
-
-# ---- query preparation (include/spdp.h "query preparation"): poly-A tails, poly-T heads, the orientation of a cDNA query
-class QueryPrep(C.Structure):            # SpdpQueryPrep
-    _fields_ = [("q_mns", C.c_int32), ("polya_thr", C.c_int32)]
-
-
-class QueryTail(C.Structure):            # SpdpQueryTail
-    _fields_ = [(k, C.c_int32) for k in ("pol", "tlen", "left", "right", "ori")] + [("reserved", C.c_int32 * 3)]
-
-
-TAIL_FIELDS = ("pol", "tlen", "left", "right", "ori")
 
 
 def _packed(queries, lead: int = 0):
@@ -499,9 +317,146 @@ def _packed(queries, lead: int = 0):
     return codes, offs
 
 
+def _gene(G, exons):
+    ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
+          for j in range(G.n_exons)]
+    return dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex)
+
+
+def _free(*ptrs):
+    """what an entry malloc'ed for its caller"""
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    for p in ptrs:
+        libc.free(p)
+
+
+class _Call:
+    """One call of an entry that searches the genome for a batch of queries.  Every such entry begins (ctx, index, its description,
+    genome, `models` ..., codes, offs, ...): this holds the packed queries, the Genome and the arrays they point into while the
+    call runs and its outputs are read.  run() sets the entry's types from the arguments it is given -- a Python int is an int32, a
+    numpy array its data, everything else a pointer -- and raises on a negative return code."""
+
+    def __init__(self, index: "BlockIndex", genome_codes, chr_off, queries, *models):
+        self.lib, self.eng, self.n = index.lib, index.eng, len(queries)
+        self.codes, self.offs = _packed(queries)
+        self._gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+        self._go = np.ascontiguousarray(chr_off, dtype=np.int64)
+        self.g = Genome(self._gc.ctypes.data, self._go.ctypes.data, len(self._go) - 1)
+        self.sec = (C.c_double * 4)()
+        self._head = (C.c_void_p(index.eng.ctx), C.c_void_p(index.h), C.byref(index.desc), C.byref(self.g)) + models + (self.codes, self.offs)
+
+    def run(self, fn: str, *rest) -> int:
+        args = [C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else a for a in self._head + rest]
+        f = getattr(self.lib, fn)
+        f.restype = C.c_int
+        f.argtypes = [C.c_int32 if isinstance(a, int) else C.c_void_p for a in args]
+        rc = f(*args)
+        if rc < 0:
+            self.eng._check(rc, fn)
+        return rc
+
+    def best(self, fn: str, *middle, tails=()):
+        """an entry that reports one gene per query: (per query None or its dict, seconds, return code)"""
+        genes = (MapGene * max(self.n, 1))()
+        exons = C.POINTER(MapExon)()
+        rc = self.run(fn, self.n, *middle, genes, C.byref(exons), self.sec, *tails)
+        out = [None if genes[i].chr < 0 else _gene(genes[i], exons) for i in range(self.n)]
+        _free(exons)
+        return out, list(self.sec), rc
+
+    def lists(self, fn: str, *middle, more=(), tails=()):
+        """an entry that reports a list of genes per query (more: further outputs behind the three every such entry has):
+        (per query the list of its dicts, in the entry's order; seconds; return code)"""
+        gene_off = np.zeros(self.n + 1, dtype=np.int64)
+        genes, exons = C.POINTER(MapGene)(), C.POINTER(MapExon)()
+        rc = self.run(fn, self.n, *middle, gene_off, C.byref(genes), C.byref(exons), *more, self.sec, *tails)
+        out = [[_gene(genes[k], exons) for k in range(int(gene_off[i]), int(gene_off[i + 1]))] for i in range(self.n)]
+        _free(genes, exons)
+        return out, list(self.sec), rc
+
+
+def _rp_s(rescore):
+    """map_align's (codonk1, minl, jneibr, lsg) as the cDNA entries take it"""
+    from . import abi
+    return abi.RescoreParams(*(int(x) for x in rescore))
+
+
+def _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, rp, queries) -> _Call:
+    """the arguments every map + align entry begins with"""
+    return _Call(index, genome_codes, chr_off, queries, C.byref(sc), C.byref(sp), C.c_void_p(C.addressof(sigmodel)), C.byref(prm), C.byref(rp))
+
+
+def find(index: "BlockIndex", genome_codes, chr_off, model, sc, prm: BlkFindParams, queries, ranges=None):
+    """spdp_blk_find: the block search of every query up to its candidate loci.  Returns (per query a list of dicts
+    {chr, rvs, base, len, left, right, jscr, hsps (n + 1, 5)}, status array)."""
+    call = _Call(index, genome_codes, chr_off, queries, C.c_void_p(C.addressof(model)), C.byref(sc), C.byref(prm))
+    n = call.n
+    left = np.array([0 if ranges is None else ranges[i][0] for i in range(n)], dtype=np.int32)
+    right = np.array([len(queries[i]) if ranges is None else ranges[i][1] for i in range(n)], dtype=np.int32)
+    loci = C.POINTER(Locus)()
+    hsps = C.POINTER(C.c_int32)()
+    nl = C.c_int32()
+    status = np.zeros(n, dtype=np.int32)
+    call.eng._check(call.run("spdp_blk_find", left, right, n, C.byref(loci), C.byref(nl), C.byref(hsps), status), "spdp_blk_find")
+    out = [[] for _ in range(n)]
+    for k in range(nl.value):
+        L = loci[k]
+        h = np.array([[hsps[5 * (L.hsp_off + j) + c] for c in range(5)] for j in range(L.n_hsp + 1)], dtype=np.int32)
+        out[L.query].append(dict(chr=L.chr, rvs=L.rvs, base=L.base, len=L.len, left=L.left, right=L.right, jscr=L.jscr, hsps=h))
+    _free(loci, hsps)
+    return out, status
+
+
+def map_align(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1):
+    """spdp_map_align_s: block search -> loci -> signals -> seeded alignment -> rescoring, one call for all queries.
+    rescore = (codonk1, minl, jneibr, lsg).  Returns (per query None or dict(chr, rvs, score, val, n_loci,
+    exons = [(q_left, q_right, g_left, g_right)]), seconds [find, regions + signals, align, rescore], return code)."""
+    return _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, _rp_s(rescore), queries).best("spdp_map_align_s", int(ori))
+
+
+def map_align_h(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries):
+    """spdp_map_align_h: the same for protein queries against the translated index.  sc: abi.ScoringH; rescore = abi.RescoreParamsH;
+    Returns as map_align."""
+    return _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries).best("spdp_map_align_h")
+
+
+def map_align_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1,
+                    all_out: bool = False):
+    """spdp_map_align_s_multi: what `spaln -M N` prints of every query -- up to prm.max_out loci, highest fstat.val first, the
+    threshold sp.vthr applied unless all_out (-pw); a locus printed though the threshold dropped it has score abi.NEVSEL.  The
+    index must have been made for prm.max_out (ncand = max_out + 10).  ori = 3: every locus picks its orientation on its own; the
+    program aligns a query's further loci with the query left reverse-complemented after a locus that took that orientation, so
+    such a query's later loci can differ from spaln's (include/spdp.h).
+    Returns (per query a list of dicts shaped as map_align's, in print order; seconds; return code)."""
+    c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, _rp_s(rescore), queries)
+    return c.lists("spdp_map_align_s_multi", int(ori), int(bool(all_out)))
+
+
+def map_align_h_multi(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries,
+                      all_out: bool = False):
+    """spdp_map_align_h_multi: the same for protein queries against the translated index (arguments as map_align_h's)"""
+    return _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries).lists("spdp_map_align_h_multi", int(bool(all_out)))
+
+
+# ---- query preparation (include/spdp.h "query preparation"): poly-A tails, poly-T heads, the orientation of a cDNA query
+class QueryPrep(C.Structure):            # SpdpQueryPrep
+    _fields_ = [("q_mns", C.c_int32), ("polya_thr", C.c_int32)]
+
+
+class QueryTail(C.Structure):            # SpdpQueryTail
+    _fields_ = [(k, C.c_int32) for k in ("pol", "tlen", "left", "right", "ori")] + [("reserved", C.c_int32 * 3)]
+
+
+TAIL_FIELDS = ("pol", "tlen", "left", "right", "ori")
+
+
+def _tail_records(tails, n):
+    return np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
+
+
 def _tails_out(tails, codes_out, offs, n):
-    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
-    return rec, [codes_out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)]
+    return _tail_records(tails, n), [codes_out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)]
 
 
 def _hip_runtime():
@@ -569,83 +524,37 @@ def polya_scan(eng, queries, q_mns: int = 3, polya_thr: int = 12, lead: int = 0,
         for b in bufs:
             if b:
                 hip.hipFree(b)
-    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
-    return rec, [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)], ms.value
-
-
-def _gene(G, exons):
-    ex = [(exons[G.exon_off + j].q_left, exons[G.exon_off + j].q_right, exons[G.exon_off + j].g_left, exons[G.exon_off + j].g_right)
-          for j in range(G.n_exons)]
-    return dict(chr=G.chr, rvs=G.rvs, q_rev=G.q_rev, score=G.score, val=G.val, n_loci=G.n_loci, exons=ex)
-
-
-def _prep_call(index, fn, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns, polya_thr, middle, outs):
-    """the inputs the two _prep entries share, the call, the records: middle = the integers between prep and the outputs"""
-    from . import abi
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    codes, offs = _packed(queries)
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    rp = abi.RescoreParams(*(int(x) for x in rescore))
-    prep = QueryPrep(int(q_mns), int(polya_thr))
-    tails = (QueryTail * max(n, 1))()
-    sec = (C.c_double * 4)()
-    f = getattr(lib, fn)
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_void_p] + [C.c_int32] * len(middle) + [C.c_void_p] * (len(outs) + 2)
-    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp),
-           codes.ctypes.data, offs.ctypes.data, n, C.byref(prep), *middle, *outs, sec, tails)
-    if rc < 0:
-        eng._check(rc, fn)
-    rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
-    return list(sec), rc, rec
+    return _tails_out(tails, out, offs, n) + (ms.value,)
 
 
 def map_align_prep(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, q_mns: int = 3,
                    polya_thr: int = 12):
     """spdp_map_align_s_prep: map_align with PolyA::rmpolyA in front -- what `spaln -Q7` does to queries as a FASTA file holds
     them.  Returns (genes as map_align's, seconds, return code, records as polya_scan's)."""
-    n = len(queries)
-    genes = (MapGene * max(n, 1))()
-    exons = C.POINTER(MapExon)()
-    sec, rc, rec = _prep_call(index, "spdp_map_align_s_prep", genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns, polya_thr,
-                              (), (genes, C.byref(exons)))
-    out = [None if genes[i].chr < 0 else _gene(genes[i], exons) for i in range(n)]
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(exons)
-    return out, sec, rc, rec
+    c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, _rp_s(rescore), queries)
+    prep, tails = QueryPrep(int(q_mns), int(polya_thr)), (QueryTail * max(c.n, 1))()
+    return c.best("spdp_map_align_s_prep", C.byref(prep), tails=(tails,)) + (_tail_records(tails, c.n),)
 
 
 def map_align_multi_prep(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries,
                          q_mns: int = 3, polya_thr: int = 12, all_out: bool = False):
     """spdp_map_align_s_multi_prep: map_align_multi with PolyA::rmpolyA in front.  Returns (lists as map_align_multi's, seconds,
     return code, records as polya_scan's)."""
-    n = len(queries)
-    gene_off = np.zeros(n + 1, dtype=np.int64)
-    genes = C.POINTER(MapGene)()
-    exons = C.POINTER(MapExon)()
-    sec, rc, rec = _prep_call(index, "spdp_map_align_s_multi_prep", genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries, q_mns,
-                              polya_thr, (int(bool(all_out)),), (gene_off.ctypes.data, C.byref(genes), C.byref(exons)))
-    out = [[_gene(genes[k], exons) for k in range(int(gene_off[i]), int(gene_off[i + 1]))] for i in range(n)]
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    libc.free(genes)
-    libc.free(exons)
-    return out, sec, rc, rec
+    c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, _rp_s(rescore), queries)
+    prep, tails = QueryPrep(int(q_mns), int(polya_thr)), (QueryTail * max(c.n, 1))()
+    return c.lists("spdp_map_align_s_multi_prep", C.byref(prep), int(bool(all_out)), tails=(tails,)) + (_tail_records(tails, c.n),)
 
 
 # ---- dispersed loci (include/spdp.h "dispersed loci"): what `spaln -pr` prints of a query whose parts lie in different places
-def _dispersed_out(n, gene_off, genes, exons, part, covered):
-    out = [[dict(_gene(genes[k], exons), part=int(part[k])) for k in range(int(gene_off[i]), int(gene_off[i + 1]))] for i in range(n)]
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    for p in (genes, exons, part):
-        libc.free(p)
-    return out, covered.reshape(n, 2)
+def _dispersed(c: _Call, fn: str, *middle, tails=()):
+    """a _dispersed entry: its lists with every gene's part, the covered ranges, seconds, return code"""
+    part = C.POINTER(C.c_int32)()
+    covered = np.zeros(2 * max(c.n, 1), dtype=np.int32)
+    out, sec, rc = c.lists(fn, *middle, more=(C.byref(part), covered), tails=tails)
+    for k, g in enumerate(g for lst in out for g in lst):       # (the genes lie in the lists' order)
+        g["part"] = int(part[k])
+    _free(part)
+    return out, covered[:2 * c.n].reshape(c.n, 2), sec, rc
 
 
 def map_align_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, min_seg_len: int,
@@ -655,57 +564,15 @@ def map_align_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigm
     index; prm.max_out must be 1.  prep = (q_mns, polya_thr): PolyA::rmpolyA in front, as map_align_prep (it replaces ori).
     Returns (per query a list of dicts shaped as map_align's plus part = 0 / 1 / 2: first search / left rest / right rest;
     covered: (n, 2) int32, the range every query has after its first search; seconds; return code; records as polya_scan's or None)."""
-    from . import abi
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    codes, offs = _packed(queries)
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    rp = abi.RescoreParams(*(int(x) for x in rescore))
-    qp = QueryPrep(int(prep[0]), int(prep[1])) if prep is not None else None
-    tails = (QueryTail * max(n, 1))() if prep is not None else None
-    gene_off = np.zeros(n + 1, dtype=np.int64)
-    genes, exons, part = C.POINTER(MapGene)(), C.POINTER(MapExon)(), C.POINTER(C.c_int32)()
-    covered = np.zeros(2 * max(n, 1), dtype=np.int32)
-    sec = (C.c_double * 4)()
-    f = lib.spdp_map_align_s_dispersed
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
-    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rp),
-           codes.ctypes.data, offs.ctypes.data, n, int(ori), C.byref(qp) if qp is not None else None, int(min_seg_len),
-           gene_off.ctypes.data, C.byref(genes), C.byref(exons), C.byref(part), covered.ctypes.data, sec, tails)
-    if rc < 0:
-        eng._check(rc, "spdp_map_align_s_dispersed")
-    rec = None
-    if prep is not None:
-        rec = np.array([[getattr(tails[i], k) for k in TAIL_FIELDS] for i in range(n)], dtype=np.int32).reshape(n, len(TAIL_FIELDS))
-    out, cov = _dispersed_out(n, gene_off, genes, exons, part, covered[:2 * n])
-    return out, cov, list(sec), rc, rec
+    c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, _rp_s(rescore), queries)
+    qp = C.byref(QueryPrep(int(prep[0]), int(prep[1]))) if prep is not None else None
+    tails = (QueryTail * max(c.n, 1))() if prep is not None else None
+    res = _dispersed(c, "spdp_map_align_s_dispersed", int(ori), qp, int(min_seg_len), tails=(tails,))
+    return res + (_tail_records(tails, c.n) if prep is not None else None,)
 
 
 def map_align_h_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, min_seg_len: int):
     """spdp_map_align_h_dispersed: the same for protein queries against the translated index (arguments as map_align_h's; positions
     of the query in residues).  Returns (lists, covered, seconds, return code) as map_align_dispersed."""
-    lib, eng = index.lib, index.eng
-    n = len(queries)
-    codes, offs = _packed(queries)
-    g = Genome()
-    gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
-    go = np.ascontiguousarray(chr_off, dtype=np.int64)
-    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
-    gene_off = np.zeros(n + 1, dtype=np.int64)
-    genes, exons, part = C.POINTER(MapGene)(), C.POINTER(MapExon)(), C.POINTER(C.c_int32)()
-    covered = np.zeros(2 * max(n, 1), dtype=np.int32)
-    sec = (C.c_double * 4)()
-    f = lib.spdp_map_align_h_dispersed
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 11 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6
-    rc = f(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(sp), C.addressof(sigmodel), C.byref(prm), C.byref(rescore),
-           codes.ctypes.data, offs.ctypes.data, n, int(min_seg_len), gene_off.ctypes.data, C.byref(genes), C.byref(exons), C.byref(part),
-           covered.ctypes.data, sec)
-    if rc < 0:
-        eng._check(rc, "spdp_map_align_h_dispersed")
-    out, cov = _dispersed_out(n, gene_off, genes, exons, part, covered[:2 * n])
-    return out, cov, list(sec), rc
+    c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries)
+    return _dispersed(c, "spdp_map_align_h_dispersed", int(min_seg_len))

@@ -1,12 +1,14 @@
-// spdp_map_api.cpp -- spdp_map_align_s: block search -> regions + splice signals -> seeded alignment -> rescoring -> the
-// locus that stays, for a batch of nucleotide queries in one call (include/spdp.h "map and align").  What the reference's
-// per-query driver does around alignS_ng when the genome is searched (src/spaln.cc:880-1010: blkaln / spalign2, genomicseq at
-// :913 reading the region and building its Exinon), batched: all loci of a chunk of queries share one signal launch, one
-// seeded call and one rescoring call.  Host code only; the device work is that of the entries it calls.
+// spdp_map_api.cpp -- map and align in one call (include/spdp.h "map and align"): block search -> regions + splice signals -> seeded
+// alignment -> rescoring -> the loci that stay, for a batch of cDNA queries (spdp_map_align_s*) or of protein queries against the
+// translated index (spdp_map_align_h*).  What the reference's per-query driver does around alignS_ng when the genome is searched
+// (src/spaln.cc:880-1010: blkaln / spalign2, genomicseq at :913 reading the region and building its Exinon), batched: all loci of a
+// chunk of queries share one signal launch, one seeded call and one rescoring call.  Host code only; the device work is that of the
+// entries it calls.
 //
-// One chain serves two outputs: the best locus of a query (spdp_map_align_s / _h) and the list of loci spaln -M prints
-// (spdp_map_align_s_multi / _h_multi, blkaln's selection at src/spaln.cc:913-976).  The chain hands every candidate locus,
-// aligned and rescored, to a sink in the block search's order; the two selections are sinks.
+// One chain, written once for both kinds of query, serves three outputs: the best locus of a query (spdp_map_align_s / _h), the
+// list of loci spaln -M prints (_multi, blkaln's selection at src/spaln.cc:913-976) and the dispersed loci of spaln -pr
+// (_dispersed).  The chain hands every candidate locus, aligned and rescored, to a sink in the block search's order; the
+// selections are sinks.
 #include "spdp_internal.h"
 #include "spdp_h_internal.h"
 #include "spdp_region.h"
@@ -17,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <new>
 #include <numeric>
 #include <vector>
@@ -71,10 +74,7 @@ int hand_out(SpdpContext* ctx, const char* who, const Reported& r, int n, int64_
     for (int i = 0; i < n; ++i) { ng += r.genes[i].size(); for (const auto& e : r.ex[i]) ne += e.size(); }
     *exons = (SpdpMapExon*) malloc(sizeof(SpdpMapExon) * std::max<size_t>(ne, 1));
     *genes = (SpdpMapGene*) malloc(sizeof(SpdpMapGene) * std::max<size_t>(ng, 1));
-    if (!*exons || !*genes) {
-        free(*exons); *exons = nullptr; free(*genes); *genes = nullptr;
-        ctx->err = std::string(who) + ": out of memory"; return -1;
-    }
+    if (!*exons || !*genes) { ctx->err = std::string(who) + ": out of memory"; return -1; }      // (the entry's frame frees what there is)
     size_t o = 0, k = 0;
     gene_off[0] = 0;
     for (int i = 0; i < n; ++i) {
@@ -184,611 +184,449 @@ int check_multi(SpdpContext* ctx, const char* who, const SpdpBlkIndexDesc* hix, 
     return 0;
 }
 
-}  // namespace
+// ---- the chain: block search -> regions + signals -> seeded walks -> rescoring -> sink -------------------------------------------
+// Written once for both kinds of query.  A kind (KindS: cDNA, KindH: protein against the translated index, `spaln -W -KP`) holds what
+// differs: the types, the layout of a chunk's staging block, and one function per step of a chunk.  What blkaln / genomicseq /
+// spalign2 do per query (src/spaln.cc:846-1010, 1137-1152), for a batch: all loci of a chunk share one signal launch, one seeded
+// call and one rescoring call.
 
-namespace {
-
-// The cDNA chain in its steps, and what one call holds between them: setup() checks the arguments and prepares the queries,
-// find() is the block search on one range per query, align() takes loci through regions + signals, the seeded walks and the
-// rescoring and hands each to the sink.  spdp_map_align_s and its siblings run the steps once; the dispersed entries run find()
-// per pass and align() per round.
-struct ChainS {
-    SpdpContext* ctx; const SpdpBlkIndex* ix; const SpdpBlkIndexDesc* hix; const SpdpGenome* genome; const SpdpScoring* sc;
-    const SpdpSeedParams* sp; const SpdpSignalModel* sigmodel; const SpdpBlkFindParams* fprm; const SpdpRescoreParams* rp;
-    const uint8_t* codes; const int64_t* offs; int32_t n; int32_t ori;     // (codes: the normalised queries once setup() has prepared them)
-    double sec[4] = {0, 0, 0, 0};
+// what a call holds whatever its queries are
+struct ChainBase {
+    const char* who;                                    // the entry that was called: its name stands in front of every message
+    SpdpContext* ctx; const SpdpBlkIndex* ix; const SpdpBlkIndexDesc* hix; const SpdpGenome* genome;
+    const SpdpSeedParams* sp; const SpdpBlkFindParams* fprm;
+    const uint8_t* codes; const int64_t* offs; int32_t n;      // (codes: the normalised queries once a preparation has run)
+    double sec[4] = {0, 0, 0, 0};                       // find, regions + signals, align, rescore
     int partial = 0;
     std::vector<int32_t> ql, qr;                        // every query's range
+    int refuse(const std::string& why) { ctx->err = std::string(who) + ": " + why; return -1; }
+};
+
+// One chunk of loci between the steps.  Its arrays lie in one pinned block H of the context (it stays for the next call) and one
+// device block of the same layout, T positions per array; slot j < m is locus j as the block search gave it, slot m + k (cDNA,
+// ori = 3) locus k's other strand, right behind it in the arrays.  It owns the alignments and the rescored exons.
+template <class Problem>
+struct Chunk {
+    const SpdpLocus* loci; int m, ns;
+    const int32_t* rng;                                 // (may be null) the query range of locus k: rng[2 k] .. rng[2 k + 1]
+    std::vector<int64_t> at;                            // first position of slot j
+    int64_t tot = 0, T = 0;
+    uint8_t* H = nullptr;
+    std::vector<Problem> probs;
+    std::vector<const SpdpJuxt*> hl;
+    std::vector<int32_t> hn, low, orient;               // orient[k]: the walk took locus k's other-strand slot
+    std::vector<SpdpAlignment> aln;
+    std::vector<SpdpRescored> res;
+    Chunk(const SpdpLocus* l, int m_, int slots, const int32_t* r)
+        : loci(l), m(m_), ns(slots * m_), rng(r), at(ns), probs(ns), hl(m), hn(m), low(m, 0), orient(m, 0), aln(m), res(m)
+    {}                                                  // (the vectors' records are zeroed)
+    ~Chunk() { spdp_free_rescored(res.data(), m); spdp_free_alignments(aln.data(), m); }
+    Chunk(const Chunk&) = delete;
+    bool other(int j) const { return j >= m; }
+    const SpdpLocus& locus(int j) const { return loci[j < m ? j : j - m]; }
+    int32_t left(int j) const { const SpdpLocus& L = locus(j); return j < m ? L.left : L.len - L.right; }
+    int32_t right(int j) const { const SpdpLocus& L = locus(j); return j < m ? L.right : L.len - L.left; }
+};
+
+// chunks of loci, chunk i = [b[i], b[i + 1]): as few as `limit` positions each allow, of equal size (a call's time is a chain of
+// request latencies, not device work: DESIGN.md 6g -- so the larger a chunk the better, and a short last chunk costs as much as a
+// full one); a locus larger than that is a chunk of its own
+std::vector<int> cut_chunks(const std::vector<int64_t>& positions, int64_t limit)
+{
+    const int n = (int) positions.size();
+    const int64_t all = std::accumulate(positions.begin(), positions.end(), (int64_t) 0);
+    const int64_t n_chunks = std::max<int64_t>(1, (all + limit - 1) / limit);
+    const int64_t per_chunk = (all + n_chunks - 1) / n_chunks;
+    std::vector<int> b(1, 0);
+    int64_t tot = 0;
+    for (int k = 0; k < n; ++k) {
+        if (k > b.back() && tot + positions[k] > per_chunk + (1 << 17)) { b.push_back(k); tot = 0; }
+        tot += positions[k];
+    }
+    if (n) b.push_back(n);
+    return b;
+}
+
+// ---- cDNA queries: spdp_signals, spdp_align_s_seeded (_ori3 with both orientations), spdp_skl_rng_s
+struct KindS : ChainBase {
+    using Problem = SpdpProblem;
+    using Job = SigJob;
+    // staging block: codes | sig5 | sig3 (int16) | cano5 | cano3 | dinc; len + 1 positions per slot.  The default limit is 16 GiB of
+    // pinned host memory and as much on the device (a C4-sized batch of 125 000 ESTs x 2 strands x ~50 kb of loci is what reaches it)
+    static constexpr int host_bytes = 8, dev_bytes = 8, pad = 1;
+    static constexpr size_t default_mpos = 2048;
+    const SpdpScoring* sc; const SpdpSignalModel* sigmodel; const SpdpRescoreParams* rp; int32_t ori;
+    const SpdpQueryPrep* prep; bool prepares; SpdpQueryTail* tails_out;      // the _prep entries (include/spdp.h "query preparation")
     std::vector<SpdpQueryTail> tail;                    // empty: no preparation, or none that scans (polya_thr <= 0)
     std::vector<uint8_t> normal;
     std::vector<int32_t> qt;                            // Seq::tlen per query
     bool tailed = false;
-    std::vector<uint8_t> codes_rc;                      // comrev() of every query (ori = 3), made by the first align()
+    std::vector<uint8_t> codes_rc;                      // comrev() of every normalised query (ori = 3)
+    SpdpSignalModel sigm; SpdpSeedParams spx;           // the caller's with both_ori set: Exinon(seq, pwd, ori == 3), src/spaln.cc:1143, 1150
+    KindS(const ChainBase& b, const SpdpScoring* sc_, const SpdpSignalModel* sm, const SpdpRescoreParams* rp_, int32_t ori_,
+          const SpdpQueryPrep* prep_ = nullptr, bool prepares_ = false, SpdpQueryTail* tails = nullptr)
+        : ChainBase(b), sc(sc_), sigmodel(sm), rp(rp_), ori(ori_), prep(prep_), prepares(prepares_), tails_out(tails) {}
     const int32_t* tlen() const { return tailed ? qt.data() : nullptr; }
     bool prep_turned(int q) const { return tailed && tail[q].pol == 2; }   // the preparation reverse-complemented query q
+    int slots() const { return ori == 3 ? 2 : 1; }
+    const SpdpScoring* chain_costs() { return sc; }
 
-    int setup(const SpdpQueryPrep* prep, bool prepares, SpdpQueryTail* tails_out);
-    int find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
-             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps);
-    int align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink);
-    int finish(double* seconds);
-};
+    int refused()
+    {
+        // the _prep entries: the orientation is the preparation's (rmpolyA returns q_mns for every query: 3 whatever it finds, 1 under
+        // -S1 where no T head is looked for -- so a batch never mixes orientations)
+        if (prepares) {
+            if (const char* why = spdp_prep_refused(prep)) return refuse(why);
+            ori = prep->q_mns;
+        }
+        if (ori != 1 && ori != 3) return refuse("ori must be 1 (the query as given) or 3 (both orientations)");
+        if (!sp->wilip) return refuse("SpdpSeedParams.wilip missing (the HSP searches of this call are the library's own)");
+        sigm = *sigmodel; spx = *sp;
+        if (ori == 3) sigm.both_ori = spx.both_ori = 1;
+        return 0;
+    }
+    // the preparation (PolyA::rmpolyA, spdp_polya.hip): tails found, antisense queries turned; from here on `codes` are the
+    // normalised queries and every reader of a query's range or length takes them from its record.  Then their other strand
+    int prepare()
+    {
+        if (prepares && prep->polya_thr > 0) {
+            tail.resize(n); normal.resize((size_t) offs[n]);
+            if (spdp_polya_scan(ctx, codes, offs, n, prep, tail.data(), normal.data(), nullptr)) return -1;
+            codes = normal.data();
+            qt.resize(n);
+            for (int i = 0; i < n; ++i) { ql[i] = tail[i].left; qr[i] = tail[i].right; qt[i] = tail[i].tlen; }
+            if (tails_out) memcpy(tails_out, tail.data(), sizeof(SpdpQueryTail) * (size_t) n);
+        } else if (prepares && tails_out && spdp_polya_scan_host(codes, offs, n, prep, tails_out, nullptr)) return refuse("bad query offsets");
+        tailed = !tail.empty();
+        if (ori == 3) {
+            codes_rc.resize((size_t) offs[n]);
+            on_host_threads(n, [&](int q) {
+                const int64_t a0 = offs[q], len = offs[q + 1] - offs[q];
+                for (int64_t i = 0; i < len; ++i) codes_rc[a0 + i] = spdp_region::other_strand(codes[a0 + len - 1 - i]);
+            });
+        }
+        return 0;
+    }
 
-// -1: refused (ctx->err says why); 0: go on (n <= 0: there is nothing to do)
-int ChainS::setup(const SpdpQueryPrep* prep, bool prepares, SpdpQueryTail* tails_out)
-{
-    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
-        ctx->err = "spdp_map_align_s: null argument"; return -1;
+    // x.sig5 .. x.dinc of a SignalArgs or a problem: the arrays of block B, from position `at` on
+    template <class X> static void lay(X& x, uint8_t* B, int64_t T, int64_t at)
+    {
+        x.sig5 = (int16_t*) (B + T) + at; x.sig3 = (int16_t*) (B + 3 * T) + at;
+        x.cano5 = B + 5 * T + at; x.cano3 = B + 6 * T + at; x.dinc = B + 7 * T + at;
     }
-    // the _prep entries: the orientation is the preparation's (rmpolyA returns q_mns for every query: 3 whatever it finds, 1 under
-    // -S1 where no T head is looked for -- so a batch never mixes orientations)
-    if (prepares) {
-        if (const char* why = spdp_prep_refused(prep)) { ctx->err = std::string("spdp_map_align_s_prep: ") + why; return -1; }
-        ori = prep->q_mns;
+    void cut(Chunk<Problem>& c, int j)
+    {
+        const SpdpLocus& L = c.locus(j);
+        spdp_region::materialize_into(genome->codes, genome->chr_off, L.chr, L.base, L.len, (L.rvs != 0) != c.other(j), false, c.H + c.at[j]);
     }
-    if (ori != 1 && ori != 3) { ctx->err = "spdp_map_align_s: ori must be 1 (the query as given) or 3 (both orientations)"; return -1; }
-    if (!sp->wilip) { ctx->err = "spdp_map_align_s: SpdpSeedParams.wilip missing (the HSP searches of this call are the library's own)"; return -1; }
-    if (n <= 0) return 0;
-    auto t0 = std::chrono::steady_clock::now();
-    ql.assign(n, 0); qr.resize(n);
-    for (int i = 0; i < n; ++i) qr[i] = (int32_t) (offs[i + 1] - offs[i]);
-    // ---- the preparation (PolyA::rmpolyA, spdp_polya.hip): tails found, antisense queries turned; from here on `codes` are the
-    // normalised queries and every reader of a query's range or length takes them from its record
-    if (prepares && prep->polya_thr > 0) {
-        tail.resize(n); normal.resize((size_t) offs[n]);
-        if (spdp_polya_scan(ctx, codes, offs, n, prep, tail.data(), normal.data(), nullptr)) return -1;
-        codes = normal.data();
-        qt.resize(n);
-        for (int i = 0; i < n; ++i) { ql[i] = tail[i].left; qr[i] = tail[i].right; qt[i] = tail[i].tlen; }
-        if (tails_out) memcpy(tails_out, tail.data(), sizeof(SpdpQueryTail) * (size_t) n);
-    } else if (prepares && tails_out && spdp_polya_scan_host(codes, offs, n, prep, tails_out, nullptr)) {
-        ctx->err = "spdp_map_align_s_prep: bad query offsets"; return -1;
+    int signals(Chunk<Problem>& c, const std::vector<Job>& jobs, uint8_t* D)
+    {
+        SignalArgs A;
+        memset(&A, 0, sizeof A);
+        A.codes = D;
+        lay(A, D, c.T, 0);
+        return spdp_signals_run(ctx, &sigm, jobs, A, nullptr, nullptr);
     }
-    tailed = !tail.empty();
-    sec[0] += since(t0);
-    return 0;
-}
-
-// the block search for m queries laid out by cd / of (the call's own, or a pass's selection of them), each on its range
-int ChainS::find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
-                 SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps)
-{
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = spdp_blk_find_tlen(ctx, ix, hix, genome, sp->wilip, sc, fprm, cd, of, left, right, tl, m, loci, n_loci, hsps, nullptr);
-    sec[0] += since(t0);
-    return rc;
-}
-
-// loci[k].query: a query of the call; rng (may be null): the query range locus k is aligned on, rng[2 k] .. rng[2 k + 1] of the
-// normalised query -- without it the query's own range.  The sink gets every locus, in the order given.
-int ChainS::align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink)
-{
-    auto t0 = std::chrono::steady_clock::now();
-    const bool both = ori == 3;
-    if (both && codes_rc.empty()) {
-        codes_rc.resize((size_t) offs[n]);
-        on_host_threads(n, [&](int q) {
-            const int64_t a0 = offs[q], len = offs[q + 1] - offs[q];
-            for (int64_t i = 0; i < len; ++i) codes_rc[a0 + i] = spdp_region::other_strand(codes[a0 + len - 1 - i]);
-        });
+    void point(Chunk<Problem>& c, int j, Problem& P)
+    {
+        if (c.other(j)) P.a = codes_rc.data() + offs[c.locus(j).query];
+        lay(P, c.H, c.T, c.at[j]);
     }
-    SpdpSignalModel sigm = *sigmodel;
-    SpdpSeedParams spx = *sp;
-    if (both) sigm.both_ori = spx.both_ori = 1;         // Exinon(seq, pwd, ori == 3), src/spaln.cc:1143, 1150
-    // positions (NOT bytes) of the loci one chunk may hold; the signal arrays of a chunk take 8 B per position of pinned host memory
-    // and as much on the device, allocated as the chunk needs them (the default bound is 16 GiB each; a C4-sized batch of 125 000
-    // ESTs x 2 strands x ~50 kb of loci is what reaches it).  SPDP_MAP_CHUNK_MPOS = n: n x 2^20 positions (SPDP_MAP_CHUNK_MB: its old name)
-    size_t chunk_positions = (size_t) 2048 << 20;
-    for (const char* v : {"SPDP_MAP_CHUNK_MB", "SPDP_MAP_CHUNK_MPOS"})
-        if (const char* e = getenv(v)) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    (void) hipSetDevice(ctx->device);
-    // chunks of loci: as few as the position limit allows, of equal size (a call's time is a chain of request latencies, not
-    // device work: DESIGN.md 6g -- so the larger a chunk the better, and a short last chunk costs as much as a full one)
-    int64_t all_positions = 0;
-    for (int k = 0; k < n_loci; ++k) all_positions += (both ? 2 : 1) * (int64_t) (loci[k].len + 1);
-    const int64_t n_chunks = std::max<int64_t>(1, (all_positions + (int64_t) chunk_positions - 1) / (int64_t) chunk_positions);
-    const int64_t per_chunk = (all_positions + n_chunks - 1) / n_chunks;
-    for (int c0 = 0; c0 < n_loci; ) {
-        t0 = std::chrono::steady_clock::now();
-        std::vector<int64_t> at;                        // first position of locus c0 + k in the chunk's arrays (len + 1 positions each)
-        int64_t tot = 0;
-        int c1 = c0;
-        while (c1 < n_loci && (c1 == c0 || tot + (both ? 2 : 1) * (int64_t) (loci[c1].len + 1) <= per_chunk + (1 << 17))) {
-            at.push_back(tot); tot += (both ? 2 : 1) * (int64_t) (loci[c1].len + 1); ++c1;
-        }
-        const int m = c1 - c0;
-        const int ns = both ? 2 * m : m;                // slots of the chunk's arrays: locus k as the block search gave it, then (ori = 3)
-        if (both) { at.resize(ns); for (int k = 0; k < m; ++k) at[m + k] = at[k] + loci[c0 + k].len + 1; }      // its other strand right behind it
-        auto slot_left = [&](int j) { const SpdpLocus& L = loci[c0 + (j < m ? j : j - m)]; return j < m ? L.left : L.len - L.right; };
-        auto slot_right = [&](int j) { const SpdpLocus& L = loci[c0 + (j < m ? j : j - m)]; return j < m ? L.right : L.len - L.left; };
-        for (int k = 0; k < m; ++k) {
-            const SpdpLocus& L = loci[c0 + k];
-            if (L.chr < 0 || L.chr >= genome->n_chr || L.base < 0 || L.len < 0 || L.left < 0 || L.right > L.len || L.right < L.left ||
-                genome->chr_off[L.chr] + L.base + L.len > genome->chr_off[L.chr + 1]) { ctx->err = "spdp_map_align_s: a locus outside its chromosome"; return -1; }
-        }
-        // ---- the regions as the aligner reads them, then their signals in one launch.  One pinned block of the context (it
-        // stays for the next call) and one device block of the same layout: codes | sig5 | sig3 | cano5 | cano3 | dinc
-        const int64_t T = (tot + 255) / 256 * 256;
-        uint8_t* H = (uint8_t*) ctx->staging(2, (size_t) T * 8);
-        if (!H) { ctx->err = "spdp_map_align_s: no pinned host memory for a chunk's regions and signals (SPDP_MAP_CHUNK_MB sets the chunk size)"; return -1; }
-        uint8_t* reg = H; int16_t* sig5 = (int16_t*) (H + T); int16_t* sig3 = (int16_t*) (H + 3 * T);
-        uint8_t* cano5 = H + 5 * T; uint8_t* cano3 = H + 6 * T; uint8_t* dinc = H + 7 * T;
-        on_host_threads(ns, [&](int j) {
-            const SpdpLocus& L = loci[c0 + (j < m ? j : j - m)];
-            const uint8_t* src = genome->codes + genome->chr_off[L.chr] + L.base;
-            uint8_t* dst = reg + at[j];
-            if ((L.rvs != 0) == (j < m)) for (int i = 0; i < L.len; ++i) dst[i] = spdp_region::other_strand(src[L.len - 1 - i]);
-            else memcpy(dst, src, (size_t) L.len);
-            dst[L.len] = 0;
-        });
-        const double t_regions = since(t0);
-        {
-            DevMem d;
-            HIPCHK(d.get((size_t) T * 8));
-            uint8_t* D = d.as<uint8_t>();
-            HIPCHK(hipMemcpyAsync(D, reg, tot, hipMemcpyHostToDevice, ctx->stream));
-            std::vector<SigJob> jobs(ns);
-            for (int j = 0; j < ns; ++j) {
-                SigJob& J = jobs[j];
-                memset(&J, 0, sizeof J);
-                J.b_off = at[j]; J.out_off = at[j]; J.b_len = loci[c0 + (j < m ? j : j - m)].len; J.left = slot_left(j); J.right = slot_right(j);
-            }
-            SignalArgs A;
-            memset(&A, 0, sizeof A);
-            A.codes = D;
-            A.sig5 = (int16_t*) (D + T); A.sig3 = (int16_t*) (D + 3 * T);
-            A.cano5 = D + 5 * T; A.cano3 = D + 6 * T; A.dinc = D + 7 * T;
-            if (spdp_signals_run(ctx, &sigm, jobs, A, nullptr, nullptr)) return -1;
-            HIPCHK(hipMemcpy(H + T, D + T, (size_t) T * 7, hipMemcpyDeviceToHost));
-        }
-        if (getenv("SPDP_MAP_VERBOSE")) fprintf(stderr, "[map] regions cut %.3f s, signals made and brought back %.3f s\n", t_regions, since(t0) - t_regions);
-        std::vector<SpdpProblem> probs(ns);
-        std::vector<const SpdpJuxt*> hl(m);
-        std::vector<int32_t> hn(m), low(m, 0);
-        for (int j = 0; j < ns; ++j) {
-            const int k = j < m ? j : j - m;
-            const SpdpLocus& L = loci[c0 + k];
-            SpdpProblem& P = probs[j];
-            memset(&P, 0, sizeof P);
-            P.a = (j < m ? codes : codes_rc.data()) + offs[L.query]; P.a_len = (int32_t) (offs[L.query + 1] - offs[L.query]);
-            P.b = reg + at[j]; P.b_len = L.len;
-            P.sig5 = sig5 + at[j]; P.sig3 = sig3 + at[j];
-            P.cano5 = cano5 + at[j]; P.cano3 = cano3 + at[j]; P.dinc = dinc + at[j];
-            P.b_left = slot_left(j); P.b_right = slot_right(j);
-            // the query's range: the one given for this locus, else its own (the reverse leg: Seq::comrev mirrors it, Seq::rev_attr)
-            const int32_t al = rng ? rng[2 * (c0 + k)] : ql[L.query], ar = rng ? rng[2 * (c0 + k) + 1] : qr[L.query];
-            P.a_left = j < m ? al : P.a_len - ar; P.a_right = j < m ? ar : P.a_len - al;
-            P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
-            if (j < m) { hl[k] = hsps + L.hsp_off; hn[k] = L.n_hsp; }
-        }
-        sec[1] += since(t0);
-        // ---- the aligner on every locus, then the printer's scores
-        t0 = std::chrono::steady_clock::now();
-        std::vector<SpdpAlignment> aln(m);
-        std::vector<int32_t> orient(m, 0);
+    int walk(Chunk<Problem>& c)
+    {
+        const int m = c.m;
         // Seq::tlen of every problem for the walks' own HSP searches; the reverse leg keeps the forward one's (alignS_ng turns the
         // query in place, which leaves tlen alone: there the bound cuts the transcript's end, the tail sits at the front)
         std::vector<int32_t> ptl;
-        if (tailed) { ptl.resize(ns); for (int j = 0; j < ns; ++j) ptl[j] = tail[loci[c0 + (j < m ? j : j - m)].query].tlen; }
+        if (tailed) { ptl.resize(c.ns); for (int j = 0; j < c.ns; ++j) ptl[j] = tail[c.locus(j).query].tlen; }
         struct TlenSet { SpdpContext* c; ~TlenSet() { c->seed_a_tlen = nullptr; } } tlen_set{ctx};
         ctx->seed_a_tlen = tailed ? ptl.data() : nullptr;
-        const int rc = both ? spdp_align_s_seeded_ori3(ctx, sc, &spx, probs.data(), probs.data() + m, m, hl.data(), hn.data(), low.data(), nullptr, aln.data(), orient.data())
-                            : spdp_align_s_seeded(ctx, sc, &spx, probs.data(), m, hl.data(), hn.data(), low.data(), nullptr, aln.data());
-        ctx->seed_a_tlen = nullptr;
-        if (rc < 0) return -1;
-        if (both) for (int k = 0; k < m; ++k) if (orient[k]) probs[k] = probs[m + k];        // rescoring reads the pair that was aligned
-        if (rc > 0) ++partial;
-        sec[2] += since(t0);
-        if (getenv("SPDP_MAP_VERBOSE")) {
-            int64_t st[12] = {0};
-            spdp_seeded_stats(ctx, st, 11);
-            fprintf(stderr, "[map] chunk of %d loci, %.1f M positions: regions + signals %.3f s; seeded call %.3f s (upload %.3f, walks with the device idle %.3f, "
-                    "device batches %.3f, handing back %.3f; %lld batches, %lld + %lld DP requests, %lld HSP searches)\n", m, tot / 1e6, sec[1], since(t0),
-                    st[6] / 1e6, st[7] / 1e6, st[8] / 1e6, st[9] / 1e6, (long long) st[0], (long long) st[1], (long long) st[2], (long long) st[4]);
+        const int rc = ori == 3 ? spdp_align_s_seeded_ori3(ctx, sc, &spx, c.probs.data(), c.probs.data() + m, m, c.hl.data(), c.hn.data(), c.low.data(),
+                                                           nullptr, c.aln.data(), c.orient.data())
+                                : spdp_align_s_seeded(ctx, sc, &spx, c.probs.data(), m, c.hl.data(), c.hn.data(), c.low.data(), nullptr, c.aln.data());
+        if (rc >= 0 && ori == 3) for (int k = 0; k < m; ++k) if (c.orient[k]) c.probs[k] = c.probs[m + k];     // rescoring reads the pair that was aligned
+        return rc;
+    }
+    int rescore(Chunk<Problem>& c) { return spdp_skl_rng_s(ctx, sc, rp, c.probs.data(), c.m, c.aln.data(), c.res.data()); }
+    void rows(const Chunk<Problem>& c, int k, LocusOut& o)
+    {
+        const SpdpLocus& L = c.loci[k];
+        const SpdpRescored& R = c.res[k];
+        const int q_rev = c.orient[k];
+        const int rvs = q_rev ? !L.rvs : (L.rvs != 0);                                            // the strand the aligned region lies on
+        const int a_len = c.probs[k].a_len;
+        o.g.chr = L.chr; o.g.rvs = rvs; o.g.q_rev = q_rev; o.g.score = R.score; o.g.val = R.val;
+        std::vector<SpdpMapExon>& ex = o.ex;
+        auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
+        // positions of the query as given (Seq::SiteNo with inex.sens reversed): the reverse leg turned it, and so did the
+        // preparation of a query with a T head -- both: as given again
+        const bool turned = (q_rev != 0) != prep_turned(L.query);
+        for (int e = 0; e < R.n_exons; ++e) {
+            const SpdpExon& x = R.exons[e];
+            if (x.left > (1 << 30)) continue;                                                     // (the closing record of the list)
+            // the query range covered, from the first exon's rleft to the last one's rright; the reverse leg's turned back
+            const int32_t xl = q_rev ? a_len - x.rright : x.rleft, xr = q_rev ? a_len - x.rleft : x.rright;
+            o.rleft = ex.empty() ? xl : std::min(o.rleft, xl); o.rright = ex.empty() ? xr : std::max(o.rright, xr);
+            if (turned) ex.push_back({a_len - x.rleft, a_len - x.rright + 1, site(x.left), site(x.right - 1)});
+            else ex.push_back({x.rleft + 1, x.rright, site(x.left), site(x.right - 1)});
         }
-        t0 = std::chrono::steady_clock::now();
-        std::vector<SpdpRescored> res(m);
-        memset(res.data(), 0, sizeof(SpdpRescored) * m);
-        if (spdp_skl_rng_s(ctx, sc, rp, probs.data(), m, aln.data(), res.data())) { spdp_free_alignments(aln.data(), m); return -1; }
-        for (int k = 0; k < m; ++k) {
-            const SpdpLocus& L = loci[c0 + k];
-            LocusOut o;
-            o.aligned = aln[k].n_skl >= 1;
-            o.g = no_gene();
-            if (!o.aligned) { sink(L, std::move(o)); continue; }
-            const int rvs = orient[k] ? !L.rvs : (L.rvs != 0);                                    // the strand the aligned region lies on
-            const int a_len = probs[k].a_len;
-            o.g.chr = L.chr; o.g.rvs = rvs; o.g.q_rev = orient[k]; o.g.score = res[k].score; o.g.val = res[k].val;
-            std::vector<SpdpMapExon>& ex = o.ex;
-            auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
-            for (int e = 0; e < res[k].n_exons; ++e) {
-                const SpdpExon& x = res[k].exons[e];
-                if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
-                // the query range covered, from the first exon's rleft to the last one's rright; the reverse leg's turned back
-                const int32_t xl = orient[k] ? a_len - x.rright : x.rleft, xr = orient[k] ? a_len - x.rleft : x.rright;
-                o.rleft = ex.empty() ? xl : std::min(o.rleft, xl); o.rright = ex.empty() ? xr : std::max(o.rright, xr);
-                // positions of the query as given (Seq::SiteNo with inex.sens reversed): the reverse leg turned it, and so did the
-                // preparation of a query with a T head -- both: as given again
-                const bool turned = (orient[k] != 0) != (tailed && tail[L.query].pol == 2);
-                if (turned) ex.push_back({a_len - x.rleft, a_len - x.rright + 1, site(x.left), site(x.right - 1)});
-                else ex.push_back({x.rleft + 1, x.rright, site(x.left), site(x.right - 1)});
-            }
-            sink(L, std::move(o));
-        }
-        spdp_free_rescored(res.data(), m);
-        spdp_free_alignments(aln.data(), m);
-        sec[3] += since(t0);
-        c0 = c1;
     }
-    return 0;
-}
-
-int ChainS::finish(double* seconds)
-{
-    if (seconds) memcpy(seconds, sec, sizeof sec);
-    if (partial) { ctx->err = "spdp_map_align_s: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
-    return 0;
-}
-
-}  // namespace
-
-static int map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                                const LocusSink& sink, double* seconds,
-                                const SpdpQueryPrep* prep = nullptr, bool prepares = false, SpdpQueryTail* tails_out = nullptr)
-{
-    if (!ctx) return -1;
-    ChainS R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori};
-    if (R.setup(prep, prepares, tails_out)) return -1;
-    if (n <= 0) return 0;
-    SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
-    if (R.find(R.codes, offs, R.ql.data(), R.qr.data(), R.tlen(), n, &loci, &n_loci, &hsps)) return -1;
-    struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
-    if (R.align(loci, n_loci, hsps, nullptr, sink)) return -1;
-    return R.finish(seconds);
-}
-
-extern "C" int spdp_map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori,
-                                SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
-{
-    if (!ctx) return -1;
-    if (!genes || !exons) { ctx->err = "spdp_map_align_s: null argument"; return -1; }
-    *exons = nullptr;
-    try {
-        BestSink best(std::max(n, 0));
-        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
-        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori, std::ref(best), seconds);
-        if (rc < 0 || n <= 0) return rc;
-        return best.finish(ctx, "spdp_map_align_s", n, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {                     // (nothing of C++ crosses the C boundary)
-        ctx->err = "spdp_map_align_s: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        if (*exons) { free(*exons); *exons = nullptr; }
-        return -1;
-    }
-}
-
-extern "C" int spdp_map_align_s_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                      const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                      const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                      const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, int32_t all_out,
-                                      int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
-{
-    if (!ctx) return -1;
-    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_s_multi: null argument"; return -1; }
-    *genes = nullptr; *exons = nullptr;
-    if (check_multi(ctx, "spdp_map_align_s_multi", hix, fprm)) return -1;
-    try {
-        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
-        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, ori, std::ref(multi), seconds);
-        if (rc < 0) return rc;
-        return multi.finish(ctx, "spdp_map_align_s_multi", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = "spdp_map_align_s_multi: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
-        return -1;
-    }
-}
-
-
-// ---- protein queries: spdp_map_align_h ---------------------------------------------------------------------------------------------
-// The same chain for amino-acid queries against the translated index (`spaln -W -KP`): spdp_blk_find (the vote on the amino-acid
-// words, the HSP search on regions read as tron codes) -> per locus the region as the aligner reads it (other strand, Seq::nuc2tron) and
-// its SGPT6 signals, all loci of a chunk in one launch of spdp_signals_h -> spdp_align_h_seeded with the library's own HSP searches ->
-// the junction phases the walks chose written back (skl_rngH_ng reads them: spdp_seeded_phase_marks) -> spdp_skl_rng_h -> every locus
-// to the sink (the best one, or the list spaln -M prints).  What blkaln / genomicseq / spalign2 do per query (src/spaln.cc:846-1010, 1137-1152), for a batch.
-namespace {
-
-// the protein chain in the same steps (ChainS): no orientation, no preparation
-struct ChainH {
-    SpdpContext* ctx; const SpdpBlkIndex* ix; const SpdpBlkIndexDesc* hix; const SpdpGenome* genome; const SpdpScoringH* sc;
-    const SpdpSeedParams* sp; const SpdpSignalModelH* sigmodel; const SpdpBlkFindParams* fprm; const SpdpRescoreParamsH* rp;
-    const uint8_t* codes; const int64_t* offs; int32_t n;
-    double sec[4] = {0, 0, 0, 0};
-    int partial = 0;
-    std::vector<int32_t> ql, qr;                        // every query's range
-    const int32_t* tlen() const { return nullptr; }
-    bool prep_turned(int) const { return false; }
-
-    int setup();
-    int find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
-             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps);
-    int align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink);
-    int finish(double* seconds);
 };
 
-int ChainH::setup()
-{
-    if (!ix || !hix || !genome || !sc || !sp || !sigmodel || !fprm || !rp || !codes || !offs) {
-        ctx->err = "spdp_map_align_h: null argument"; return -1;
+// ---- protein queries: the region as the aligner reads it (other strand, Seq::nuc2tron) and its SGPT6 signals (spdp_signals_h),
+// spdp_align_h_seeded with the library's own HSP searches, spdp_skl_rng_h.  No orientation, no preparation
+struct KindH : ChainBase {
+    using Problem = SpdpProblemH;
+    using Job = SigJobH;
+    // staging block: tron codes | sig5 sig3 sigS sigT sigE (int16) | phs5 phs3 (int8) | dinc, on the device | cano behind them;
+    // len + 3 positions per locus
+    static constexpr int host_bytes = 14, dev_bytes = 15, pad = 3;
+    static constexpr size_t default_mpos = 512;
+    const SpdpScoringH* sc; const SpdpSignalModelH* sigmodel; const SpdpRescoreParamsH* rp;
+    SpdpScoring costs;                                  // (the gap and intron prices the HSP chaining of the block search reads)
+    KindH(const ChainBase& b, const SpdpScoringH* sc_, const SpdpSignalModelH* sm, const SpdpRescoreParamsH* rp_)
+        : ChainBase(b), sc(sc_), sigmodel(sm), rp(rp_) {}
+    const int32_t* tlen() const { return nullptr; }
+    bool prep_turned(int) const { return false; }
+    int slots() const { return 1; }
+    const SpdpScoring* chain_costs()
+    {
+        memset(&costs, 0, sizeof costs);
+        costs.gop = sc->gop; costs.gep = sc->gep; costs.lgop = sc->lgop; costs.lgep = sc->lgep; costs.codonk1 = sc->codonk1;
+        costs.intpen = sc->intpen; costs.intpen_len = sc->intpen_len;
+        return &costs;
     }
-    if (!sp->wilip || sp->wilip->dvsp != 1) { ctx->err = "spdp_map_align_h: SpdpSeedParams.wilip must be the protein model (dvsp = 1)"; return -1; }
-    if (!sc->intpen || sc->intpen_len <= 0) { ctx->err = "spdp_map_align_h: SpdpScoringH.intpen missing"; return -1; }
-    if (n <= 0) return 0;
-    ql.assign(n, 0); qr.resize(n);
-    for (int i = 0; i < n; ++i) qr[i] = (int32_t) (offs[i + 1] - offs[i]);
-    return 0;
-}
-
-int ChainH::find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t*, int32_t m,
-                 SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps)
-{
-    auto t0 = std::chrono::steady_clock::now();
-    SpdpScoring chain_costs;                            // (the gap and intron prices the HSP chaining reads)
-    memset(&chain_costs, 0, sizeof chain_costs);
-    chain_costs.gop = sc->gop; chain_costs.gep = sc->gep; chain_costs.lgop = sc->lgop; chain_costs.lgep = sc->lgep; chain_costs.codonk1 = sc->codonk1;
-    chain_costs.intpen = sc->intpen; chain_costs.intpen_len = sc->intpen_len;
-    const int rc = spdp_blk_find(ctx, ix, hix, genome, sp->wilip, &chain_costs, fprm, cd, of, left, right, m, loci, n_loci, hsps, nullptr);
-    sec[0] += since(t0);
-    return rc;
-}
-
-// as ChainS::align: rng (may be null) = the range of the query, in residues, locus k is aligned on
-int ChainH::align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink)
-{
-    auto t0 = std::chrono::steady_clock::now();
-    size_t chunk_positions = (size_t) 512 << 20;        // 14 B per position on both sides of the bus
-    if (const char* e = getenv("SPDP_MAP_CHUNK_MPOS")) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
-    (void) hipSetDevice(ctx->device);
-    for (int k = 0; k < n_loci; ++k) {
-        const SpdpLocus& L = loci[k];
-        if (L.chr < 0 || L.chr >= genome->n_chr || L.base < 0 || L.len < 0 || L.left < 0 || L.right > L.len || L.right < L.left ||
-            genome->chr_off[L.chr] + L.base + L.len > genome->chr_off[L.chr + 1]) { ctx->err = "spdp_map_align_h: a locus outside its chromosome"; return -1; }
+    int refused()
+    {
+        if (!sp->wilip || sp->wilip->dvsp != 1) return refuse("SpdpSeedParams.wilip must be the protein model (dvsp = 1)");
+        if (!sc->intpen || sc->intpen_len <= 0) return refuse("SpdpScoringH.intpen missing");
+        return 0;
     }
-    for (int c0 = 0; c0 < n_loci; ) {
-        t0 = std::chrono::steady_clock::now();
-        std::vector<int64_t> at;                        // first position of locus c0 + k in the chunk's arrays (len + 3 positions each)
-        int64_t tot = 0;
-        int c1 = c0;
-        while (c1 < n_loci && (c1 == c0 || tot + loci[c1].len + 3 <= (int64_t) chunk_positions)) { at.push_back(tot); tot += loci[c1].len + 3; ++c1; }
-        const int m = c1 - c0;
-        const int64_t T = (tot + 255) / 256 * 256;
-        // one host block: tron codes | sig5 sig3 sigS sigT sigE (int16) | phs5 phs3 (int8) | dinc
-        uint8_t* Hbuf = (uint8_t*) ctx->staging(2, (size_t) T * 14);       // (pinned, kept by the context)
-        if (!Hbuf) { ctx->err = "spdp_map_align_h: no pinned host memory for a chunk's regions and signals (SPDP_MAP_CHUNK_MPOS sets the chunk size)"; return -1; }
-        uint8_t* reg = Hbuf;
-        int16_t* s16[5]; for (int i = 0; i < 5; ++i) s16[i] = (int16_t*) (Hbuf + T + 2 * T * i);
-        int8_t* phs5 = (int8_t*) (Hbuf + 11 * T); int8_t* phs3 = (int8_t*) (Hbuf + 12 * T);
-        uint8_t* dinc = Hbuf + 13 * T;
-        on_host_threads(m, [&](int j) {
-            const SpdpLocus& L = loci[c0 + j];
-            spdp_region::materialize_into(genome->codes, genome->chr_off, L.chr, L.base, L.len, L.rvs != 0, true, reg + at[j]);
-            reg[at[j] + L.len + 1] = reg[at[j] + L.len + 2] = 0;
-        });
-        {
-            DevMem d;
-            HIPCHK(d.get((size_t) T * 15));
-            uint8_t* D = d.as<uint8_t>();
-            HIPCHK(hipMemcpyAsync(D, reg, tot, hipMemcpyHostToDevice, ctx->stream));
-            std::vector<SigJobH> jobs(m);
-            for (int j = 0; j < m; ++j) {
-                SigJobH& J = jobs[j];
-                memset(&J, 0, sizeof J);
-                J.b_off = at[j]; J.out_off = at[j]; J.b_len = loci[c0 + j].len; J.left = loci[c0 + j].left; J.right = loci[c0 + j].right;
-            }
-            SignalArgsH A;
-            memset(&A, 0, sizeof A);
-            A.codes = D;
-            A.sig5 = (int16_t*) (D + T); A.sig3 = (int16_t*) (D + 3 * T); A.sigS = (int16_t*) (D + 5 * T); A.sigT = (int16_t*) (D + 7 * T);
-            A.sigE = (int16_t*) (D + 9 * T); A.phs5 = (int8_t*) (D + 11 * T); A.phs3 = (int8_t*) (D + 12 * T); A.dinc = D + 13 * T; A.cano = D + 14 * T;
-            if (spdh_signals_run(ctx, sigmodel, jobs, A, 0)) return -1;
-            HIPCHK(hipMemcpy(Hbuf + T, D + T, (size_t) T * 13, hipMemcpyDeviceToHost));
-        }
-        std::vector<SpdpProblemH> probs(m);
-        std::vector<const SpdpJuxt*> hl(m);
-        std::vector<int32_t> hn(m), low(m, 0);
-        for (int j = 0; j < m; ++j) {
-            const SpdpLocus& L = loci[c0 + j];
-            SpdpProblemH& P = probs[j];
-            memset(&P, 0, sizeof P);
-            P.a = codes + offs[L.query]; P.a_len = (int32_t) (offs[L.query + 1] - offs[L.query]);
-            P.b = reg + at[j]; P.b_len = L.len;
-            P.sig5 = s16[0] + at[j]; P.sig3 = s16[1] + at[j]; P.sigS = s16[2] + at[j]; P.sigT = s16[3] + at[j]; P.sigE = s16[4] + at[j];
-            P.phs5 = phs5 + at[j]; P.phs3 = phs3 + at[j]; P.dinc = dinc + at[j];
-            P.exin_left = L.left; P.exin_right = L.right;
-            P.a_left = rng ? rng[2 * (c0 + j)] : ql[L.query]; P.a_right = rng ? rng[2 * (c0 + j) + 1] : qr[L.query];
-            P.b_left = L.left; P.b_right = L.right;
-            P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
-            hl[j] = hsps + L.hsp_off; hn[j] = L.n_hsp;
-        }
-        sec[1] += since(t0);
-        t0 = std::chrono::steady_clock::now();
-        std::vector<SpdpAlignment> aln(m);
-        const int rc = spdp_align_h_seeded(ctx, sc, sp, probs.data(), m, hl.data(), hn.data(), low.data(), nullptr, aln.data());
-        if (rc < 0) return -1;
-        if (rc > 0) ++partial;
-        struct Alns { SpdpAlignment* a; int n; ~Alns() { spdp_free_alignments(a, n); } } alns{aln.data(), m};
-        // the phases of the junctions the walks chose themselves: where the reference's walk writes into its Exinon
-        for (int j = 0; j < m; ++j) {
+    int prepare() { return 0; }
+
+    template <class X> static void lay(X& x, uint8_t* B, int64_t T, int64_t at)
+    {
+        x.sig5 = (int16_t*) (B + T) + at; x.sig3 = (int16_t*) (B + 3 * T) + at; x.sigS = (int16_t*) (B + 5 * T) + at;
+        x.sigT = (int16_t*) (B + 7 * T) + at; x.sigE = (int16_t*) (B + 9 * T) + at;
+        x.phs5 = (int8_t*) (B + 11 * T) + at; x.phs3 = (int8_t*) (B + 12 * T) + at; x.dinc = B + 13 * T + at;
+    }
+    void cut(Chunk<Problem>& c, int j)
+    {
+        const SpdpLocus& L = c.loci[j];
+        uint8_t* dst = c.H + c.at[j];
+        spdp_region::materialize_into(genome->codes, genome->chr_off, L.chr, L.base, L.len, L.rvs != 0, true, dst);
+        dst[L.len + 1] = dst[L.len + 2] = 0;
+    }
+    int signals(Chunk<Problem>& c, const std::vector<Job>& jobs, uint8_t* D)
+    {
+        SignalArgsH A;
+        memset(&A, 0, sizeof A);
+        A.codes = D; A.cano = D + 14 * c.T;
+        lay(A, D, c.T, 0);
+        return spdh_signals_run(ctx, sigmodel, jobs, A, 0);
+    }
+    void point(Chunk<Problem>& c, int j, Problem& P)
+    {
+        lay(P, c.H, c.T, c.at[j]);
+        P.exin_left = c.loci[j].left; P.exin_right = c.loci[j].right;
+    }
+    int walk(Chunk<Problem>& c)
+    {
+        const int rc = spdp_align_h_seeded(ctx, sc, sp, c.probs.data(), c.m, c.hl.data(), c.hn.data(), c.low.data(), nullptr, c.aln.data());
+        if (rc < 0) return rc;
+        // the phases of the junctions the walks chose themselves: where the reference's walk writes into its Exinon (skl_rngH_ng
+        // reads them)
+        int8_t* phs5 = (int8_t*) (c.H + 11 * c.T); int8_t* phs3 = (int8_t*) (c.H + 12 * c.T);
+        for (int j = 0; j < c.m; ++j) {
             const SpdpPhaseMark* mk = nullptr;
             const int nm = spdp_seeded_phase_marks(ctx, j, &mk);
             for (int i = 0; i < nm; ++i) {
-                if (mk[i].n < 0 || mk[i].n > loci[c0 + j].len + 2) continue;
-                (mk[i].side == 5 ? phs5 : phs3)[at[j] + mk[i].n] = mk[i].value;
+                if (mk[i].n < 0 || mk[i].n > c.loci[j].len + 2) continue;
+                (mk[i].side == 5 ? phs5 : phs3)[c.at[j] + mk[i].n] = mk[i].value;
             }
         }
-        sec[2] += since(t0);
-        t0 = std::chrono::steady_clock::now();
-        std::vector<SpdpRescored> res(m);
-        memset(res.data(), 0, sizeof(SpdpRescored) * m);
-        if (spdp_skl_rng_h(ctx, sc, rp, probs.data(), m, aln.data(), res.data())) return -1;
-        for (int j = 0; j < m; ++j) {
-            const SpdpLocus& L = loci[c0 + j];
-            LocusOut o;
-            o.aligned = aln[j].n_skl >= 1;
-            o.g = no_gene();
-            if (!o.aligned) { sink(L, std::move(o)); continue; }
-            o.g.chr = L.chr; o.g.rvs = L.rvs != 0; o.g.q_rev = 0; o.g.score = res[j].score; o.g.val = res[j].val;
-            std::vector<SpdpMapExon>& ex = o.ex;
-            const int rvs = L.rvs != 0;
-            auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
-            // an exon closes at a record that carries an intron score; records of frame shifts inside it (iscr = NEVSEL, skl_rngH_ng:
-            // src/fwd2h1.cc:739-751, 783-797) do not: the printer reads the exon across them (src/sqpr.cc:896-952, spdp_exon_form)
-            int open = -1;
-            for (int e = 0; e < res[j].n_exons; ++e) {
-                const SpdpExon& x = res[j].exons[e];
-                if (x.left > (1 << 30)) continue;                                                 // (the closing record of the list)
-                if (open < 0) open = e;
-                if (ex.empty() && open == e) o.rleft = x.rleft;                                   // the query range covered: every record counts
-                o.rright = x.rright;
-                if (x.iscr <= SPDP_NEVSEL) continue;
-                const SpdpExon& x0 = res[j].exons[open];
-                ex.push_back({x0.rleft + 1, x.rright, site(x0.left), site(x.right - 1)});
-                open = -1;
-            }
-            sink(L, std::move(o));
-        }
-        spdp_free_rescored(res.data(), m);
-        sec[3] += since(t0);
-        c0 = c1;
+        return rc;
     }
-    return 0;
-}
+    int rescore(Chunk<Problem>& c) { return spdp_skl_rng_h(ctx, sc, rp, c.probs.data(), c.m, c.aln.data(), c.res.data()); }
+    void rows(const Chunk<Problem>& c, int k, LocusOut& o)
+    {
+        const SpdpLocus& L = c.loci[k];
+        const SpdpRescored& R = c.res[k];
+        const int rvs = L.rvs != 0;
+        o.g.chr = L.chr; o.g.rvs = rvs; o.g.q_rev = 0; o.g.score = R.score; o.g.val = R.val;
+        std::vector<SpdpMapExon>& ex = o.ex;
+        auto site = [&L, rvs](int pos) { return L.base + (rvs ? L.len - pos : pos + 1); };      // Seq::SiteNo
+        // an exon closes at a record that carries an intron score; records of frame shifts inside it (iscr = NEVSEL, skl_rngH_ng:
+        // src/fwd2h1.cc:739-751, 783-797) do not: the printer reads the exon across them (src/sqpr.cc:896-952, spdp_exon_form)
+        int open = -1;
+        for (int e = 0; e < R.n_exons; ++e) {
+            const SpdpExon& x = R.exons[e];
+            if (x.left > (1 << 30)) continue;                                                     // (the closing record of the list)
+            if (open < 0) open = e;
+            if (ex.empty() && open == e) o.rleft = x.rleft;                                       // the query range covered: every record counts
+            o.rright = x.rright;
+            if (x.iscr <= SPDP_NEVSEL) continue;
+            const SpdpExon& x0 = R.exons[open];
+            ex.push_back({x0.rleft + 1, x.rright, site(x0.left), site(x.right - 1)});
+            open = -1;
+        }
+    }
+};
 
-int ChainH::finish(double* seconds)
+// The chain in its steps: setup() checks the arguments and prepares the queries, find() is the block search on one range per
+// query, align() takes loci through regions + signals, the seeded walks and the rescoring and hands each to the sink.  The plain
+// entries run the steps once (run_once); the dispersed entries run find() per pass and align() per round.
+template <class K>
+struct Chain : K {
+    using K::K;
+    using Problem = typename K::Problem;
+
+    // -1: refused (ctx->err says why); 0: go on (n <= 0: there is nothing to do)
+    int setup()
+    {
+        K& R = *this;
+        if (!R.ix || !R.hix || !R.genome || !R.sc || !R.sp || !R.sigmodel || !R.fprm || !R.rp || !R.codes || !R.offs) return R.refuse("null argument");
+        if (R.refused()) return -1;
+        if (R.n <= 0) return 0;
+        auto t0 = std::chrono::steady_clock::now();
+        R.ql.assign(R.n, 0); R.qr.resize(R.n);
+        for (int i = 0; i < R.n; ++i) R.qr[i] = (int32_t) (R.offs[i + 1] - R.offs[i]);
+        if (R.prepare()) return -1;
+        R.sec[0] += since(t0);
+        return 0;
+    }
+
+    // the block search for m queries laid out by cd / of (the call's own, or a pass's selection of them), each on its range
+    int find(const uint8_t* cd, const int64_t* of, const int32_t* left, const int32_t* right, const int32_t* tl, int32_t m,
+             SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps)
+    {
+        K& R = *this;
+        auto t0 = std::chrono::steady_clock::now();
+        const int rc = spdp_blk_find_tlen(R.ctx, R.ix, R.hix, R.genome, R.sp->wilip, R.chain_costs(), R.fprm, cd, of, left, right, tl, m, loci, n_loci, hsps, nullptr);
+        R.sec[0] += since(t0);
+        return rc;
+    }
+
+    // loci[k].query: a query of the call; rng (may be null): the query range locus k is aligned on, rng[2 k] .. rng[2 k + 1] of the
+    // normalised query (protein: in residues) -- without it the query's own range.  The sink gets every locus, in the order given.
+    int align(const SpdpLocus* loci, int n_loci, const SpdpJuxt* hsps, const int32_t* rng, const LocusSink& sink)
+    {
+        K& R = *this;
+        SpdpContext* ctx = R.ctx;
+        const SpdpGenome* genome = R.genome;
+        const bool verbose = getenv("SPDP_MAP_VERBOSE") != nullptr;
+        const int slots = R.slots();
+        std::vector<int64_t> positions(n_loci);
+        for (int k = 0; k < n_loci; ++k) {
+            const SpdpLocus& L = loci[k];
+            if (L.chr < 0 || L.chr >= genome->n_chr || L.base < 0 || L.len < 0 || L.left < 0 || L.right > L.len || L.right < L.left ||
+                genome->chr_off[L.chr] + L.base + L.len > genome->chr_off[L.chr + 1]) return R.refuse("a locus outside its chromosome");
+            positions[k] = slots * (int64_t) (L.len + K::pad);
+        }
+        // positions (NOT bytes) of the loci one chunk may hold; the arrays of a chunk take host_bytes per position of pinned host
+        // memory and dev_bytes on the device, allocated as the chunk needs them.  SPDP_MAP_CHUNK_MPOS = n: n x 2^20 positions
+        // (SPDP_MAP_CHUNK_MB: its old name)
+        size_t chunk_positions = K::default_mpos << 20;
+        for (const char* v : {"SPDP_MAP_CHUNK_MB", "SPDP_MAP_CHUNK_MPOS"})
+            if (const char* e = getenv(v)) chunk_positions = (size_t) std::max(1, atoi(e)) << 20;
+        (void) hipSetDevice(ctx->device);
+        const std::vector<int> bounds = cut_chunks(positions, (int64_t) chunk_positions);
+        for (size_t ci = 0; ci + 1 < bounds.size(); ++ci) {
+            auto t0 = std::chrono::steady_clock::now();
+            const int c0 = bounds[ci], m = bounds[ci + 1] - c0;
+            Chunk<Problem> c(loci + c0, m, slots, rng ? rng + 2 * c0 : nullptr);
+            for (int k = 0; k < m; ++k) {
+                c.at[k] = c.tot; c.tot += positions[c0 + k];
+                if (slots == 2) c.at[m + k] = c.at[k] + loci[c0 + k].len + K::pad;
+            }
+            // ---- the regions as the aligner reads them, then their signals in one launch
+            c.T = (c.tot + 255) / 256 * 256;
+            c.H = (uint8_t*) ctx->staging(2, (size_t) c.T * K::host_bytes);
+            if (!c.H) return R.refuse("no pinned host memory for a chunk's regions and signals (SPDP_MAP_CHUNK_MPOS sets the chunk size)");
+            on_host_threads(c.ns, [&](int j) { R.cut(c, j); });
+            const double t_regions = since(t0);
+            {
+                DevMem d;
+                HIPCHK(d.get((size_t) c.T * K::dev_bytes));
+                uint8_t* D = d.as<uint8_t>();
+                HIPCHK(hipMemcpyAsync(D, c.H, c.tot, hipMemcpyHostToDevice, ctx->stream));
+                std::vector<typename K::Job> jobs(c.ns);
+                for (int j = 0; j < c.ns; ++j) {
+                    typename K::Job& J = jobs[j];
+                    memset(&J, 0, sizeof J);
+                    J.b_off = c.at[j]; J.out_off = c.at[j]; J.b_len = c.locus(j).len; J.left = c.left(j); J.right = c.right(j);
+                }
+                if (R.signals(c, jobs, D)) return -1;
+                HIPCHK(hipMemcpy(c.H + c.T, D + c.T, (size_t) c.T * (K::host_bytes - 1), hipMemcpyDeviceToHost));
+            }
+            if (verbose) fprintf(stderr, "[map] regions cut %.3f s, signals made and brought back %.3f s\n", t_regions, since(t0) - t_regions);
+            for (int j = 0; j < c.ns; ++j) {
+                const int k = j < m ? j : j - m;
+                const SpdpLocus& L = loci[c0 + k];
+                Problem& P = c.probs[j];
+                P.a = R.codes + R.offs[L.query]; P.a_len = (int32_t) (R.offs[L.query + 1] - R.offs[L.query]);
+                P.b = c.H + c.at[j]; P.b_len = L.len;
+                P.b_left = c.left(j); P.b_right = c.right(j);
+                // the query's range: the one given for this locus, else its own (the reverse leg: Seq::comrev mirrors it, Seq::rev_attr)
+                const int32_t al = c.rng ? c.rng[2 * k] : R.ql[L.query], ar = c.rng ? c.rng[2 * k + 1] : R.qr[L.query];
+                P.a_left = j < m ? al : P.a_len - ar; P.a_right = j < m ? ar : P.a_len - al;
+                P.a_exgl = P.a_exgr = P.b_exgl = P.b_exgr = 1;
+                R.point(c, j, P);
+                if (j < m) { c.hl[k] = hsps + L.hsp_off; c.hn[k] = L.n_hsp; }
+            }
+            R.sec[1] += since(t0);
+            // ---- the aligner on every locus, then the printer's scores
+            t0 = std::chrono::steady_clock::now();
+            const int rc = R.walk(c);
+            if (rc < 0) return -1;
+            if (rc > 0) ++R.partial;
+            R.sec[2] += since(t0);
+            if (verbose) {
+                int64_t st[12] = {0};
+                spdp_seeded_stats(ctx, st, 11);
+                fprintf(stderr, "[map] chunk of %d loci, %.1f M positions: regions + signals %.3f s; seeded call %.3f s (upload %.3f, walks with the device idle %.3f, "
+                        "device batches %.3f, handing back %.3f; %lld batches, %lld + %lld DP requests, %lld HSP searches)\n", m, c.tot / 1e6, R.sec[1], since(t0),
+                        st[6] / 1e6, st[7] / 1e6, st[8] / 1e6, st[9] / 1e6, (long long) st[0], (long long) st[1], (long long) st[2], (long long) st[4]);
+            }
+            t0 = std::chrono::steady_clock::now();
+            if (R.rescore(c)) return -1;
+            for (int k = 0; k < m; ++k) {
+                LocusOut o;
+                o.aligned = c.aln[k].n_skl >= 1;
+                o.g = no_gene();
+                if (o.aligned) R.rows(c, k, o);
+                sink(loci[c0 + k], std::move(o));
+            }
+            R.sec[3] += since(t0);
+        }
+        return 0;
+    }
+
+    int finish(double* seconds)
+    {
+        K& R = *this;
+        if (seconds) memcpy(seconds, R.sec, sizeof R.sec);
+        if (R.partial) { R.refuse("some walks met a state the seeded path does not serve; those loci come back without an alignment"); return 1; }
+        return 0;
+    }
+};
+using ChainS = Chain<KindS>;
+using ChainH = Chain<KindH>;
+
+// the steps once, every locus to the sink: -1, 0, or 1 (some loci came back without an alignment)
+template <class Chain>
+int run_once(Chain& R, const LocusSink& sink, double* seconds)
 {
-    if (seconds) memcpy(seconds, sec, sizeof sec);
-    if (partial) { ctx->err = "spdp_map_align_h: some walks met a state the seeded path does not serve; those loci come back without an alignment"; return 1; }
-    return 0;
-}
-
-}  // namespace
-
-static int map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                       const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
-                       const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
-                       const uint8_t* codes, const int64_t* offs, int32_t n,
-                       const LocusSink& sink, double* seconds)
-{
-    if (!ctx) return -1;
-    ChainH R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n};
     if (R.setup()) return -1;
-    if (n <= 0) return 0;
+    if (R.n <= 0) return 0;
     SpdpLocus* loci = nullptr; SpdpJuxt* hsps = nullptr; int32_t n_loci = 0;
-    if (R.find(codes, offs, R.ql.data(), R.qr.data(), nullptr, n, &loci, &n_loci, &hsps)) return -1;
+    if (R.find(R.codes, R.offs, R.ql.data(), R.qr.data(), R.tlen(), R.n, &loci, &n_loci, &hsps)) return -1;
     struct Owned { SpdpLocus* l; SpdpJuxt* h; ~Owned() { free(l); free(h); } } owned{loci, hsps};
     if (R.align(loci, n_loci, hsps, nullptr, sink)) return -1;
     return R.finish(seconds);
 }
 
-extern "C" int spdp_map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
-                                const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
-                                const uint8_t* codes, const int64_t* offs, int32_t n,
-                                SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
-{
-    if (!ctx) return -1;
-    if (!genes || !exons) { ctx->err = "spdp_map_align_h: null argument"; return -1; }
-    *exons = nullptr;
-    try {
-        BestSink best(std::max(n, 0));
-        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
-        const int rc = map_align_h(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, std::ref(best), seconds);
-        if (rc < 0 || n <= 0) return rc;
-        return best.finish(ctx, "spdp_map_align_h", n, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = "spdp_map_align_h: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
-        if (*exons) { free(*exons); *exons = nullptr; }
-        return -1;
-    }
-}
-
-extern "C" int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                      const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
-                                      const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
-                                      const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
-                                      int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
-{
-    if (!ctx) return -1;
-    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_h_multi: null argument"; return -1; }
-    *genes = nullptr; *exons = nullptr;
-    if (check_multi(ctx, "spdp_map_align_h_multi", hix, fprm)) return -1;
-    try {
-        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
-        const int rc = map_align_h(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, std::ref(multi), seconds);
-        if (rc < 0) return rc;
-        return multi.finish(ctx, "spdp_map_align_h_multi", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = "spdp_map_align_h_multi: out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
-        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
-        return -1;
-    }
-}
-
-// ---- the cDNA entries with the query preparation in front (include/spdp.h "query preparation")
-extern "C" int spdp_map_align_s_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                     const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                     const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                     const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
-                                     SpdpMapGene* genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails)
-{
-    if (!ctx) return -1;
-    if (!genes || !exons) { ctx->err = "spdp_map_align_s_prep: null argument"; return -1; }
-    *exons = nullptr;
-    try {
-        BestSink best(std::max(n, 0));
-        for (int i = 0; i < n; ++i) genes[i] = best.best[i];
-        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, 0, std::ref(best), seconds, prep, true, tails);
-        if (rc < 0 || n <= 0) return rc;
-        return best.finish(ctx, "spdp_map_align_s_prep", n, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = "spdp_map_align_s_prep: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        if (*exons) { free(*exons); *exons = nullptr; }
-        return -1;
-    }
-}
-
-extern "C" int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                           const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep, int32_t all_out,
-                                           int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails)
-{
-    if (!ctx) return -1;
-    if (!gene_off || !genes || !exons || !sp) { ctx->err = "spdp_map_align_s_multi_prep: null argument"; return -1; }
-    *genes = nullptr; *exons = nullptr;
-    if (check_multi(ctx, "spdp_map_align_s_multi_prep", hix, fprm)) return -1;
-    try {
-        MultiSink multi(std::max(n, 0), fprm->max_out, all_out, sp->vthr);
-        const int rc = map_align_s(ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, n, 0, std::ref(multi), seconds, prep, true, tails);
-        if (rc < 0) return rc;
-        return multi.finish(ctx, "spdp_map_align_s_multi_prep", std::max(n, 0), gene_off, genes, exons) ? -1 : rc;
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = "spdp_map_align_s_multi_prep: out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr;
-        return -1;
-    }
-}
+}  // namespace
 
 // ---- dispersed loci: quick4 around blkaln with algmode.mlt = 1 (`spaln -pr`; include/spdp.h "dispersed loci") ---------------------
 // quick4's rule alone (src/spaln.cc:1114-1134): which stretches of the query's range are searched again after its first search
@@ -878,8 +716,7 @@ int dispersed_pass(Chain& R, const std::vector<Piece>& pieces, bool whole_call, 
 // quick4 for every query of the call (src/spaln.cc:1114-1134): the first search on the query's own range, then in one further
 // pass every rest that is longer than min_seg_len; per search the locus blkaln prints with MaxOut = 1
 template <class Chain>
-int dispersed(Chain& R, const char* who, int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
-              int32_t* covered)
+int dispersed(Chain& R, int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part, int32_t* covered)
 {
     const int n = R.n;
     const int vthr = R.sp->vthr;
@@ -910,9 +747,9 @@ int dispersed(Chain& R, const char* who, int32_t min_seg_len, int64_t* gene_off,
     };
     for (int q = 0; q < n; ++q) report(first[q], o1[q]);
     for (size_t k = 0; k < rest.size(); ++k) report(rest[k], o2[k]);       // (a query's left rest stands before its right one)
-    if (hand_out(R.ctx, who, rep, n, gene_off, genes, exons)) return -1;
+    if (hand_out(R.ctx, R.who, rep, n, gene_off, genes, exons)) return -1;
     *part = (int32_t*) malloc(sizeof(int32_t) * std::max<size_t>((size_t) gene_off[n], 1));
-    if (!*part) { free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; R.ctx->err = std::string(who) + ": out of memory"; return -1; }
+    if (!*part) return R.refuse("out of memory");
     size_t k = 0;
     for (int q = 0; q < n; ++q) for (int32_t v : parts[q]) (*part)[k++] = v;
     return 0;
@@ -927,54 +764,160 @@ int check_dispersed(SpdpContext* ctx, const char* who, const SpdpBlkFindParams* 
     return 0;
 }
 
+// The frame of every entry: `needed` are the pointers the entry itself reads (the outputs among them), `outs` those of them it
+// hands memory out through -- nulled first, freed and nulled again on every failing path, so that a failed call hands nothing out.
+// body() gives the entry's return code.  Nothing of C++ crosses the C boundary.
+template <class Body>
+int entry(SpdpContext* ctx, const char* who, std::initializer_list<const void*> needed, std::initializer_list<void**> outs, Body body)
+{
+    if (!ctx) return -1;
+    for (const void* p : needed) if (!p) { ctx->err = std::string(who) + ": null argument"; return -1; }
+    for (void** p : outs) *p = nullptr;
+    int rc = -1;
+    try { rc = body(); }
+    catch (const std::bad_alloc&) { ctx->err = std::string(who) + ": out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)"; }
+    if (rc < 0) for (void** p : outs) { free(*p); *p = nullptr; }
+    return rc;
+}
+
+// the two sinks around run_once: the best locus per query into genes[n], and the list spaln -M prints
+template <class Chain>
+int best_only(Chain& R, SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
+{
+    const int n = R.n;
+    BestSink best(std::max(n, 0));
+    for (int i = 0; i < n; ++i) genes[i] = best.best[i];
+    const int rc = run_once(R, std::ref(best), seconds);
+    if (rc < 0 || n <= 0) return rc;
+    return best.finish(R.ctx, R.who, n, genes, exons) ? -1 : rc;
+}
+template <class Chain>
+int printed_lists(Chain& R, int32_t all_out, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
+{
+    if (check_multi(R.ctx, R.who, R.hix, R.fprm)) return -1;
+    const int n = std::max(R.n, 0);
+    MultiSink multi(n, R.fprm->max_out, all_out, R.sp->vthr);
+    const int rc = run_once(R, std::ref(multi), seconds);
+    if (rc < 0) return rc;
+    return multi.finish(R.ctx, R.who, n, gene_off, genes, exons) ? -1 : rc;
+}
+template <class Chain>
+int dispersed_lists(Chain& R, int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part, int32_t* covered,
+                    double* seconds)
+{
+    if (check_dispersed(R.ctx, R.who, R.fprm, R.sp, min_seg_len)) return -1;
+    R.n = std::max(R.n, 0);
+    if (R.setup()) return -1;
+    if (dispersed(R, min_seg_len, gene_off, genes, exons, part, covered)) return -1;
+    return R.finish(seconds);
+}
+
 }  // namespace
 
+// (every entry: what it was handed, as the chain holds it)
+#define CHAIN_BASE(who) ChainBase{who, ctx, ix, hix, genome, sp, fprm, codes, offs, n}
+
+extern "C" int spdp_map_align_s(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    int32_t ori, SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
+{
+    const char* who = "spdp_map_align_s";
+    return entry(ctx, who, {genes, exons}, {(void**) exons}, [&] {
+        ChainS R(CHAIN_BASE(who), sc, sigmodel, rp, ori);
+        return best_only(R, genes, exons, seconds);
+    });
+}
+
+extern "C" int spdp_map_align_s_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    int32_t ori, int32_t all_out, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons,
+                                      double* seconds)
+{
+    const char* who = "spdp_map_align_s_multi";
+    return entry(ctx, who, {gene_off, genes, exons, sp}, {(void**) genes, (void**) exons}, [&] {
+        ChainS R(CHAIN_BASE(who), sc, sigmodel, rp, ori);
+        return printed_lists(R, all_out, gene_off, genes, exons, seconds);
+    });
+}
+
+// ---- protein queries against the translated index
+extern "C" int spdp_map_align_h(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    SpdpMapGene* genes, SpdpMapExon** exons, double* seconds)
+{
+    const char* who = "spdp_map_align_h";
+    return entry(ctx, who, {genes, exons}, {(void**) exons}, [&] {
+        ChainH R(CHAIN_BASE(who), sc, sigmodel, rp);
+        return best_only(R, genes, exons, seconds);
+    });
+}
+
+extern "C" int spdp_map_align_h_multi(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    int32_t all_out, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds)
+{
+    const char* who = "spdp_map_align_h_multi";
+    return entry(ctx, who, {gene_off, genes, exons, sp}, {(void**) genes, (void**) exons}, [&] {
+        ChainH R(CHAIN_BASE(who), sc, sigmodel, rp);
+        return printed_lists(R, all_out, gene_off, genes, exons, seconds);
+    });
+}
+
+// ---- the cDNA entries with the query preparation in front (include/spdp.h "query preparation")
+extern "C" int spdp_map_align_s_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    const SpdpQueryPrep* prep, SpdpMapGene* genes, SpdpMapExon** exons, double* seconds,
+                                     SpdpQueryTail* tails)
+{
+    const char* who = "spdp_map_align_s_prep";
+    return entry(ctx, who, {genes, exons}, {(void**) exons}, [&] {
+        ChainS R(CHAIN_BASE(who), sc, sigmodel, rp, 0, prep, true, tails);
+        return best_only(R, genes, exons, seconds);
+    });
+}
+
+extern "C" int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+    const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    const SpdpQueryPrep* prep, int32_t all_out, int64_t* gene_off, SpdpMapGene** genes,
+                                           SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails)
+{
+    const char* who = "spdp_map_align_s_multi_prep";
+    return entry(ctx, who, {gene_off, genes, exons, sp}, {(void**) genes, (void**) exons}, [&] {
+        ChainS R(CHAIN_BASE(who), sc, sigmodel, rp, 0, prep, true, tails);
+        return printed_lists(R, all_out, gene_off, genes, exons, seconds);
+    });
+}
+
+// ---- dispersed loci (`spaln -pr`)
 extern "C" int spdp_map_align_s_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                          const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
-                                          const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
-                                          const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, const SpdpQueryPrep* prep,
-                                          int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
-                                          int32_t* covered, double* seconds, SpdpQueryTail* tails)
+    const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    int32_t ori, const SpdpQueryPrep* prep, int32_t min_seg_len, int64_t* gene_off,
+                                          SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part, int32_t* covered, double* seconds,
+                                          SpdpQueryTail* tails)
 {
     const char* who = "spdp_map_align_s_dispersed";
-    if (!ctx) return -1;
-    if (!gene_off || !genes || !exons || !part) { ctx->err = std::string(who) + ": null argument"; return -1; }
-    *genes = nullptr; *exons = nullptr; *part = nullptr;
-    if (check_dispersed(ctx, who, fprm, sp, min_seg_len)) return -1;
-    try {
-        ChainS R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, std::max(n, 0), ori};
-        if (R.setup(prep, prep != nullptr, tails)) return -1;
-        if (dispersed(R, who, min_seg_len, gene_off, genes, exons, part, covered)) return -1;
-        return R.finish(seconds);
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = std::string(who) + ": out of host memory (SPDP_MAP_CHUNK_MB sets the size of a chunk)";
-        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; free(*part); *part = nullptr;
-        return -1;
-    }
+    return entry(ctx, who, {gene_off, genes, exons, part}, {(void**) genes, (void**) exons, (void**) part}, [&] {
+        ChainS R(CHAIN_BASE(who), sc, sigmodel, rp, ori, prep, prep != nullptr, tails);
+        return dispersed_lists(R, min_seg_len, gene_off, genes, exons, part, covered, seconds);
+    });
 }
 
 extern "C" int spdp_map_align_h_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
-                                          const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel,
-                                          const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
-                                          const uint8_t* codes, const int64_t* offs, int32_t n, int32_t min_seg_len,
-                                          int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
-                                          int32_t* covered, double* seconds)
+    const SpdpScoringH* sc, const SpdpSeedParams* sp, const SpdpSignalModelH* sigmodel, const SpdpBlkFindParams* fprm, const SpdpRescoreParamsH* rp,
+    const uint8_t* codes, const int64_t* offs, int32_t n,
+    int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons,
+                                          int32_t** part, int32_t* covered, double* seconds)
 {
     const char* who = "spdp_map_align_h_dispersed";
-    if (!ctx) return -1;
-    if (!gene_off || !genes || !exons || !part) { ctx->err = std::string(who) + ": null argument"; return -1; }
-    *genes = nullptr; *exons = nullptr; *part = nullptr;
-    if (check_dispersed(ctx, who, fprm, sp, min_seg_len)) return -1;
-    try {
-        ChainH R{ctx, ix, hix, genome, sc, sp, sigmodel, fprm, rp, codes, offs, std::max(n, 0)};
-        if (R.setup()) return -1;
-        if (dispersed(R, who, min_seg_len, gene_off, genes, exons, part, covered)) return -1;
-        return R.finish(seconds);
-    }
-    catch (const std::bad_alloc&) {
-        ctx->err = std::string(who) + ": out of host memory (SPDP_MAP_CHUNK_MPOS sets the size of a chunk)";
-        free(*genes); *genes = nullptr; free(*exons); *exons = nullptr; free(*part); *part = nullptr;
-        return -1;
-    }
+    return entry(ctx, who, {gene_off, genes, exons, part}, {(void**) genes, (void**) exons, (void**) part}, [&] {
+        ChainH R(CHAIN_BASE(who), sc, sigmodel, rp);
+        return dispersed_lists(R, min_seg_len, gene_off, genes, exons, part, covered, seconds);
+    });
 }

@@ -5,6 +5,7 @@ library's, on genomes regenerated from their seeds and indexes made by the libra
 import ctypes as C
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -180,6 +181,54 @@ def test_one_locus_equals_the_best_only_entry(eng, name, run, ori):
             n_same += 1
         assert n_same >= len(c.queries) // 2
         assert any(len(v) > 1 for v in loci)                            # (MaxOut2 4: a choice to make)
+    finally:
+        c.free()
+
+
+def _chunk_lines(stderr):
+    return [ln for ln in stderr.splitlines() if ln.startswith("[map] chunk of ")]
+
+
+@pytest.mark.parametrize("name,run,ori", RUNS, ids=[r[1] for r in RUNS])
+def test_several_chunks_equal_one_chunk(eng, name, run, ori, monkeypatch, capfd):
+    """the chunk loop of the map + align chain: a call cut into at least three chunks of loci (SPDP_MAP_CHUNK_MPOS=1: 2^20 positions
+    each) reports what the same call in one chunk reports -- every locus (-pw), scores, val, n_loci and exon rows.  What can go
+    wrong only beyond one chunk: slot m + k of the other strand under ori = 3, the at[] offsets, the range rng[2 (c0 + k)].  The
+    `[map] chunk of` lines of SPDP_MAP_VERBOSE say how many chunks a call made.  A fixture whose loci fill fewer than three chunks
+    has its queries repeated k times, k the smallest number that gives three by the positions the one-chunk call printed (queries
+    are independent: every copy's lists must equal the first one's).  On these fixtures: S1 two copies, five chunks; S3 one copy,
+    five chunks; P four copies, three chunks"""
+    c = Case(eng, name)
+    try:
+        monkeypatch.setenv("SPDP_MAP_VERBOSE", "1")
+        for v in ("SPDP_MAP_CHUNK_MPOS", "SPDP_MAP_CHUNK_MB"):
+            monkeypatch.delenv(v, raising=False)
+
+        def call():
+            capfd.readouterr()
+            lists, _, rc = c.multi(True, ori)
+            assert rc == 0
+            return lists, _chunk_lines(capfd.readouterr().err)
+
+        one, lines = call()
+        assert len(lines) == 1, lines
+        # "... loci, %.1f M positions": at least this many (the figure is rounded to 10^5); three chunks are planned from 2 x 2^20 + 1 on
+        positions = float(re.search(r"([0-9.]+) M positions", lines[0]).group(1)) * 1e6 - 5e4
+        assert positions > 0, lines
+        k = int((2 << 20) // positions) + 1
+        n = len(c.queries)
+        if k > 1:
+            c.queries = c.queries * k
+            one, lines = call()
+            assert len(lines) == 1, lines
+        monkeypatch.setenv("SPDP_MAP_CHUNK_MPOS", "1")
+        cut, lines = call()
+        print("copies of the queries", k, "loci per chunk", [int(ln.split()[3]) for ln in lines])
+        assert len(lines) >= 3, (k, lines)
+        assert cut == one, [(i, a, b) for i, (a, b) in enumerate(zip(one, cut)) if a != b][:2]
+        assert sum(len(lst) for lst in one[:n]) > n                     # (several loci per query)
+        for j in range(1, k):
+            assert one[j * n:(j + 1) * n] == one[:n], j
     finally:
         c.free()
 
