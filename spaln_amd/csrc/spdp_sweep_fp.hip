@@ -14,7 +14,10 @@
 //     {H, Fcand(, Hlink, Fcandlink)};
 //   * "no acceptor yet" (hil <= llmt) is folded into the intron-penalty table: an entry is {A, C} and
 //     the candidate is max(hv2 + sig3 + A, floor) + C with {A, C} = {-2^22, nevsel - floor} for the
-//     short lengths, which yields exactly `nevsel` there, as the reference's blend does;
+//     short lengths, which yields exactly `nevsel` there, as the reference's blend does; a donor resets hil to
+//     1, such an entry, so a step reads its entry once hil is final and needs no "a donor fired" select;
+//   * hil advances by one entry per step with no clamp: the table carries SPDP_FPEN_PAD entries behind its
+//     SPDP_FPEN_TAB, every entry behind pen_cap prices like pen_cap, and hil is clamped once per block of 16 steps;
 //   * the bottom row leaves the stripe through LDS: its lane writes the step's {H, Fcand, links} into slot `step` of a
 //     16-entry block under a one-lane exec mask (a ds_write beside the VALU stream) and lane j reads slot j back at the
 //     flush; the block shares its LDS with the feed, which slot `step` no longer needs by then (round 2 used one 64-bit row_newbcast DPP per pair of values and step; the int kernels a rotate + shift per value).
@@ -38,7 +41,8 @@ namespace {
 enum { FL_SCORE = 0, FL_FORWARD = 1, FL_UDH = 2 };
 
 #define END_OF_ULK (INT32_MAX - 2)
-#define SPDP_FPEN_TAB 992                       // entries of the {A, C} penalty table in LDS
+#define SPDP_FPEN_TAB 992                       // entries of the {A, C} penalty table in LDS that a run may need (pen_cap < SPDP_FPEN_TAB)
+#define SPDP_FPEN_PAD 16                        // ... and behind them: hil runs up to 16 entries past pen_cap inside a block of 16 steps
 
 constexpr float NEVF = (float) SPDP_NEV16;
 constexpr float FLOORF = (float) SPDP_FLOOR16;
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     constexpr int RS = 80;
     __shared__ float  s_mtx[32 * 36];
     __shared__ int    s_perm[32];
-    __shared__ float2 s_pen[SPDP_FPEN_TAB];
+    __shared__ float2 s_pen[SPDP_FPEN_TAB + SPDP_FPEN_PAD];
     // per wave, per DPP row: 2 x 32-slot rings of column records (each record written twice, 32 slots apart: the
     // 31-column window of a block is contiguous) and the 16 boundary entries of the block
     __shared__ float2 s_sig[WPB][4][RS];                // {sig5 + ipen, sig3}
@@ -132,12 +136,15 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     const int nquant = sc->nquant, llmt = sc->llmt;
     // index of the last table entry: every hil >= pen_cap prices alike and is an acceptor candidate
     const int pen_cap = max(nquant > 1 ? sc->qm_len[nquant - 2] + 1 : 0, llmt + 1);
-    for (int h = threadIdx.x; SPJ && h <= pen_cap; h += blockDim.x) {
+    // the step advances hil without a clamp and a block of 16 steps clamps it once, where it starts: an index may pass
+    // pen_cap by up to 16, so every entry behind pen_cap, the pad included, holds the price of pen_cap
+    for (int e = threadIdx.x; SPJ && e < SPDP_FPEN_TAB + SPDP_FPEN_PAD; e += blockDim.x) {
         // pen(hil) = qm_pen[j] for the last j with hil > qm_len[j-1]  (fwd2s1_wip_simd.h:163-167); no candidate
         // unless hil > llmt: the blend leaves `nevsel` there
+        const int h = min(e, pen_cap);
         int pv = sc->qm_pen[0];
         for (int j = 1; j < nquant; ++j) if (h > sc->qm_len[j - 1]) pv = sc->qm_pen[j];
-        s_pen[h] = (h > llmt) ? make_float2(0.f, (float) pv) : make_float2(-BIGF, NEVF - FLOORF);
+        s_pen[e] = (h > llmt) ? make_float2(0.f, (float) pv) : make_float2(-BIGF, NEVF - FLOORF);
     }
     __syncthreads();
 
@@ -313,12 +320,13 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
         // candidate and its link), E, the diagonal neighbour, the donor state
         float Hs = NEVF, E = NEVF, Hd = NEVF, hv2 = NEVF;
         float Hg = hg0, Fm = fm0;
-        // hil is carried as the byte offset of its table entry; the entry itself is read one step ahead (for
-        // hil + 1, i.e. assuming no donor fires in between: a donor resets hil to 1, whose candidate is `nevsel`
-        // whatever the donor score, llmt >= 1) so that no LDS round trip sits inside the cell-to-cell recurrence
+        // hil is carried as the byte offset of its table entry, and ptc is that entry: read at the end of a step, where
+        // hil is final (a donor resets hil to 1, whose entry yields `nevsel` whatever the donor score, llmt >= 1), for
+        // the step after it.  The read sits inside the cell-to-cell recurrence of the wave; the other waves of the SIMD
+        // cover it.  (Until five waves fitted, the entry for hil + 1 was read a step ahead, on the guess that no donor
+        // fires, and a select per step put `nevsel` in when one had.)
         int hil8 = 0;
         float2 ptc = SPJ ? s_pen[0] : make_float2(0.f, 0.f);
-        bool don_prev = false;
         int Cs = 0, FCm = 0, Cd = 0, ec = 0, hc2 = 0;              // UDH links
         int donor_r = 0, rlst = INT32_MAX;                         // UDH, lane k8 only
         int* const outb = &s_io[wv][g][0];
@@ -445,7 +453,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                     }
 
                     // LDS operands are read ahead of the step that uses them: the matrix column offset three steps, the
-                    // substitution score two, signals, feed entry and penalty entry one
+                    // substitution score two, signals and feed entry one; the penalty entry at the end of the step before
                     int bofv[16]; float pvv[16]; float2 sgv[16]; int4 fdv[16];
                     code4[0] = code4[1] = code4[2] = code4[3] = 0;  // FWD: the 16 code bytes of my steps of this block
                     auto ld_feed = [&](int j) {
@@ -458,16 +466,12 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                     if constexpr (SPJ) sgv[0] = mysig[0];
                     pvv[0] = ld_pv(bofv[0]); pvv[1] = ld_pv(bofv[1]);
 
+                    if constexpr (SPJ) hil8 = min(hil8, cap8);     // once per block: the step lets hil run past pen_cap, into the table's pad
 #define STEP(J)                                                                                  \
                     {                                                                                        \
                         if constexpr (J + 3 < 16) bofv[J + 3] = mybof[J + 3];                                \
                         if constexpr (J + 2 < 16) pvv[J + 2] = ld_pv(bofv[J + 2]);                           \
                         if constexpr (J + 1 < 16) { fdv[J + 1] = ld_feed(J + 1); if constexpr (SPJ) sgv[J + 1] = mysig[J + 1]; } \
-                        int hil_n = 0; float2 pt_n = make_float2(0.f, 0.f);                                  \
-                        if constexpr (SPJ) {                                                                 \
-                            hil_n = min(hil8 + 8, cap8);                                                     \
-                            pt_n = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(s_pen) + hil_n); \
-                        }                                                                                    \
                         SPDP_PIN_LOADS();                                                                    \
                         /* neighbour exchange: lane 0 of the row takes the boundary entry of this step */    \
                         const int4 fd = fdv[J];                                                              \
@@ -505,7 +509,6 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                         if constexpr (SPJ) {                                                                 \
                             const float2 sg2 = sgv[J];                                                       \
                             float x = fmaxf(hv2 + sg2.y + ptc.x, FLOORF) + ptc.y;                            \
-                            x = don_prev ? NEVF : x;                                                         \
                             if constexpr (UDH) { is_acc = x > h; hc = is_acc ? hc2 : hc; }                   \
                             if constexpr (FWD) { is_acc = x > h; code = is_acc ? ((code & ~15u) | (unsigned) TB_ACCR) : code; } \
                             h = fmaxf(h, x);                                                                 \
@@ -514,8 +517,11 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                             is_don = qd > hv2;                                                               \
                             hv2 = fmaxf(hv2, qd);                                                            \
                             if constexpr (UDH) hc2 = is_don ? hc : hc2;                                      \
-                            hil8 = is_don ? 8 : hil_n;                                                       \
-                            ptc = pt_n; don_prev = is_don;                                                   \
+                            /* the entry the next step prices with, read where hil is final (no clamp here: the */ \
+                            /* block clamps once and the table's pad prices like pen_cap); issued ahead of the next */ \
+                            /* step's read-ahead loads, so the wait for it does not wait for them */          \
+                            hil8 = is_don ? 8 : hil8 + 8;                                                    \
+                            ptc = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(s_pen) + hil8); \
                             if constexpr (FWD) code |= is_don ? (unsigned) TB_DONR : 0u;                     \
                         }                                                                                    \
                         if constexpr (FWD) {                                                                 \
