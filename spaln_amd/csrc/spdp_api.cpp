@@ -611,6 +611,8 @@ int DevRun::lay_out(const std::vector<RunItem>& items, ItemShare& tot)
 // fp32 sweeps: every score must stay an exactly representable integer below 2^22 - 2^16 (the penalty table
 // pushes a candidate down by 2^22 to disable it).  Upper bound of a score: matches on every row, plus
 // whatever an intron can gain where the signals outweigh its penalties (never, with real parameters).
+// The step carries the gap opened from a cell unfloored (spdp_sweep_fp.hip, above its STEP): an E or F state at the floor
+// must not rise again by extension, so a positive gap extension stays with the int32 sweeps.
 static bool fp_range_ok(const DevStore* st, const std::vector<RunItem>& items)
 {
     int64_t rows = 0, cols_span = 0;
@@ -619,7 +621,7 @@ static bool fp_range_ok(const DevStore* st, const std::vector<RunItem>& items)
         cols_span = std::max<int64_t>(cols_span, it.b_right - it.b_left);
     }
     const int64_t ub = (rows + 1) * st->fp_maxpos + (st->fp_gain > 0 ? (cols_span + 1) * st->fp_gain : 0) + 65536;
-    return spdp_knob_on("SPDP_FP") && ub < (1ll << 22) - 65536;
+    return spdp_knob_on("SPDP_FP") && ub < (1ll << 22) - 65536 && st->sc.gep <= 0;
 }
 
 int DevRun::allocate(const ItemShare& tot)

@@ -43,6 +43,7 @@ enum { FL_SCORE = 0, FL_FORWARD = 1, FL_UDH = 2 };
 #define END_OF_ULK (INT32_MAX - 2)
 #define SPDP_FPEN_TAB 992                       // entries of the {A, C} penalty table in LDS that a run may need (pen_cap < SPDP_FPEN_TAB)
 #define SPDP_FPEN_PAD 16                        // ... and behind them: hil runs up to 16 entries past pen_cap inside a block of 16 steps
+#define SPDP_FPEN_LEAD 8                        // ... and in front of them: a donor at step J of a half block of 8 steps sets hil to entry 1 less J + 1 entries
 
 constexpr float NEVF = (float) SPDP_NEV16;
 constexpr float FLOORF = (float) SPDP_FLOOR16;
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     constexpr int RS = 80;
     __shared__ float  s_mtx[32 * 36];
     __shared__ int    s_perm[32];
-    __shared__ float2 s_pen[SPDP_FPEN_TAB + SPDP_FPEN_PAD];
+    __shared__ float2 s_pen[SPDP_FPEN_LEAD + SPDP_FPEN_TAB + SPDP_FPEN_PAD];
     // per wave, per DPP row: 2 x 32-slot rings of column records (each record written twice, 32 slots apart: the
     // 31-column window of a block is contiguous) and the 16 boundary entries of the block
     __shared__ float2 s_sig[WPB][4][RS];                // {sig5 + ipen, sig3}
@@ -138,13 +139,14 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     const int pen_cap = max(nquant > 1 ? sc->qm_len[nquant - 2] + 1 : 0, llmt + 1);
     // the step advances hil without a clamp and a block of 16 steps clamps it once, where it starts: an index may pass
     // pen_cap by up to 16, so every entry behind pen_cap, the pad included, holds the price of pen_cap
-    for (int e = threadIdx.x; SPJ && e < SPDP_FPEN_TAB + SPDP_FPEN_PAD; e += blockDim.x) {
+    // (entry e sits at s_pen[SPDP_FPEN_LEAD + e]; the lead is never read and is filled like entry 0)
+    for (int e = (int) threadIdx.x - SPDP_FPEN_LEAD; SPJ && e < SPDP_FPEN_TAB + SPDP_FPEN_PAD; e += blockDim.x) {
         // pen(hil) = qm_pen[j] for the last j with hil > qm_len[j-1]  (fwd2s1_wip_simd.h:163-167); no candidate
         // unless hil > llmt: the blend leaves `nevsel` there
-        const int h = min(e, pen_cap);
+        const int h = min(max(e, 0), pen_cap);
         int pv = sc->qm_pen[0];
         for (int j = 1; j < nquant; ++j) if (h > sc->qm_len[j - 1]) pv = sc->qm_pen[j];
-        s_pen[e] = (h > llmt) ? make_float2(0.f, (float) pv) : make_float2(-BIGF, NEVF - FLOORF);
+        s_pen[SPDP_FPEN_LEAD + e] = (h > llmt) ? make_float2(0.f, (float) pv) : make_float2(-BIGF, NEVF - FLOORF);
     }
     __syncthreads();
 
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     const float hg0 = as_f(__builtin_amdgcn_readfirstlane(as_i(fmaxf(NEVF + gnf, FLOORF))));
     const float fm0 = as_f(__builtin_amdgcn_readfirstlane(as_i(fmaxf(NEVF + gef, hg0))));
     const int ge = sc->gep;
-    const int cap8 = pen_cap * 8;               // hil is carried as the byte offset of its table entry
+    const int cap8 = (SPDP_FPEN_LEAD + pen_cap) * 8;    // hil is carried as the byte offset of its table entry in s_pen
 
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (uniform: a scalar, not a register of every lane)
     const int G = CROSS ? A.cross_g : 1;            // blocks cooperating on my problem
@@ -325,8 +327,8 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
         // the step after it.  The read sits inside the cell-to-cell recurrence of the wave; the other waves of the SIMD
         // cover it.  (Until five waves fitted, the entry for hil + 1 was read a step ahead, on the guess that no donor
         // fires, and a select per step put `nevsel` in when one had.)
-        int hil8 = 0;
-        float2 ptc = SPJ ? s_pen[0] : make_float2(0.f, 0.f);
+        int hil8 = SPDP_FPEN_LEAD * 8;
+        float2 ptc = SPJ ? s_pen[SPDP_FPEN_LEAD] : make_float2(0.f, 0.f);
         int Cs = 0, FCm = 0, Cd = 0, ec = 0, hc2 = 0;              // UDH links
         int donor_r = 0, rlst = INT32_MAX;                         // UDH, lane k8 only
         int* const outb = &s_io[wv][g][0];
@@ -351,7 +353,6 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
             // the reference's write condition (fwd2s1_wip_simd.h:205-209) as a range of the sweep step n0 + k
             const int fl_lo = max(b_left + j9, lw + (ml + 1) + 2 * j8);
             const int fl_hi = j9 > 0 ? min(up + (ml + 1) + 2 * j8 + 1, n_end) : INT32_MIN;
-            int lbm = 0;                                                // (16 lb) mod 32: where the block sits in the 32-slot rings
             auto prefetch = [&](int) {
                 if constexpr (UDH) nx_b = ldx_b4<CROSS>(brs, bnd, pf_b);
                 else { const int2 v = ldx_b2<CROSS>(brs, bnd, pf_b); nx_b.x = v.x; nx_b.y = v.y; }
@@ -394,6 +395,10 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
             for (int blk = 0; blk < tot && !dead; ++blk) {
                 if (blk + 1 < nb0) wait_for(blk + 1);
                 const int lb = blk - SPDP_GROUP_LAG * g;               // my local block number
+                // (16 lb) mod 32: where the block sits in the 32-slot rings.  The lag between the rows of a wave is even, so all
+                // rows are at the same position: a scalar (a register, an xor per block and two spills of the SIG form less)
+                static_assert(SPDP_GROUP_LAG % 2 == 0, "the rows of a wave share the ring position");
+                const int lbm = (blk & 1) << 4;
                 uint32_t code4[4] = {0, 0, 0, 0};
                 if (lb == -1 && nb > 0) prefetch(0);                    // one block ahead of first use
                 if (lb >= 0 && lb < nb) {
@@ -467,6 +472,26 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                     pvv[0] = ld_pv(bofv[0]); pvv[1] = ld_pv(bofv[1]);
 
                     if constexpr (SPJ) hil8 = min(hil8, cap8);     // once per block: the step lets hil run past pen_cap, into the table's pad
+                    // The gap opened from a cell is carried UNFLOORED, Hg = h + gop + gep, and the floor is the third operand of
+                    // the two maxima it feeds: E = max3(E + gep, Hg, floor), Fm = max3(F + gep, Hg, floor), one 4-cycle form each
+                    // where max(Hg, floor) first and a two-operand maximum then were three in all.  Exactness against the floored form
+                    // (Hg' = max(Hg, floor), as spdp_kernels.hip and the reference have it):
+                    //  * values: max3(x, Hg, floor) = max(x, max(Hg, floor)): E, Fm, and with them every H and every boundary
+                    //    entry {H, Fcand}, are bit for bit what they were, in every state;
+                    //  * the compares "extended, not opened" are x > Hg for x > Hg' (x = E + gep, F + gep): they differ only where
+                    //    Hg < x <= floor, i.e. in an E or F state whose value is the floor itself, and there the state keeps the
+                    //    link (UDH) / says "extended" (NHOR) where the floored form says "opened";
+                    //  * no cell ever takes such a state: H takes E or F only by a strict compare against an h >= floor (c1, c2
+                    //    below), so a taken E or F is above the floor; and an E or F at the floor never rises again by extension
+                    //    (gep <= 0), only by being opened anew from an H (DevRun turns gep > 0 away, spdp_api.cpp: fp_range_ok), which sets its link / bit from that H in both forms.
+                    //    A path that is walked back through E (F) states stays in states above the floor for the same reason:
+                    //    extension only lowers the value.  So the differing links and bits lie in states that no H, no
+                    //    boundary H link, no intermediate-row record of a path and no traceback ever reads, and this holds
+                    //    without any condition on the scores (nothing to add to DevRun's range check, spdp_api.cpp: fp_range_ok).
+                    //    The forward flavour's NVER bit is formed from the floored gap of the cell above, as before.
+                    //  The floor of the diagonal, h = max(Hd + pv, floor), can NOT be folded the same way: fin > Hd + pv for
+                    //  fin > max(Hd + pv, floor) turns DIAG into VERT in H states at the floor, which are on the reported path of
+                    //  every problem whose score ends at the floor (tests/test_gpu_fp_sweep_oracle.py: test_scores_at_the_floor).
 #define STEP(J)                                                                                  \
                     {                                                                                        \
                         if constexpr (J + 3 < 16) bofv[J + 3] = mybof[J + 3];                                \
@@ -484,7 +509,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                         if constexpr (UDH) ec = (ee > Hg) ? ec : Cs;                                         \
                         unsigned code = 0;                                                                   \
                         if constexpr (FWD) code = (ee > Hg) ? 0u : (unsigned) TB_NHOR;                       \
-                        E = fmaxf(ee, Hg);                                                                   \
+                        E = fmaxf(fmaxf(ee, Hg), FLOORF);                   /* (one v_max3_f32) */           \
                         float h; int hc = Cd, pb3 = 0;                                                       \
                         if constexpr (FWD) {                                                                 \
                             /* my F was opened (not extended) iff it equals the gap opened from the H above */ \
@@ -519,9 +544,13 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                             if constexpr (UDH) hc2 = is_don ? hc : hc2;                                      \
                             /* the entry the next step prices with, read where hil is final (no clamp here: the */ \
                             /* block clamps once and the table's pad prices like pen_cap); issued ahead of the next */ \
-                            /* step's read-ahead loads, so the wait for it does not wait for them */          \
-                            hil8 = is_don ? 8 : hil8 + 8;                                                    \
-                            ptc = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(s_pen) + hil8); \
+                            /* step's read-ahead loads, so the wait for it does not wait for them.  hil8 is the entry's */ \
+                            /* address less the share of the steps of this half block: the read's immediate offset adds */ \
+                            /* J + 1 entries, a donor sets the (inline) constant for which that lands on entry 1, and the */ \
+                            /* half block adds its 64 bytes once: a select per step and no add */             \
+                            hil8 = is_don ? (SPDP_FPEN_LEAD - (J & 7)) * 8 : hil8;                           \
+                            ptc = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(s_pen) + hil8 + 8 * ((J & 7) + 1)); \
+                            if constexpr ((J & 7) == 7) hil8 += 64;                                          \
                             if constexpr (FWD) code |= is_don ? (unsigned) TB_DONR : 0u;                     \
                         }                                                                                    \
                         if constexpr (FWD) {                                                                 \
@@ -547,10 +576,10 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                         Hd = upH; Hs = h;                                                                    \
                         if constexpr (UDH) { Cd = upC; Cs = hc; }                                            \
                         /* what follows from my cell: the gap opened from H, the row below's F candidate */  \
-                        Hg = fmaxf(h + gnf, FLOORF);                                                         \
+                        Hg = h + gnf;                                       /* (unfloored, see above the step) */ \
                         const float fe = fin + gef;                                                          \
                         if constexpr (UDH) FCm = (fe > Hg) ? fl : hc;                                        \
-                        Fm = fmaxf(fe, Hg);                                                                  \
+                        Fm = fmaxf(fmaxf(fe, Hg), FLOORF);                                                   \
                         /* bottom lane of the stripe -> slot J of the row's output block */                  \
                         if (is_bottom) {                                                                     \
                             if constexpr (UDH) reinterpret_cast<int4*>(outb)[J] = make_int4(as_i(Hs), as_i(Fm), Cs, FCm); \
@@ -581,7 +610,6 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                             else st_b2<CROSS>(bnd + st_p, reinterpret_cast<const int2*>(outb)[k]);
                         }
                         st_p += 16 * BW;
-                        lbm ^= 16;
                     }
                     if constexpr (FWD) {
                         uint4* dst = reinterpret_cast<uint4*>(A.tb + my_tb + 256ll * lb + 16 * k);
