@@ -340,6 +340,25 @@ int spdp_chunk_plan(const int64_t* cells, int n, int max_chunks, double ratio, i
  * out[] needs 2 n + 1 entries, returns the number written.  Host only (no device work). */
 int spdp_corner_list(const SpdpSkl* recs, int n, int m_unit, SpdpSkl* out);
 
+/* The linear-space ladder's decisions as pure functions (host only, no device work).  unit: genomic columns per query row,
+ * 1 for cDNA (lspS_ng, src/fwd2s1.cc:1801-1897), 3 for protein queries (lspH_ng, src/fwd2h1.cc:2140-2231);
+ * range = {a_left, a_right, b_left, b_right}. */
+enum { SPDP_PLAN_EMPTY = 0, SPDP_PLAN_ONE_SEQUENCE, SPDP_PLAN_DIAGONAL, SPDP_PLAN_TRACEBACK, SPDP_PLAN_LINEAR_SPACE };
+typedef struct SpdpLadderPlan { int32_t kind, n_imd, imd_intvl, recursive; } SpdpLadderPlan;   /* the last three: linear space only */
+/* What lsp[SH]_ng does with a range and its window w before any engine runs.  mode = scalar_engines, the others the
+ * scoring fields of the same names (noll is read for unit 1 only). */
+int spdp_ladder_plan(int unit, const int32_t range[4], const SpdpWindow* w, int mode, int recursive, int ubh,
+                     int max_vmf_space, int noll, SpdpLadderPlan* out);
+/* mimd_postwork (recursive = 0) / rcsv_postwork (1) on the (n_imd + 1) x 10 cpos rows of a linear-space call that wrote back
+ * `range`, inside a parent of a_len x b_len (read for unit 3 only): the Mfile records (m = a_left, n = b_left) and the calls it
+ * would queue, in order -- slabs to trace back and, recursive, half problems for the next round, each with its range, its
+ * b_exgl and its window (a0: the diagonal bounds of the rows; else the band of `sh`).  `local` is read for unit 1 only.
+ * Returns the number of steps; those beyond `cap` are not written. */
+enum { SPDP_STEP_RECORD = 0, SPDP_STEP_SLAB, SPDP_STEP_HALF };
+typedef struct SpdpLadderStep { int32_t kind, a_left, a_right, b_left, b_right, b_exgl; SpdpWindow w; } SpdpLadderStep;
+int spdp_ladder_postwork(int unit, int recursive, int a0, int local, int sh, const int32_t range[4], int a_len, int b_len,
+                         int n_imd, const int32_t* cpos, SpdpLadderStep* out, int cap);
+
 /* ---- rescoring: skl_rngS_ng (src/fwd2s1.cc:446) ---------------------------------------------- */
 /* The score the CLI prints and the per-exon records come from a walk over the finished corner
  * list, not from the DP engines.  Needs the exact-model inputs (SpdpScoring.intpen / t53,

@@ -18,28 +18,12 @@
 #include "../../include/spdp.h"
 #include "spdp_dev.h"
 #include "spdp_internal.h"
+#include "spdp_ladder.h"
 
 // ---- small helpers --------------------------------------------------------------
-static void stripe_rng(int a_left, int a_right, int b_left, int b_right, int sh, SpdpWindow* w)
-{   // stripe(), src/aln2.cc:156-176 (cmode 3)
-    if (sh < 0) {
-        int shorter = std::min(a_right - a_left, b_right - b_left);
-        sh = -sh * shorter / 100;
-    }
-    w->up = b_right - a_right;
-    w->lw = b_left - a_left;
-    if (w->up < w->lw) std::swap(w->up, w->lw);
-    w->up += sh;
-    w->lw -= sh;
-    int q;
-    if ((q = b_right - a_left) < w->up) w->up = q;
-    if ((q = b_left - a_right) > w->lw) w->lw = q;
-    w->width = w->up - w->lw + 3;
-}
-
 void spdp_stripe(const SpdpProblem* p, int sh, SpdpWindow* w)
-{
-    stripe_rng(p->a_left, p->a_right, p->b_left, p->b_right, sh, w);
+{   // stripe(), src/aln2.cc:156-176 (cmode 3)
+    ladder::stripe<1>(p->a_left, p->a_right, p->b_left, p->b_right, sh, w);
 }
 
 int64_t spdp_cells_w(int a_left, int a_right, int b_left, int b_right, const SpdpWindow& w)
@@ -90,7 +74,7 @@ RunItem spdp_item_of(const SpdpProblem& p, int parent, int sh)
     it.parent = parent;
     it.a_left = p.a_left; it.a_right = p.a_right; it.b_left = p.b_left; it.b_right = p.b_right;
     it.a_exgl = p.a_exgl; it.a_exgr = p.a_exgr; it.b_exgl = p.b_exgl; it.b_exgr = p.b_exgr;
-    stripe_rng(p.a_left, p.a_right, p.b_left, p.b_right, sh, &it.w);
+    ladder::stripe<1>(p.a_left, p.a_right, p.b_left, p.b_right, sh, &it.w);
     it.n_im = 0;
     return it;
 }

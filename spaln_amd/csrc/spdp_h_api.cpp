@@ -20,6 +20,7 @@
 #include "spdp_h_dev.h"
 #include "spdp_h_internal.h"
 #include "spdp_h_requests.h"
+#include "spdp_ladder.h"
 
 #define HIPCHK(call)                                                                     \
     do {                                                                                 \
@@ -38,27 +39,9 @@ static const int H_SKL_CAP = 4096;       // slot of one traceback record list; a
                                            // two per intron), and the slot is min(this, rows + columns + 8): protein queries stay far below
 
 // ---- geometry --------------------------------------------------------------------------
-static void stripe31_rng(int a_left, int a_right, int b_left, int b_right, int sh, SpdpWindow* w)
-{   // stripe31(), src/aln2.cc:178-198 (cmode 3)
-    if (sh < 0) {
-        int shorter = std::min(a_right - a_left, b_right - b_left);
-        sh = -sh * shorter / 100;
-    }
-    sh *= 3;
-    w->up = b_right - 3 * a_right;
-    w->lw = b_left - 3 * a_left;
-    if (w->up < w->lw) std::swap(w->up, w->lw);
-    w->up += sh;
-    w->lw -= sh;
-    int q;
-    if ((q = b_right - 3 * a_left) < w->up) w->up = q;
-    if ((q = b_left - 3 * a_right) > w->lw) w->lw = q;
-    w->width = w->up - w->lw + 7;
-}
-
 void spdp_stripe31(const SpdpProblemH* p, int sh, SpdpWindow* w)
-{
-    stripe31_rng(p->a_left, p->a_right, p->b_left, p->b_right, sh, w);
+{   // stripe31(), src/aln2.cc:178-198 (cmode 3)
+    ladder::stripe<3>(p->a_left, p->a_right, p->b_left, p->b_right, sh, w);
 }
 
 static int64_t cells31_rng(int a_left, int a_right, int b_left, int b_right, const SpdpWindow& w)
@@ -286,7 +269,7 @@ static HItem item_of(const SpdpProblemH& p, int top, int sh)
     it.top = it.slot = top;
     it.a_left = p.a_left; it.a_right = p.a_right; it.b_left = p.b_left; it.b_right = p.b_right;
     it.a_exgl = p.a_exgl; it.a_exgr = p.a_exgr; it.b_exgl = p.b_exgl; it.b_exgr = p.b_exgr;
-    stripe31_rng(p.a_left, p.a_right, p.b_left, p.b_right, sh, &it.w);
+    ladder::stripe<3>(p.a_left, p.a_right, p.b_left, p.b_right, sh, &it.w);
     return it;
 }
 
@@ -888,9 +871,8 @@ static bool bad_range(const HItem& it, const SpdpProblemH& p)
            it.a_right < it.a_left || it.b_right < it.b_left || it.b_left < p.exin_left || it.b_right > p.exin_right;
 }
 
-static thread_local int a0_mode = 0;             // SpdpScoringH.scalar_engines of the running ladder: 1 -A0, 2 -A1
-
-static bool queue_trcbk(const HItem& it, std::vector<HItem>& fwd, std::vector<HItem>& scl, bool scalar_ok, HTop& t)
+// mode: SpdpScoringH.scalar_engines of the running ladder (1 -A0, 2 -A1)
+static bool queue_trcbk(const HItem& it, int mode, std::vector<HItem>& fwd, std::vector<HItem>& scl, bool scalar_ok, HTop& t)
 {
     if (it.w.width < 0) return true;                         // NEVSEL, no records
     if (it.cut_r > it.cut_l) {                               // a cut range: always the scalar engine (:2004-2008)
@@ -902,12 +884,12 @@ static bool queue_trcbk(const HItem& it, std::vector<HItem>& fwd, std::vector<HI
         scl.push_back(it);
         return true;
     }
-    if (a0_mode == 1 || it.a_right - it.a_left < 8) {        // -A0, or below 8 rows: scalar forwardH_ng
+    if (mode == 1 || it.a_right - it.a_left < 8) {        // -A0, or below 8 rows: scalar forwardH_ng
         if (!scalar_ok) { t.cls = 1; return false; }
         scl.push_back(it);
         return true;
     }
-    if (a0_mode == 2) {                                      // -A1: forwardH1 (modes 3 / 5)
+    if (mode == 2) {                                         // -A1: forwardH1 (modes 3 / 5)
         if (!scalar_ok) { t.cls = 1; return false; }
         scl.push_back(it);
         scl.back().exact = true;
@@ -917,86 +899,62 @@ static bool queue_trcbk(const HItem& it, std::vector<HItem>& fwd, std::vector<HI
     return true;
 }
 
-// lspH_ng (src/fwd2h1.cc:2140-2180) up to the engine call
-static void queue_lsp(const SpdpScoringH& sc, const SpdpProblemH& p, HItem it, std::vector<HItem>& fwd, std::vector<HItem>& scl,
-                      bool scalar_ok, std::vector<HItem>& udh, HTop& t)
+// diagonalH_ng (src/fwd2h1.cc:1963-1995): one O(m) walk, host side in the reference's ladder as well
+static int diagonal_h(const SpdpScoringH& sc, const SpdpProblemH& p, const HItem& it, HTop& t)
 {
-    const int m = it.a_right - it.a_left, n = it.b_right - it.b_left;
-    if (!m && !n) { if (it.first) t.score = 0; return; }
-    if (!m || !n) {                                          // one sequence only: the two end records and the gap's
-        push_rec(t, it.a_left, it.b_left);                   // price (src/fwd2h1.cc:2148-2159; PwdB::GapPenalty /
-        push_rec(t, it.a_right, it.b_right);                 // GapExtPen / UnpPenalty3 / GapExtPen3, src/aln.h:275-304)
-        if (it.first) {
-            if (m) t.score = (it.a_exgl || it.a_exgr) ? (m > sc.codonk1 ? sc.lgep : sc.gep)
-                                                      : (m > sc.codonk1 ? sc.lgop + m * sc.lgep : sc.gop + m * sc.gep);
-            else if (it.b_exgl || it.b_exgr) t.score = n > sc.codonk1 ? sc.lgep : sc.gep;
-            else {
-                const int d = n / 3;
-                const int egop = n % 3 == 1 ? sc.gape1 : (n % 3 == 2 ? sc.gape2 : 0);
-                t.score = n <= sc.codonk1 ? d * sc.gep + egop : d * sc.gep - sc.diffu * (d - sc.k1) + egop;
-            }
-        }
-        return;
+    const bool LocalL = sc.local && it.a_exgl && it.b_exgl;
+    const bool LocalR = sc.local && it.a_exgr && it.b_exgr;
+    int scr = 0, maxh = SPDP_NEVSEL, mL = it.a_left, mR = it.a_right;
+    for (int mm = it.a_left; mm < it.a_right; ++mm) {
+        const int nn = it.b_left + 1 + 3 * (mm - it.a_left);
+        if (mm >= p.a_len || nn > p.b_len) break;
+        scr += sc.mtx[p.a[mm] * sc.mtx_cols + p.b[nn]] + p.sigE[nn];
+        if (LocalL && scr < 0) { scr = 0; mL = mm + 1; }
+        if (LocalR && scr > maxh) { maxh = scr; mR = mm + 1; }
     }
-    if (it.w.up == it.w.lw) {                                // diagonalH_ng (src/fwd2h1.cc:1963-1995): one O(m) walk,
-        const bool LocalL = sc.local && it.a_exgl && it.b_exgl;  // host side in the reference's ladder as well
-        const bool LocalR = sc.local && it.a_exgr && it.b_exgr;
-        int scr = 0, maxh = SPDP_NEVSEL, mL = it.a_left, mR = it.a_right;
-        for (int mm = it.a_left; mm < it.a_right; ++mm) {
-            const int nn = it.b_left + 1 + 3 * (mm - it.a_left);
-            if (mm >= p.a_len || nn > p.b_len) break;
-            scr += sc.mtx[p.a[mm] * sc.mtx_cols + p.b[nn]] + p.sigE[nn];
-            if (LocalL && scr < 0) { scr = 0; mL = mm + 1; }
-            if (LocalR && scr > maxh) { maxh = scr; mR = mm + 1; }
-        }
-        push_rec(t, mL, 3 * (mL - it.a_left) + it.b_left);
-        push_rec(t, mR, 3 * (mR - it.a_left) + it.b_left);
-        if (it.first) t.score = LocalR ? maxh : scr;
-        return;
-    }
-    if (std::abs(n - m) < 16 || m == 1 || n <= 3) { queue_trcbk(it, fwd, scl, scalar_ok, t); return; }
-    const float coef_B = 2.f, coef_C = 12.f;                 // sizeof(short); (Noll + 1) * sizeof(int)
-    float cvol = float(m) * (n + 3 * m);                     // rhombic, simd >= 2
-    if (a0_mode) {                                           // hexagonal, simd < 2 (src/fwd2h1.cc:2166-2169)
-        const float k = it.w.lw - it.b_left + 3 * it.a_right;
-        const float q = it.b_right - 3 * it.a_left - it.w.up;
-        cvol = float(m) * n - (k * k + q * q) / 6;
-    }
-    if (coef_B * cvol < sc.max_vmf_space) { queue_trcbk(it, fwd, scl, scalar_ok, t); return; }
-    bool recursive = sc.recursive != 0;                      // algmode.alg & 4
-    int n_imd = 1;
-    it.imd_intvl = (m + 1) / 2;
-    if (!recursive) {
-        const double z = 2. * m * coef_B / coef_C;
-        const int imd1 = int(pow(z, 1. / 3) + 0.5) - 1;
-        const float spc = coef_C * n * imd1 + coef_B * cvol / (imd1 + 1) / (imd1 + 1);
-        if (spc > sc.max_vmf_space) recursive = true;
-        else {
-            const int imd3 = m / 16;
-            n_imd = sc.ubh ? sc.ubh : std::min(imd1, imd3);
-            const int intvl = it.imd_intvl = (m + n_imd) / (n_imd + 1);
-            if (intvl * n_imd == m) --n_imd;
-            if (n_imd == 0) { queue_trcbk(it, fwd, scl, scalar_ok, t); return; }
-        }
-    }
-    if (a0_mode && !scalar_ok) { t.cls = 1; return; }
-    it.n_im = n_imd; it.recursive = recursive;
-    udh.push_back(it);
+    push_rec(t, mL, 3 * (mL - it.a_left) + it.b_left);
+    push_rec(t, mR, 3 * (mR - it.a_left) + it.b_left);
+    return LocalR ? maxh : scr;
 }
 
-// window of a slab: stripe31() under SIMD; under -A0 the diagonal bounds hirschbergH_ng recorded in the
-// cpos row (src/fwd2h1.cc:2068-2073, 2108-2128)
-static void slab_window(HItem& it, int sh, const int32_t* row)
+// lspH_ng (src/fwd2h1.cc:2140-2180) up to the engine call
+static void queue_lsp(const SpdpScoringH& sc, const SpdpProblemH& p, HItem it, int mode, std::vector<HItem>& fwd,
+                      std::vector<HItem>& scl, bool scalar_ok, std::vector<HItem>& udh, HTop& t)
 {
-    if (a0_mode != 1) { stripe31_rng(it.a_left, it.a_right, it.b_left, it.b_right, sh, &it.w); return; }
-    it.w.lw = row[8]; it.w.up = row[9];
-    it.w.width = it.w.up - it.w.lw + 7;
+    const ladder::Plan pl = ladder::plan<3>(it.a_left, it.a_right, it.b_left, it.b_right, it.w,
+                                            {mode, sc.recursive, sc.ubh, sc.max_vmf_space, 0});
+    int scr = 0;
+    switch (pl.kind) {
+    case ladder::EMPTY: break;
+    case ladder::ONE_SEQUENCE: {                             // the two end records and the gap's price (src/fwd2h1.cc:2148-2159;
+        const int m = it.a_right - it.a_left, n = it.b_right - it.b_left;    // PwdB::GapPenalty / GapExtPen / UnpPenalty3 /
+        push_rec(t, it.a_left, it.b_left);                   // GapExtPen3, src/aln.h:275-304)
+        push_rec(t, it.a_right, it.b_right);
+        if (m) scr = (it.a_exgl || it.a_exgr) ? (m > sc.codonk1 ? sc.lgep : sc.gep)
+                                              : (m > sc.codonk1 ? sc.lgop + m * sc.lgep : sc.gop + m * sc.gep);
+        else if (it.b_exgl || it.b_exgr) scr = n > sc.codonk1 ? sc.lgep : sc.gep;
+        else {
+            const int d = n / 3;
+            const int egop = n % 3 == 1 ? sc.gape1 : (n % 3 == 2 ? sc.gape2 : 0);
+            scr = n <= sc.codonk1 ? d * sc.gep + egop : d * sc.gep - sc.diffu * (d - sc.k1) + egop;
+        }
+        break;
+    }
+    case ladder::DIAGONAL: scr = diagonal_h(sc, p, it, t); break;
+    case ladder::TRACEBACK: queue_trcbk(it, mode, fwd, scl, scalar_ok, t); return;
+    default:
+        if (mode && !scalar_ok) { t.cls = 1; return; }
+        it.n_im = pl.n_imd; it.imd_intvl = pl.imd_intvl; it.recursive = pl.recursive != 0;
+        udh.push_back(it);
+        return;
+    }
+    if (it.first) t.score = scr;
 }
 
 static int run_ladder(HStore& st, bool ladder, std::vector<HTop>& tops, HStats& hs, const SpdhRequest* reqs = nullptr, int n_reqs = 0)
 {
     const SpdpScoringH& sc = st.sc;
-    a0_mode = ladder ? sc.scalar_engines : 0;
+    const int mode = ladder ? sc.scalar_engines : 0;
     tops.assign(reqs ? n_reqs : st.n, HTop());
     std::vector<HItem> pending, fwd, udh, scl;
     // explicit requests (the seeded walk, spdp_seeded_h.cpp): a sub-range of a resident parent with its own flags and
@@ -1012,7 +970,7 @@ static int run_ladder(HStore& st, bool ladder, std::vector<HTop>& tops, HStats& 
         if (q.kind == 0) { pending.push_back(it); continue; }
         it.nospj = q.kind == 3; it.cut_l = q.cut_l; it.cut_r = q.cut_r;
         if (bad_range(it, st.probs[it.top])) { tops[k].cls = 1; continue; }
-        queue_trcbk(it, fwd, scl, st.scalar_ok, tops[k]);
+        queue_trcbk(it, mode, fwd, scl, st.scalar_ok, tops[k]);
     }
     for (int i = 0; !reqs && i < st.n; ++i) {
         HItem it = item_of(st.probs[i], i, sc.sh);
@@ -1031,14 +989,14 @@ static int run_ladder(HStore& st, bool ladder, std::vector<HTop>& tops, HStats& 
         for (const HItem& it : pending) {
             if (tops[it.slot].cls) continue;
             if (bad_range(it, st.probs[it.top])) { tops[it.slot].cls = 1; continue; }
-            queue_lsp(sc, st.probs[it.top], it, fwd, scl, st.scalar_ok, udh, tops[it.slot]);
+            queue_lsp(sc, st.probs[it.top], it, mode, fwd, scl, st.scalar_ok, udh, tops[it.slot]);
         }
         pending.clear();
         // ---- linear-space round: cpos rows -> slabs (mimd_postwork) or halves (rcsv_postwork)
         if (!udh.empty()) {
             HUdhOut uo;
             std::vector<int> uflags(udh.size(), 0);
-            if (a0_mode ? run_scalar_udh(st, udh, uo, uflags, a0_mode == 2 ? 1 : 0)
+            if (mode ? run_scalar_udh(st, udh, uo, uflags, mode == 2 ? 1 : 0)
                         : sc.local ? run_scalar_udh(st, udh, uo, uflags, 2) : run_udh(st, udh, uo)) return -1;
             hs.udh_ms += uo.sweep_ms; hs.udh_cells += uo.cells;
             for (size_t u = 0; u < udh.size(); ++u) {
@@ -1053,50 +1011,19 @@ static int run_ladder(HStore& st, bool ladder, std::vector<HTop>& tops, HStats& 
                 const int32_t* rg = &uo.ranges[u * 4];
                 HItem cur = it;
                 cur.first = false; cur.n_im = 0; cur.recursive = false;
-                cur.a_left = rg[0]; cur.a_right = rg[1]; cur.b_left = rg[2]; cur.b_right = rg[3];
-#define CP(i, c) cpos[(i) * 10 + (c)]
-                if (CP(0, 0) == END_ULK) {                   // does not cross an intermediate row
-                    push_rec(t, cur.a_left, cur.b_left);
-                    push_rec(t, cur.a_right, cur.b_right);
-                } else if (it.recursive) {                   // rcsv_postwork, src/fwd2h1.cc:2091-2138
-                    cur.a_exgl = cur.a_exgr = cur.b_exgl = cur.b_exgr = 0;
-                    int c = 1;
-                    while (c < 9 && CP(0, c + 1) < END_ULK) { ++c; push_rec(t, CP(0, 0), CP(0, c)); }
-                    HItem h1 = cur, h2 = cur;
-                    h1.a_right = CP(0, 0); h1.b_right = CP(0, c);
-                    slab_window(h1, sc.sh, &CP(0, 0));
-                    h2.a_left = CP(0, 0); h2.b_exgl = CP(0, 1); h2.b_left = CP(0, 2);
-                    slab_window(h2, sc.sh, &CP(1, 0));
-                    pending.push_back(h1);
-                    pending.push_back(h2);
-                } else {                                     // mimd_postwork, src/fwd2h1.cc:2045-2089
-                    const int aleft = cur.a_left, bleft = cur.b_left;
-                    const int a_len = st.probs[it.top].a_len, b_len = st.probs[it.top].b_len;
-                    cur.a_exgl = cur.a_exgr = cur.b_exgl = cur.b_exgr = 0;
-                    int i = it.n_im;
-                    bool bad = false;
-                    while (--i >= 0 && CP(i, 0) == END_ULK) ;
-                    for ( ; i >= 0 && CP(i, 0) != END_ULK; --i) {
-                        int c = 0;
-                        cur.a_left = CP(i, c);
-                        cur.b_exgl = CP(i, ++c);
-                        cur.b_left = CP(i, ++c);
-                        if (cur.a_right > a_len || cur.b_right > b_len || cur.a_left < 0 || cur.b_left < 0) { bad = true; break; }
-                        if (cur.b_left < 0 || cur.b_left > cur.b_right) break;
-                        while (c < 9 && CP(i, c + 1) < END_ULK) { ++c; push_rec(t, cur.a_left, CP(i, c)); }
-                        ++c;
-                        slab_window(cur, sc.sh, &CP(i + 1, 0));
-                        if (!queue_trcbk(cur, fwd, scl, st.scalar_ok, t)) break;
-                        cur.a_right = cur.a_left;
-                        cur.b_right = CP(i, c - 1);
-                    }
-                    if (!bad && !t.cls && ((i < 0 && CP(0, 0) != END_ULK) || CP(0, 2) != END_ULK)) {
-                        cur.a_left = aleft; cur.b_left = bleft;
-                        slab_window(cur, sc.sh, &CP(0, 0));
-                        queue_trcbk(cur, fwd, scl, st.scalar_ok, t);
-                    }
-                }
-#undef CP
+                cur.a_exgl = cur.a_exgr = cur.b_exgr = 0;
+                auto item = [&](const ladder::Slab& s) {
+                    cur.a_left = s.al; cur.a_right = s.ar; cur.b_left = s.bl; cur.b_right = s.br; cur.b_exgl = s.b_exgl; cur.w = s.w;
+                    return cur;
+                };
+                auto sink = ladder::sink([&](int m, int n) { push_rec(t, m, n); },
+                                         [&](const ladder::Slab& s) { return queue_trcbk(item(s), mode, fwd, scl, st.scalar_ok, t); },
+                                         [&](const ladder::Slab& s) { pending.push_back(item(s)); });
+                if (cpos[0] == END_ULK) {                    // does not cross an intermediate row
+                    push_rec(t, rg[0], rg[2]);
+                    push_rec(t, rg[1], rg[3]);
+                } else ladder::postwork<3>(it.recursive, mode == 1, false, sc.sh, {rg[0], rg[1], rg[2], rg[3]},
+                                           st.probs[it.top].a_len, st.probs[it.top].b_len, it.n_im, cpos, sink);
             }
         }
         // ---- traceback round; sub-problems below 8 rows go through the scalar engine

@@ -3,9 +3,9 @@
 // What it mirrors (ogotoh/spaln v3.0.7):
 //   alignS_ng (ori = 1, seeding off)        src/fwd2s1.cc:2746-2760
 //   Aln2s1::globalS_ng                      src/fwd2s1.cc:2674-2694
-//   Aln2s1::lspS_ng   (decision ladder)     src/fwd2s1.cc:1801-1897
+//   Aln2s1::lspS_ng   (decision ladder)     src/fwd2s1.cc:1801-1897   (its decisions: spdp_ladder.h, shared with
+//   Aln2s1::mimd_postwork / rcsv_postwork   src/fwd2s1.cc:1714-1799    the protein ladder of spdp_h_api.cpp)
 //   Aln2s1::trcbkalignS_ng                  src/fwd2s1.cc:1667-1710
-//   Aln2s1::mimd_postwork / rcsv_postwork   src/fwd2s1.cc:1714-1799
 //   Aln2s1::diagonalS_ng                    src/fwd2s1.cc:1629-1665
 //   stdskl / trimskl                        src/gaps.cc:140-180, 254-273
 //
@@ -30,11 +30,11 @@
 
 #include "spdp_internal.h"
 #include "spdp_chunk_plan.h"
+#include "spdp_ladder.h"
 
 namespace {
 
 const int kEndOfUlk = SPDP_END_OF_ULK;
-const float kCoefB = 2.0f;                  // sizeof(short), src/fwd2s1.cc:58
 const int kScalarRows = 8;                  // trcbkalignS_ng: m < 8 goes to the scalar engine
 
 struct Rng { int al, ar, bl, br; uint8_t a_exgl, a_exgr, b_exgl, b_exgr; };
@@ -51,13 +51,7 @@ struct LspItem { int job; Rng r; SpdpWindow w; bool top; };
 struct TbItem  { int job; Rng r; SpdpWindow w; bool top; int cut_l = 0, cut_r = 0; };     // trcbkalignS_ng call (cut_r > cut_l: with a cut range)
 struct UdhItem { int job; Rng r; SpdpWindow w; bool top; int n_imd; bool recursive; int imd_intvl; };
 
-void stripe_of(const Rng& r, int sh, SpdpWindow* w)
-{
-    SpdpProblem p;
-    memset(&p, 0, sizeof p);
-    p.a_left = r.al; p.a_right = r.ar; p.b_left = r.bl; p.b_right = r.br;
-    spdp_stripe(&p, sh, w);
-}
+Rng rng_of(const ladder::Slab& s) { return {s.al, s.ar, s.bl, s.br, 0, 0, (uint8_t) s.b_exgl, 0}; }
 
 RunItem run_item(int parent, const Rng& r, const SpdpWindow& w, int n_im)
 {
@@ -256,122 +250,31 @@ struct Aligner {
     }
 
     // Aln2s1::lspS_ng up to the point where an engine is needed
-    bool classify(const LspItem& it, std::vector<UdhItem>& udh)
+    void classify(const LspItem& it, std::vector<UdhItem>& udh)
     {
         const SpdpScoring& sc = st->sc;
         const Rng& r = it.r;
         Job& J = jobs[it.job];
-        const int m = r.ar - r.al, n = r.br - r.bl;
-        if (!m && !n) { set_score(it.job, it.top, 0); return true; }
-        if (!m || !n) {
+        const ladder::Plan pl = ladder::plan<1>(r.al, r.ar, r.bl, r.br, it.w,
+                                                {sc.scalar_engines, sc.recursive, sc.ubh, sc.max_vmf_space, sc.noll});
+        switch (pl.kind) {
+        case ladder::EMPTY: set_score(it.job, it.top, 0); return;
+        case ladder::ONE_SEQUENCE: {
+            const int m = r.ar - r.al, n = r.br - r.bl;
             J.rec.push_back({r.al, r.bl});
             J.rec.push_back({r.ar, r.br});
             int scr;
             if (m) scr = (r.a_exgl || r.a_exgr) ? gap_ext_pen(sc, m) : gap_penalty(sc, m);
             else   scr = (r.b_exgl || r.b_exgr) ? gap_ext_pen(sc, n) : unp_penalty(sc, n);
             set_score(it.job, it.top, scr);
-            return true;
+            return;
         }
-        if (it.w.up == it.w.lw) {
-            set_score(it.job, it.top, diagonal_s(sc, probs[it.job], r, J.rec));
-            return true;
+        case ladder::DIAGONAL: set_score(it.job, it.top, diagonal_s(sc, probs[it.job], r, J.rec)); return;
+        case ladder::TRACEBACK: trcbk(it.job, r, it.w, it.top); return;
         }
-        if (abs(n - m) < 8 || m == 1 || n == 1) { trcbk(it.job, r, it.w, it.top); return true; }
-        int n_imd = 1;
-        bool recursive = sc.recursive != 0;     // algmode.alg & 4 (-A4 .. -A7)
-        float cvol = float(m) * (n + m);        // rhombic, simd >= 2
-        if (sc.scalar_engines >= 1) {           // hexagonal, simd < 2 (src/fwd2s1.cc:1830-1833)
-            const float k = it.w.lw - r.bl + r.ar;
-            const float q = r.br - r.al - it.w.up;
-            cvol = float(m) * n - (k * k + q * q) / 2;
-        }
-        if (kCoefB * cvol < sc.max_vmf_space) { trcbk(it.job, r, it.w, it.top); return true; }
-        int intvl = (m + 1) / 2;
-        if (!recursive) {
-            const float coef_C = (sc.noll + 1) * sizeof(int);
-            const double z = 2. * m * kCoefB / coef_C;
-            const int imd1 = int(pow(z, 1. / 3) + 0.5) - 1;
-            const float spc = coef_C * n * imd1 + kCoefB * cvol / (imd1 + 1) / (imd1 + 1);
-            if (spc > sc.max_vmf_space) recursive = true;
-            else {
-                const int imd3 = m / SPDP_NELEM;
-                n_imd = sc.ubh ? sc.ubh : std::min(imd1, imd3);
-                const int imd_intvl = intvl = (m + n_imd) / (n_imd + 1);
-                if (imd_intvl * n_imd == m) --n_imd;
-                if (n_imd == 0) { trcbk(it.job, r, it.w, it.top); return true; }
-            }
-        }
-        if (bad_range(it.job, r) || it.w.width < 3) { ++unsupported; J.failed = true; return true; }
-        if (sc.scalar_engines == 1 && !st->has_exact) { ++unsupported; J.failed = true; return true; }
-        if (sc.scalar_engines == 2 && !st->has_exact) { ++unsupported; J.failed = true; return true; }
-        udh.push_back({it.job, r, it.w, it.top, n_imd, recursive, intvl});
-        return true;
-    }
-
-    // window of a slab: stripe() under SIMD; under -A0 the diagonal bounds hirschbergS_ng recorded in
-    // the cpos row (src/fwd2s1.cc:1735-1740, 1778-1797)
-    void slab_window(const Rng& r, int sh, const int32_t* row, SpdpWindow* w) const
-    {
-        if (st->sc.scalar_engines != 1) { stripe_of(r, sh, w); return; }
-        w->lw = row[8]; w->up = row[9];
-        w->width = w->up - w->lw + 3;
-    }
-
-    // Aln2s1::mimd_postwork on the written-back ranges
-    void mimd(const UdhItem& u, const int32_t* cpos, Rng cur)
-    {
-        Job& J = jobs[u.job];
-        const int sh = st->sc.sh;
-        const int aleft = cur.al, bleft = cur.bl;
-        cur.a_exgl = cur.a_exgr = cur.b_exgl = cur.b_exgr = 0;
-#define CP(i, c) cpos[(i) * 10 + (c)]
-        int i = u.n_imd;
-        while (--i >= 0 && CP(i, 0) == kEndOfUlk) ;
-        for ( ; i >= 0 && CP(i, 0) != kEndOfUlk; --i) {
-            int c = 0;
-            cur.al = CP(i, c);
-            cur.b_exgl = CP(i, ++c) ? 1 : 0;
-            cur.bl = CP(i, ++c);
-            if (cur.bl < 0 || cur.bl > cur.br) break;
-            while (c < 9 && CP(i, ++c) < kEndOfUlk) J.rec.push_back({cur.al, CP(i, c)});
-            SpdpWindow vw;
-            slab_window(cur, sh, &CP(i + 1, 0), &vw);
-            trcbk(u.job, cur, vw, false);
-            cur.ar = cur.al;
-            cur.br = CP(i, c - 1);
-        }
-        if ((i < 0 && CP(0, 0) != kEndOfUlk) || CP(0, 2) != kEndOfUlk) {
-            cur.al = aleft; cur.bl = bleft;
-            SpdpWindow vw;
-            slab_window(cur, sh, &CP(0, 0), &vw);
-            trcbk(u.job, cur, vw, false);
-        }
-#undef CP
-    }
-
-    // Aln2s1::rcsv_postwork: two half problems for the next round
-    void rcsv(const UdhItem& u, const int32_t* cpos, Rng cur)
-    {
-        Job& J = jobs[u.job];
-        const int sh = st->sc.sh;
-        cur.a_exgl = cur.a_exgr = cur.b_exgl = cur.b_exgr = 0;
-        int c = 0;
-        if (cpos[c++] < kEndOfUlk) {
-            while (c < 9 && cpos[++c] < kEndOfUlk) J.rec.push_back({cpos[0], cpos[c]});
-            Rng first = cur;
-            first.ar = cpos[0]; first.br = cpos[c - 1];
-            SpdpWindow w;
-            slab_window(first, sh, cpos, &w);
-            pending.push_back({u.job, first, w, false});
-            Rng second = cur;
-            second.al = cpos[0]; second.b_exgl = cpos[1] ? 1 : 0; second.bl = cpos[2];
-            slab_window(second, sh, cpos + 10, &w);
-            pending.push_back({u.job, second, w, false});
-        } else if (st->sc.local) {
-            SpdpWindow w;
-            stripe_of(cur, sh, &w);
-            trcbk(u.job, cur, w, false);
-        }
+        if (bad_range(it.job, r) || it.w.width < 3) { ++unsupported; J.failed = true; return; }
+        if ((sc.scalar_engines == 1 || sc.scalar_engines == 2) && !st->has_exact) { ++unsupported; J.failed = true; return; }
+        udh.push_back({it.job, r, it.w, it.top, pl.n_imd, pl.recursive != 0, pl.imd_intvl});
     }
 
     double t_mark = 0;
@@ -415,7 +318,7 @@ struct Aligner {
             const SpdpProblem& p = probs[i];
             Rng r{p.a_left, p.a_right, p.b_left, p.b_right, p.a_exgl, p.a_exgr, p.b_exgl, p.b_exgr};
             SpdpWindow w;
-            stripe_of(r, sc.sh, &w);
+            ladder::stripe<1>(r.al, r.ar, r.bl, r.br, sc.sh, &w);
             if (req) {                          // a caller that made the reference's decisions up to the engine call itself
                 w = req->windows[base + i];
                 const int kind = req->kinds[base + i];
@@ -492,15 +395,16 @@ struct Aligner {
                 set_score(u.job, u.top, scr);
                 if (edge[k]) jobs[u.job].edge = true;
                 if (scr <= SPDP_NEVSEL) continue;
-                Rng curr = u.r;                 // ranges as written back by the engine
-                curr.al = ranges[4 * k]; curr.ar = ranges[4 * k + 1];
-                curr.bl = ranges[4 * k + 2]; curr.br = ranges[4 * k + 3];
+                const int32_t* rg = &ranges[4 * k];          // ranges as written back by the engine
                 const int32_t* cp = cpos.data() + k * stride;
-                if (cp[0] == kEndOfUlk) {
-                    jobs[u.job].rec.push_back({curr.al, curr.bl});
-                    jobs[u.job].rec.push_back({curr.ar, curr.br});
-                } else if (u.recursive) rcsv(u, cp, curr);
-                else mimd(u, cp, curr);
+                std::vector<SpdpSkl>& rec = jobs[u.job].rec;
+                auto sink = ladder::sink([&](int m, int n) { rec.push_back({m, n}); },
+                                         [&](const ladder::Slab& s) { trcbk(u.job, rng_of(s), s.w, false); return true; },
+                                         [&](const ladder::Slab& s) { pending.push_back({u.job, rng_of(s), s.w, false}); });
+                if (cp[0] == kEndOfUlk) {                       // does not cross an intermediate row
+                    rec.push_back({rg[0], rg[2]});
+                    rec.push_back({rg[1], rg[3]});
+                } else ladder::postwork<1>(u.recursive, a0, sc.local, sc.sh, {rg[0], rg[1], rg[2], rg[3]}, 0, 0, u.n_imd, cp, sink);
             }
         }
         lap("postwork (slab lists)");

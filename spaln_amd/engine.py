@@ -35,7 +35,7 @@ EXPORTS = [
     "spdp_align_s_seeded", "spdp_align_s_seeded_ori3", "spdp_seeded_stats",
     "spdp_blk_index_create", "spdp_blk_index_destroy", "spdp_blk_vote", "spdp_blk_vote_resident",
     "spdp_blk_search_opts_default", "spdp_blk_index_read", "spdp_blk_index_host_desc", "spdp_blk_index_host_free",
-    "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan",
+    "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan", "spdp_ladder_plan", "spdp_ladder_postwork",
     "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
     "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
 ]
@@ -138,6 +138,8 @@ def load_library() -> C.CDLL:
         getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.spdp_chunk_plan.restype = C.c_int
     lib.spdp_chunk_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
+    lib.spdp_ladder_plan.argtypes = [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+    lib.spdp_ladder_postwork.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.spdp_stripe.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.spdp_cells.argtypes = [C.c_void_p, C.c_void_p]
     for f in ("spdp_group_homscore_s", "spdp_group_align_s", "spdp_group_homscore_h", "spdp_group_align_h"):
