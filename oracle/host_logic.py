@@ -352,8 +352,8 @@ def skl_rng_s(sc, p, skl, *, codonk1, minl, jneibr, lsg=1):
         recs.append([int(rbuf[k]) for k in EIJ_FIELDS])
 
     if num >= 2 and corners[1][1] == corners[0][1] and p.b_exgl:
-        w += 1
-        num -= 1
+        w += 1  # unpinned: shared-n
+        num -= 1  # unpinned: shared-n
     m, n = corners[w]
     ai, bi = m, n                                        # as = a->at(m), bs = b->at(n)
     rbuf["left"], rbuf["rleft"], rbuf["iscr"], rbuf["sig3"] = n, m, abi.NEVSEL, 0

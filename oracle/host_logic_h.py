@@ -476,7 +476,7 @@ def skl_rng_h(sc, p, skl, *, intpen, t53, dinc, lgop, diffu, k1, gape1, gape2, e
             hi = abi.NEVSEL
             if insert:                                   # post-intron gap
                 if term and is_term(int(b[bi - 1])):
-                    insert -= 3
+                    insert -= 3  # unpinned: stop-gap
                 phs = insert % 3
                 insert -= phs
                 if not ((p.a_exgl and m == p.a_left) or (p.a_exgr and m == p.a_right)):
@@ -555,12 +555,12 @@ def skl_rng_h(sc, p, skl, *, intpen, t53, dinc, lgop, diffu, k1, gape1, gape2, e
                 ph3 = int(phs5[bbn]) if phs3[b3n] == 2 else int(phs3[b3n])
                 xm = xi = abi.NEVSEL
                 if ph3 == 2 and ph5 == 2:                # GTGT....AGAG
-                    nb = n + 1
-                    n3 = nb + i
-                    sig5m = int(sig5a[nb])
-                    xm = sig5m + spjscr(nb, n3)
-                    cm = _spjseq(b, p.b_left, p.b_right, nb, n3)
-                    ph3 = ph5 = 1
+                    nb = n + 1  # unpinned: gtgt
+                    n3 = nb + i  # unpinned: gtgt
+                    sig5m = int(sig5a[nb])  # unpinned: gtgt
+                    xm = sig5m + spjscr(nb, n3)  # unpinned: gtgt
+                    cm = _spjseq(b, p.b_left, p.b_right, nb, n3)  # unpinned: gtgt
+                    ph3 = ph5 = 1  # unpinned: gtgt
                 nb = n - ph3
                 n3 = nb + i
                 if ph5 == ph3 and ph5 > -2:              # isJunct
@@ -583,13 +583,13 @@ def skl_rng_h(sc, p, skl, *, intpen, t53, dinc, lgop, diffu, k1, gape1, gape2, e
                             fst["mch"] -= 1
                             fst["mmc"] += 1
                 if xm > xi:
-                    xi = xm
-                    ph3 = -1
-                    nb = n - ph3
-                    n3 = nb + i
-                    s5 = sig5m
-                    s3 = sig53_ie53(nb, n3)
-                    cs = cm
+                    xi = xm  # unpinned: gtgt
+                    ph3 = -1  # unpinned: gtgt
+                    nb = n - ph3  # unpinned: gtgt
+                    n3 = nb + i  # unpinned: gtgt
+                    s5 = sig5m  # unpinned: gtgt
+                    s3 = sig53_ie53(nb, n3)  # unpinned: gtgt
+                    cs = cm  # unpinned: gtgt
                 if xi > abi.NEVSEL:
                     if ph3 != -1:
                         cs = None

@@ -74,7 +74,7 @@ Wilip::Wilip(const Seq* seqs[], const PwdB* pwd, const int level)
 
 int main(int argc, const char** argv)
 {
-	int	ls = 2, sh = 100, local = 0, ubh = 0, nquant = 0, ori3 = 0, seeded_q = 0, crs = -1;
+	int	ls = 2, sh = 100, local = 0, ubh = 0, nquant = 0, ori3 = 0, seeded_q = 0, crs = -1, sup_tcodon = 0;
 	long	vmfspace = 0;
 const	char*	exg = 0;
 	std::vector<int>	udh_list, alg_list;
@@ -104,6 +104,7 @@ const	char*	exg = 0;
 		case 'b': bpprm.factor = atof(argv[++ai]); break;	// -yB: weight of the branch-point signal (simmtx.cc:671)
 		case 'D': bpprm.maxb3d = atoi(argv[++ai]); break;	// -yD: furthest branch point from its acceptor
 		case 'C': local = 3; break;			// -LC: local with LocalC (algmode.lcl & 32)
+		case 't': sup_tcodon = 1; break;		// OutPrm.supTcodon: skl_rngH_ng takes a closing stop codon off the last corner
 		case 'A': {
 		    const char* p = argv[++ai];
 		    while (*p) {
@@ -139,6 +140,7 @@ const	char*	files[2] = {argv[ai], argv[ai + 1]};
 const	char*	outfn = argv[ai + 2];
 
 	set_default_params();
+	if (sup_tcodon) OutPrm.supTcodon = 1;
 	optimize(GLOBAL, MAXIMUM);
 	algmode.qck = 0;		// -Q0: whole window through lspS_ng
 	algmode.blk = 0;

@@ -30,6 +30,7 @@ __global__ void spdp_rescore_s(RescoreArgs A)
     int num = A.skl_cnt[qi];
     int* hdr = A.out_hdr + 8 * qi;
     int* rec_out = A.out_rec + (int64_t) A.rec_off[qi] * 21;
+    const int rec_cap = (int) (A.rec_off[qi + 1] - A.rec_off[qi]);       // rows of this problem's slot (rec_off has n_probs + 1 entries)
     int n_rec = 0;
     const bool a_exgl = P.flags & 1, a_exgr = P.flags & 2, b_exgl = P.flags & 4, b_exgr = P.flags & 8;
     const int jn = A.jneibr;
@@ -65,7 +66,7 @@ __global__ void spdp_rescore_s(RescoreArgs A)
         rb[MCH3] = fst.mch - que[qp].mch; rb[MMC3] = fst.mmc - que[qp].mmc;
         rb[UNP3] = fst.unp - que[qp].unp; rb[GAP3] = fst.gap - que[qp].gap;
     };
-    auto push = [&]() { for (int i = 0; i < 21; ++i) rec_out[21 * n_rec + i] = rb[i]; ++n_rec; };
+    auto push = [&]() { if (n_rec < rec_cap) for (int i = 0; i < 21; ++i) rec_out[21 * n_rec + i] = rb[i]; ++n_rec; };   // counts on: the host refuses n_rec > rec_cap
     // edit records: format 1 Cigar {ope, len}, 2 Vulgar {ope, alen, blen}, 3 SAM {ope, len}
     const int fmt = A.ops_format;
     int3* ops = fmt ? A.ops + A.ops_off[qi] : nullptr;
@@ -214,6 +215,7 @@ __global__ void spdh_rescore(HRescoreArgs A)
     int num = A.skl_cnt[qi];
     int* hdr = A.out_hdr + 8 * qi;
     int* rec_out = A.out_rec + (int64_t) A.rec_off[qi] * 21;
+    const int rec_cap = (int) (A.rec_off[qi + 1] - A.rec_off[qi]);       // rows of this problem's slot (rec_off has n_probs + 1 entries)
     int n_rec = 0;
     const int jn = A.jneibr;
     const int AMBc = 2, SERc = 18, SER2c = 23, TRM2c = 24, TRMc = 25;
@@ -278,7 +280,7 @@ __global__ void spdh_rescore(HRescoreArgs A)
         rb[MCH3] = fst.mch - que[qp].mch; rb[MMC3] = fst.mmc - que[qp].mmc;
         rb[UNP3] = fst.unp - que[qp].unp; rb[GAP3] = fst.gap - que[qp].gap;
     };
-    auto push = [&]() { for (int i = 0; i < 21; ++i) rec_out[21 * n_rec + i] = rb[i]; ++n_rec; };
+    auto push = [&]() { if (n_rec < rec_cap) for (int i = 0; i < 21; ++i) rec_out[21 * n_rec + i] = rb[i]; ++n_rec; };   // counts on: the host refuses n_rec > rec_cap
     // edit records (Cigar::push / Vulgar::push, src/fwd2h1.cc:695-924): format 1 Cigar {ope, len}, 2 Vulgar {ope, alen, blen}
     const int fmt = A.ops_format;
     int3* ops = fmt ? A.ops + A.ops_off[qi] : nullptr;

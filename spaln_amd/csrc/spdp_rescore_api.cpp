@@ -62,8 +62,13 @@ static int rescore_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpRescoreP
         soff.push_back((int64_t) skl.size()); scnt.push_back(cnt);
         skl.insert(skl.end(), aln[i].skl + 1, aln[i].skl + 1 + cnt);
         roff.push_back(rtot);
-        rtot += cnt / 2 + 3;                                 // an exon needs two corners; + last exon, end marker
+        // rows of this problem's slot.  The walk takes one step per corner after the first (cnt - 1 steps), a step pushes at most
+        // one record (an accepted intron closes one exon), and the walk ends with the last exon and the end marker: cnt + 1.  This
+        // holds for every monotone corner list, the condensed ones included (a diagonal run and the gap behind it in one step:
+        // then every step can close an exon); cnt / 2 + 3 only held for lists that spend two corners on an exon
+        rtot += cnt + 1;
     }
+    roff.push_back(rtot);                                    // n + 1 entries: the kernel reads its slot's size from them
     const int nr = (int) idx.size();
     if (!nr) return 0;
     DevPool& pool = ctx->pool[R_POOL];
@@ -71,7 +76,7 @@ static int rescore_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpRescoreP
     void* d_skl = pool.get(RP_SKL, skl.size() * sizeof(SpdpSkl));
     void* d_soff = pool.get(RP_SOFF, nr * sizeof(int64_t));
     void* d_scnt = pool.get(RP_SCNT, nr * sizeof(int));
-    void* d_roff = pool.get(RP_ROFF, nr * sizeof(int64_t));
+    void* d_roff = pool.get(RP_ROFF, (nr + 1) * sizeof(int64_t));
     void* d_hdr = pool.get(RP_HDR, (size_t) nr * 8 * sizeof(int));
     void* d_rec = pool.get(RP_REC, (size_t) rtot * 21 * sizeof(int));
     if (!d_probs || !d_skl || !d_soff || !d_scnt || !d_roff || !d_hdr || !d_rec) { ctx->err = "out of device memory"; return -1; }
@@ -79,7 +84,7 @@ static int rescore_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpRescoreP
     HIPCHK(hipMemcpyAsync(d_skl, skl.data(), skl.size() * sizeof(SpdpSkl), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_soff, soff.data(), nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_scnt, scnt.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_roff, roff.data(), nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_roff, roff.data(), (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     RescoreArgs A;
     memset(&A, 0, sizeof A);
     A.sc = (const DevScoring*) st.d_sc; A.probs = (const DevProblem*) d_probs; A.n_probs = nr;
@@ -125,8 +130,8 @@ static int rescore_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpRescoreP
     HIPCHK(hipMemcpyAsync(hdr.data(), d_hdr, hdr.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(rec.data(), d_rec, rec.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < nr; ++s)
-        if (hdr[(size_t) s * 8 + 7]) { ctx->err = "rescoring (protein): a read outside the region window held on the device (SPDP_RESCORE_WINDOW=0 holds whole regions)"; return -1; }
+    for (int s = 0; s < nr; ++s)                             // the kernel counts past a full slot without writing
+        if (hdr[(size_t) s * 8 + 6] > roff[s + 1] - roff[s]) { ctx->err = "exon records: slot too small"; return -1; }
     for (int s = 0; s < nr && out; ++s) {
         SpdpRescored& o = out[idx[s]];
         const int* h = &hdr[(size_t) s * 8];
@@ -244,8 +249,16 @@ static int rescore_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpRescore
         soff.push_back(skl_tot); scnt.push_back(cnt);
         skl_tot += cnt;
         roff.push_back(rtot);
-        rtot += cnt + 3;                                    // exons, frame-shift records, end marker
+        // rows of this problem's slot.  The walk takes at most cnt steps (cnt - 1 corners after the first, and one more when an intron
+        // candidate is still open behind the last corner).  A step pushes at most one record.  An open candidate (hi > NEVSEL) is
+        // settled at the top of the very next step, whatever that step is (`h > NEVSEL && hi > NEVSEL`), so the pending insertion
+        // is then exactly preint + intlen: if the intron is accepted (one push) nothing is left for an insertion frame shift in that
+        // step, and if it is not, only the frame shift can push.  A deletion frame shift needs a pending deletion, and the two
+        // gaps are never pending together (the step that opens one flushes the other).  With the last exon and the end marker:
+        // cnt + 2 <= cnt + 3
+        rtot += cnt + 3;
     }
+    roff.push_back(rtot);                                    // n + 1 entries: the kernel reads its slot's size from them
     // the region pieces go through the context's pinned staging blocks when it has them (no zero fill, and the bus at its rate: a map +
     // align call rescoring 20 000 loci moves 2 GB here); pageable vectors otherwise
     a_all.resize((size_t) a_tot); skl.resize((size_t) skl_tot);
@@ -290,7 +303,7 @@ static int rescore_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpRescore
     void* d_skl = pool.get(RP_SKL, skl.size() * sizeof(SpdpSkl));
     void* d_soff = pool.get(RP_SOFF, nr * sizeof(int64_t));
     void* d_scnt = pool.get(RP_SCNT, nr * sizeof(int));
-    void* d_roff = pool.get(RP_ROFF, nr * sizeof(int64_t));
+    void* d_roff = pool.get(RP_ROFF, (nr + 1) * sizeof(int64_t));
     void* d_hdr = pool.get(RP_HDR, (size_t) nr * 8 * sizeof(int));
     void* d_rec = pool.get(RP_REC, (size_t) rtot * 21 * sizeof(int));
     if (!d_mtx || !d_probs || !d_a || !d_b || !d_sig || !d_phs || !d_dinc || !d_intpen || !d_skl || !d_soff ||
@@ -335,6 +348,8 @@ static int rescore_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpRescore
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int s = 0; s < nr; ++s)
         if (hdr[(size_t) s * 8 + 7]) { ctx->err = "rescoring (protein): a read outside the region window held on the device (SPDP_RESCORE_WINDOW=0 holds whole regions)"; return -1; }
+    for (int s = 0; s < nr; ++s)                             // the kernel counts past a full slot without writing
+        if (hdr[(size_t) s * 8 + 6] > roff[s + 1] - roff[s]) { ctx->err = "exon records: slot too small"; return -1; }
     for (int s = 0; s < nr && out; ++s) {
         SpdpRescored& o = out[idx[s]];
         const int* h = &hdr[(size_t) s * 8];

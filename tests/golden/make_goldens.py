@@ -244,6 +244,8 @@ def protein_cases():
     c = {}
     g = pgene(1, n_exons=3, aa_len=120, flank=200, intron_hi=600)
     c["h1_basic"] = (g.window, g.query, ["-u", "1,2,3"])
+    # the same with OutPrm.supTcodon on: the planted coding region ends in TAA, which skl_rngH_ng takes off the last corner
+    c["h1_suptcodon"] = (g.window, g.query, ["-t", "-u", "1,2"])
     g = pgene(2, n_exons=5, aa_len=400, flank=400, intron_hi=1200)
     c["h1_400aa"] = (g.window, g.query, ["-u", "1,4,7"])
     g = pgene(3, n_exons=1, aa_len=100, flank=150)
@@ -270,6 +272,12 @@ def protein_cases():
     g = pgene(8, n_exons=4, aa_len=160, flank=200, intron_hi=400, sub=0.15)
     c["h1_local"] = (g.window, g.query, ["-L", "-u", "1,2"])
     c["h1_local_udh"] = (g.window, g.query, ["-L", "-V", "100000", "-u", "3"])
+    # a local alignment of the residues of the two inner exons alone, both cut in phase 0: it opens behind an acceptor and closes at a
+    # donor, where skl_rngH_ng's end bonuses (`lcl & 20`: sig3 at the first corner, `lcl & 24`: sig5 at the last) take the splice signals
+    g = pgene(115, n_exons=4, aa_len=160, flank=200, intron_hi=400, sub=0.1)
+    cds = np.cumsum([0] + [b - a for a, b in g.exons])
+    assert cds[1] % 3 == 0 and cds[3] % 3 == 0
+    c["h1_local_inner"] = (g.window, g.query[cds[1] // 3:cds[3] // 3], ["-L", "-u", "1,2"])
     # window = the coding sequence, no shoulder: stripe31() gives up == lw and lspH_ng takes diagonalH_ng
     g2 = pgene(31, n_exons=1, aa_len=60, flank=0, sub=0.1)
     c["h1_diagonal"] = (g2.window[:3 * len(g2.query)], g2.query, ["-w", "0"])

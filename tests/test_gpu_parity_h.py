@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 H_FILES = golden_files("h1_")
 UNDEFINED = {"h1_cut_right", "h1_random"}     # the reference starts its traceback outside its bitmap
-LOCAL = {"h1_local", "h1_local_udh"}          # -LS: its own kernel variants, run separately
+LOCAL = {"h1_local", "h1_local_udh", "h1_local_inner"}          # -LS: its own kernel variants, run separately
 BELOW_8 = {"h1_tiny_m3", "h1_tiny_m5", "h1_tiny_m7"}   # every dispatch sends these to the scalar engine
 
 
