@@ -614,7 +614,7 @@ typedef struct SpdpWilipModel {
     SpdpWilipLevel level[3];
     int32_t mtx_rows, mtx_cols;      /* getSimmtx(WlnPamNo): query code x genomic code (nucleotide or tron)              */
     int32_t mtx[32 * 32];
-    int32_t dvsp;                    /* PwdB::DvsP: 0 nucleotide query, 1 protein query x tron codes                      */
+    int32_t dvsp;                    /* PwdB::DvsP: 0 nucleotide query, 1 protein query x tron codes, 3 protein pairs    */
     int32_t end_bonus;               /* Wlprms::EndBonus = (VTYPE) AvTrc() / 2 (src/wln.cc:146)                           */
     int32_t crs, lsg, mlt;           /* algmode.crs, lsg, mlt                                                             */
     int32_t hard_minl, hard_maxl, minl, maxl, llmt;                           /* IntronPrm                                */
@@ -1235,6 +1235,37 @@ int spdp_skl_edits_b(const SpdpScoring* sc, const SpdpUnsplicedParams* up, const
 int64_t spdp_cells_b(const SpdpProblem* p, const SpdpWindow* wdw);
 /* device bytes of one problem's traceback store (what is held against max_trace_bytes) */
 int64_t spdp_trace_bytes_b(const SpdpProblem* p, const SpdpWindow* wdw);
+
+/* alignB_ng with seeding on (algmode.qck = 1 .. 3: `spaln -Q1 .. -Q3` on two protein files; -Q3 is the program's default):
+ * Aln2b1::globalB_ng -> seededB_ng (src/fwd2b1.cc:1531-1560, 1404-1529).  The HSPs of a pair are searched with words at up to
+ * three levels (Wilip, the aaprm rows of src/wln.cc:104-107), neighbouring HSPs are joined by closed forms (backforth,
+ * creepback, creepfwrd, src/fwd2b1.cc:1342-1402), and lspB_ng runs only on the gaps left between them; all records go to one
+ * file.  The walks of all pairs run side by side on host threads; a walk that needs a DP result waits, and the waiting
+ * requests run as one round on the residues of the call's pairs, uploaded once: requests of at most 16 rows through the thin
+ * form of the sweep, four per wave (SPDP_B_THIN=0 in the environment: all through the tiled form), the others through the tiled
+ * sweep, the branches of lspB_ng without a DP cell on the host.  Every request takes the direct traceback.  max_trace_bytes
+ * governs a round as it governs a chunk of spdp_align_b; a pair with a request that alone exceeds it comes back "not computed"
+ * (score SPDP_NEVSEL, n_skl 0) and the call returns 1 after serving all others.
+ * Arguments as spdp_align_s_seeded (hsps[i] / n_hsps[i]: b->jxt / b->CdsNo with the free slot behind the last HSP, or none;
+ * lowest_level[i]: b->wllvl; src: the caller's HSP search, or NULL).  Of SpdpSeedParams it reads qck, wl_width, vthr (PwdB::Vthr),
+ * lcl (bit 16 must agree with SpdpScoring.local) and wilip: the protein-pair model (dvsp = 3, lsg = 0: the sequences are presented
+ * to the search with bbt = 1 as AvsA sets them, src/spaln.cc:713), needed when qck > 1 or when a pair brings no HSPs and no src
+ * answers.  Anything it does not serve is refused with -1 and a message that names the field.  tgapf is applied by the requests'
+ * boundaries exactly as in spdp_align_b: the reference's seeded path runs the same forwardB_ng.
+ * out[i] as spdp_align_b returns it (header + corners for spdp_skl_rng_b / spdp_skl_edits_b); a pair the program prints no
+ * record for comes back with n_skl = 0. */
+int spdp_align_b_seeded(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp,
+                        const SpdpProblem* probs, int n_probs, const SpdpJuxt* const* hsps, const int32_t* n_hsps,
+                        const int32_t* lowest_level, const SpdpHspSource* src, SpdpAlignment* out);
+/* counters of the last spdp_align_b_seeded call on this context: [0] walks, [1] HSP searches, [2] device batches (launch sets),
+ * DP requests [3] served by the thin kernel, [4] by the tiled kernel, [5] on the host without a cell; [6] requests of at most
+ * 16 rows (whatever served them), [7] their DP cells, [8] DP cells of all device requests, [9] requests above max_trace_bytes;
+ * microseconds: [10] the walks' host code (device idle), [11] device batches (walks asleep), [12] the call */
+int spdp_seeded_stats_b(const SpdpContext* ctx, int64_t* out, int n);
+/* what spdp_align_b_seeded says about a bundle before it touches the device: NULL when it serves it, else the message of its
+ * refusal (a static string).  hsps_for_all: every pair brings its HSPs; has_src: an SpdpHspSource answers.  Host code. */
+const char* spdp_align_b_seeded_refusal(const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp,
+                                        int hsps_for_all, int has_src);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,8 @@
 //            longest problems first
 #include "spdp_internal.h"
 #include "spdp_b_dev.h"
+#include "spdp_b_host.h"
+#include "spdp_b_walk.h"
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -14,23 +16,13 @@
 
 hipError_t spdp_b_launch(hipStream_t s, bool score, bool dagp, int n, const DevScoringB* sc, const DevProblemB* probs, const uint8_t* codes,
                          int32_t* rowp, int32_t* lastc, uint8_t* trace, int2* recs, DevResultB* res);
+hipError_t spdp_b_launch_round(hipStream_t s, bool dagp, int n_wide, int n_thin, const DevScoringB* sc, const DevProblemB* probs,
+                               const uint8_t* codes, int32_t* rowp, int32_t* lastc, uint8_t* trace, int2* recs, DevResultB* res);
 
 namespace {
 
-constexpr int LARGEN = INT_MAX / 4 * 3;                 // src/aln.h:45
+using namespace spdp_bh;
 constexpr int64_t DEFAULT_TRACE_BYTES = (int64_t) 4 << 30;
-enum { BP_SC = 0, BP_PROBS, BP_CODES, BP_ROWP, BP_LASTC, BP_TRACE, BP_RECS, BP_RES };    // slots of ctx->pool[B_POOL]
-
-// PwdB::GapPenalty / GapExtPen / UnpPenalty (src/aln.h:275-287); codonk1 = LARGEN unless Noll == 3 (src/aln2.cc:114)
-int k1_of(const SpdpScoring& sc) { return sc.noll == 3 ? sc.codonk1 : LARGEN; }
-int gap_penalty(const SpdpScoring& sc, int i) { return !i ? 0 : (i > k1_of(sc) ? sc.lgop + i * sc.lgep : sc.gop + i * sc.gep); }
-int gap_ext_pen(const SpdpScoring& sc, int i) { return i > k1_of(sc) ? sc.lgep : sc.gep; }
-int unp_penalty(const SpdpScoring& sc, int d)
-{
-    const int unp = d * sc.gep;
-    return d <= k1_of(sc) ? unp : unp + (sc.lgep - sc.gep) * (d - k1_of(sc));
-}
-int sim(const SpdpScoring& sc, int x, int y) { return (x && y) ? sc.mtx[x * sc.mtx_dim + y] : 0; }
 
 // null: the bundle can be served; otherwise what is wrong with it
 const char* refused(const SpdpScoring* sc, const SpdpUnsplicedParams* up)
@@ -53,35 +45,12 @@ const char* bad_problem(const SpdpScoring& sc, const SpdpProblem& p)
     return nullptr;
 }
 
-int64_t tile_stride(const SpdpProblem& p, const SpdpWindow& w)
+void device_scoring(const SpdpScoring& sc, DevScoringB& hs)
 {
-    const int64_t cols = p.b_right - p.b_left;
-    const int64_t span = std::min<int64_t>(cols, (int64_t) w.up - w.lw + SPDP_B_TILE) + SPDP_B_TILE - 1;
-    return (span + 3) & ~(int64_t) 3;
-}
-int64_t trace_bytes(const SpdpProblem& p, const SpdpWindow& w)
-{
-    const int64_t rows = p.a_right - p.a_left;
-    return (rows + SPDP_B_TILE - 1) / SPDP_B_TILE * tile_stride(p, w) * SPDP_B_TILE;
-}
-
-DevEdgeB edge(const SpdpScoring& sc, float f) { return {(int) (gap_penalty(sc, 1) * f), (int) (sc.gep * f), (int) (sc.lgep * f)}; }
-
-// Aln2b1::diagonalB_ng (src/fwd2b1.cc:1070-1102)
-int diagonal_b(const SpdpScoring& sc, const SpdpProblem& p, std::vector<SpdpSkl>& rec)
-{
-    const bool LocalL = sc.local && p.a_exgl && p.b_exgl, LocalR = sc.local && p.a_exgr && p.b_exgr;
-    int best = SPDP_NEVSEL, mL = p.a_left, mR = p.a_right, s = 0;
-    const int d = p.b_left - p.a_left;
-    for (int i = p.a_left; i < p.a_right; ) {
-        s += sim(sc, p.a[i], p.b[i + d]);
-        ++i;
-        if (LocalL && s < 0) { s = 0; mL = i; }
-        if (LocalR && s > best) { best = s; mR = i; }
-    }
-    rec.push_back({mL, mL + d});
-    rec.push_back({mR, mR + d});
-    return LocalR ? best : s;
+    memset(&hs, 0, sizeof hs);
+    hs.mtx_dim = sc.mtx_dim; hs.noll = sc.noll; hs.gop = sc.gop; hs.gep = sc.gep; hs.lgop = sc.lgop; hs.lgep = sc.lgep;
+    hs.k1 = k1_of(sc); hs.local = sc.local ? 1 : 0;
+    for (int x = 1; x < sc.mtx_dim; ++x) for (int y = 1; y < sc.mtx_dim; ++y) hs.mtx[x * 32 + y] = sc.mtx[x * sc.mtx_dim + y];
 }
 
 struct Item { int idx; SpdpWindow w; int64_t cells, tbytes; };
@@ -102,31 +71,21 @@ int run_chunk(SpdpContext* ctx, const SpdpScoring& sc, const SpdpUnsplicedParams
         const int rows = p.a_right - p.a_left, cols = p.b_right - p.b_left;
         d.row_off = n_row; n_row += 3 * (int64_t) (cols + 1);
         d.col_off = n_col; n_col += rows + 1;
-        d.a_left = p.a_left; d.a_right = p.a_right; d.b_left = p.b_left; d.b_right = p.b_right;
-        d.a_len = p.a_len; d.b_len = p.b_len;
-        d.lw = items[j].w.lw; d.up = items[j].w.up;
-        d.flags = (p.a_exgl ? 1 : 0) | (p.a_exgr ? 2 : 0) | (p.b_exgl ? 4 : 0) | (p.b_exgr ? 8 : 0);
+        forward_terms(sc, up.tgapf, p, items[j].w, d);
         if (score) {
             d.top = edge(sc, p.a_exgl ? 0.f : 1.f);          // (a global left end of a: the kernel runs sinitB_ng's row itself)
             d.left = edge(sc, p.b_exgl ? 0.f : 1.f);
             d.end_mode = (p.b_exgr ? 1 : 0) | (p.a_exgr ? 2 : 0);
+            d.endb = d.enda = DevEdgeB{0, 0, 0};
         } else {
             d.trace_off = n_trace; n_trace += items[j].tbytes;
             d.tstride = (int) tile_stride(p, items[j].w);
             d.rec_cap = (rows + cols) / 2 + 8;
             d.rec_off = n_rec; n_rec += d.rec_cap;
-            d.top = edge(sc, p.a_left ? 1.f : (p.a_exgl ? 0.f : up.tgapf));
-            d.left = edge(sc, p.b_left ? 1.f : (p.b_exgl ? 0.f : up.tgapf));
-            const float fb = p.b_exgr ? 0.f : up.tgapf, fa = p.a_exgr ? 0.f : up.tgapf;
-            d.endb = edge(sc, fb); d.enda = edge(sc, fa);
-            d.end_mode = ((p.b_right == p.b_len && fb < 1) ? 1 : 0) | ((p.a_right == p.a_len && fa < 1) ? 2 : 0);
         }
     }
     DevScoringB hs;
-    memset(&hs, 0, sizeof hs);
-    hs.mtx_dim = sc.mtx_dim; hs.noll = sc.noll; hs.gop = sc.gop; hs.gep = sc.gep; hs.lgop = sc.lgop; hs.lgep = sc.lgep;
-    hs.k1 = k1_of(sc); hs.local = sc.local ? 1 : 0;
-    for (int x = 1; x < sc.mtx_dim; ++x) for (int y = 1; y < sc.mtx_dim; ++y) hs.mtx[x * 32 + y] = sc.mtx[x * sc.mtx_dim + y];
+    device_scoring(sc, hs);
 
     auto* d_sc = (DevScoringB*) pool.get(BP_SC, sizeof hs);
     auto* d_probs = (DevProblemB*) pool.get(BP_PROBS, sizeof(DevProblemB) * n);
@@ -189,6 +148,132 @@ int run_items(SpdpContext* ctx, const SpdpScoring& sc, const SpdpUnsplicedParams
 
 }   // namespace
 
+const char* spdp_b_refused(const SpdpScoring* sc, const SpdpUnsplicedParams* up) { return refused(sc, up); }
+const char* spdp_b_bad_problem(const SpdpScoring* sc, const SpdpProblem* p) { return bad_problem(*sc, *p); }
+
+// ---- requests on resident inputs (spdp_internal.h)
+int spdp_b_resident_open(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n, SpdpBResident* res)
+{
+    res->a_off.assign(n, 0); res->b_off.assign(n, 0);
+    int64_t n_codes = 0;
+    for (int i = 0; i < n; ++i) { res->a_off[i] = n_codes; n_codes += probs[i].a_len; res->b_off[i] = n_codes; n_codes += probs[i].b_len; }
+    std::vector<uint8_t> codes((size_t) n_codes);
+    for (int i = 0; i < n; ++i) {
+        memcpy(codes.data() + res->a_off[i], probs[i].a, (size_t) probs[i].a_len);
+        memcpy(codes.data() + res->b_off[i], probs[i].b, (size_t) probs[i].b_len);
+    }
+    DevScoringB hs;
+    device_scoring(*sc, hs);
+    (void) hipSetDevice(ctx->device);
+    DevPool& pool = ctx->pool[B_POOL];
+    auto* d_sc = (DevScoringB*) pool.get(BP_SC, sizeof hs);
+    auto* d_codes = (uint8_t*) pool.get(BP_RESIDENT, (size_t) n_codes + 4);
+    if (!d_sc || !d_codes) { ctx->err = "unspliced aligner: out of device memory"; return -1; }
+    HIPCHK(hipMemcpyAsync(d_sc, &hs, sizeof hs, hipMemcpyHostToDevice, ctx->stream));
+    if (n_codes) HIPCHK(hipMemcpyAsync(d_codes, codes.data(), (size_t) n_codes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+namespace {
+
+struct RoundItem { SpdpBRequest* r; bool thin; int64_t cells, tbytes; int steps; };
+
+// one launch set: items[0 .. n_wide) tiled, the rest thin
+int run_round(SpdpContext* ctx, const SpdpScoring& sc, const SpdpUnsplicedParams& up, const SpdpBResident& rs, const RoundItem* items, int n_wide, int n_thin)
+{
+    const int n = n_wide + n_thin;
+    DevPool& pool = ctx->pool[B_POOL];
+    std::vector<DevProblemB> dp(n);
+    int64_t n_row = 0, n_col = 0, n_trace = 0, n_rec = 0;
+    for (int j = 0; j < n; ++j) {
+        const SpdpBRequest& q = *items[j].r;
+        const SpdpProblem& p = q.p;
+        DevProblemB& d = dp[j];
+        memset(&d, 0, sizeof d);
+        d.a_off = rs.a_off[q.parent]; d.b_off = rs.b_off[q.parent];
+        const int rows = p.a_right - p.a_left, cols = p.b_right - p.b_left;
+        d.row_off = n_row; n_row += (items[j].thin ? 1 : 3) * (int64_t) (cols + 1);
+        d.col_off = n_col; n_col += rows + 1;
+        forward_terms(sc, up.tgapf, p, q.w, d);
+        d.thin = items[j].thin ? 1 : 0;
+        d.trace_off = n_trace; n_trace += items[j].tbytes;
+        d.tstride = items[j].thin ? 0 : (int) tile_stride(p, q.w);
+        d.rec_cap = (rows + cols) / 2 + 8;
+        d.rec_off = n_rec; n_rec += d.rec_cap;
+    }
+    auto* d_sc = (DevScoringB*) pool.get(BP_SC, sizeof(DevScoringB));
+    auto* d_codes = (uint8_t*) pool.ptr[BP_RESIDENT];
+    auto* d_probs = (DevProblemB*) pool.get(BP_PROBS, sizeof(DevProblemB) * n);
+    auto* d_rowp = (int32_t*) pool.get(BP_ROWP, sizeof(int32_t) * n_row);
+    auto* d_lastc = (int32_t*) pool.get(BP_LASTC, sizeof(int32_t) * n_col);
+    auto* d_trace = (uint8_t*) pool.get(BP_TRACE, (size_t) n_trace + 4);
+    auto* d_recs = (int2*) pool.get(BP_RECS, sizeof(int2) * n_rec);
+    auto* d_res = (DevResultB*) pool.get(BP_RES, sizeof(DevResultB) * n);
+    if (!d_sc || !d_codes || !d_probs || !d_rowp || !d_lastc || !d_trace || !d_recs || !d_res) { ctx->err = "unspliced aligner: out of device memory"; return -1; }
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(d_probs, dp.data(), sizeof(DevProblemB) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(spdp_b_launch_round(s, sc.noll == 3, n_wide, n_thin, d_sc, d_probs, d_codes, d_rowp, d_lastc, d_trace, d_recs, d_res));
+    std::vector<DevResultB> res(n);
+    std::vector<int2> hrec((size_t) n_rec);
+    HIPCHK(hipMemcpyAsync(res.data(), d_res, sizeof(DevResultB) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hrec.data(), d_recs, sizeof(int2) * n_rec, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int j = 0; j < n; ++j) {
+        SpdpBRequest& q = *items[j].r;
+        q.score = res[j].score;
+        if (res[j].n_rec > dp[j].rec_cap) { ctx->err = "unspliced aligner: record list of a request exceeds its bound"; return -1; }
+        q.rec.resize(res[j].n_rec);
+        for (int k = 0; k < res[j].n_rec; ++k) { q.rec[k].m = hrec[dp[j].rec_off + k].x; q.rec[k].n = hrec[dp[j].rec_off + k].y; }
+        close_records(sc, q.p, q.rec);
+    }
+    return 0;
+}
+
+}   // namespace
+
+int spdp_b_run_requests(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpBResident* rs,
+                        SpdpBRequest* const* reqs, int n, int64_t* stats)
+{
+    const int64_t budget = up->max_trace_bytes ? up->max_trace_bytes : DEFAULT_TRACE_BYTES;
+    const bool thin_on = spdp_knob_on("SPDP_B_THIN");
+    std::vector<RoundItem> items;
+    for (int i = 0; i < n; ++i) {
+        SpdpBRequest& q = *reqs[i];
+        q.status = 0; q.rec.clear(); q.score = SPDP_NEVSEL;
+        if (lsp_without_cells(*sc, q.p, q.w, q.score, q.rec)) { ++stats[3]; continue; }
+        const int rows = q.p.a_right - q.p.a_left;
+        RoundItem it = {&q, thin_on && rows <= 16, spdp_cells_b(&q.p, &q.w), 0, 0};
+        DevProblemB d;
+        memset(&d, 0, sizeof d);
+        forward_terms(*sc, up->tgapf, q.p, q.w, d);
+        const ThinGeoB g = thin_geo_b(d);
+        it.steps = g.steps;
+        it.tbytes = it.thin ? thin_trace_bytes_b(d) : trace_bytes(q.p, q.w);
+        stats[6] += it.cells;
+        if (rows <= 16) { ++stats[4]; stats[5] += it.cells; }
+        if (it.tbytes > budget) { q.status = 1; ++stats[7]; continue; }
+        ++stats[it.thin ? 1 : 2];
+        items.push_back(it);
+    }
+    // tiled requests longest first, then the thin ones by step count, so that the four of a wave are alike
+    std::stable_sort(items.begin(), items.end(), [](const RoundItem& x, const RoundItem& y) {
+        if (x.thin != y.thin) return !x.thin;
+        return x.thin ? x.steps > y.steps : x.cells > y.cells; });
+    (void) hipSetDevice(ctx->device);
+    for (size_t at = 0; at < items.size(); ) {
+        size_t end = at;
+        int64_t used = 0;
+        while (end < items.size() && (end == at || used + items[end].tbytes <= budget) && end - at < (size_t) 1 << 20) used += items[end++].tbytes;
+        int n_wide = 0;
+        for (size_t j = at; j < end; ++j) n_wide += !items[j].thin;
+        if (run_round(ctx, *sc, *up, *rs, items.data() + at, n_wide, (int) (end - at) - n_wide)) return -1;
+        ++stats[0];
+        at = end;
+    }
+    return 0;
+}
+
 extern "C" int64_t spdp_cells_b(const SpdpProblem* p, const SpdpWindow* w)
 {
     if (!p || !w) return 0;
@@ -226,20 +311,10 @@ extern "C" int spdp_align_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpU
         const SpdpProblem& p = probs[i];
         SpdpWindow w;
         spdp_stripe(&p, sc->sh, &w);
-        const int rows = p.a_right - p.a_left, cols = p.b_right - p.b_left;
-        if (!rows && !cols) scores[i] = 0;
-        else if (!rows || !cols) {
-            recs[i] = {{p.a_left, p.b_left}, {p.a_right, p.b_right}};
-            // (lspB_ng keeps b's left flag under the name of a's, src/fwd2b1.cc:1250)
-            if (rows) scores[i] = (p.b_exgl || p.a_exgr) ? gap_ext_pen(*sc, rows) : gap_penalty(*sc, rows);
-            else scores[i] = (p.b_exgl || p.b_exgr) ? gap_ext_pen(*sc, cols) : unp_penalty(*sc, cols);
-        } else if (w.up == w.lw) scores[i] = diagonal_b(*sc, p, recs[i]);
-        else if (w.width < 0) scores[i] = SPDP_NEVSEL;
-        else {
-            Item it = {i, w, spdp_cells_b(&p, &w), trace_bytes(p, w)};
-            if (it.tbytes > budget) { ++not_computed; continue; }
-            items.push_back(it);
-        }
+        if (lsp_without_cells(*sc, p, w, scores[i], recs[i])) continue;
+        Item it = {i, w, spdp_cells_b(&p, &w), trace_bytes(p, w)};
+        if (it.tbytes > budget) { ++not_computed; continue; }
+        items.push_back(it);
     }
     std::vector<bool> on_device(n, false);
     for (const Item& it : items) on_device[it.idx] = true;
@@ -248,7 +323,7 @@ extern "C" int spdp_align_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpU
         const SpdpProblem& p = probs[i];
         std::vector<SpdpSkl>& r = recs[i];
         out[i].score = scores[i];
-        if (on_device[i] && !sc->local && !r.empty() && (r.back().m != p.a_left || r.back().n != p.b_left)) r.push_back({p.a_left, p.b_left});
+        if (on_device[i]) close_records(*sc, p, r);
         if (r.empty() || scores[i] <= SPDP_NEVSEL) continue;
         const std::vector<SpdpSkl> c = corner_list<1>(r);
         out[i].skl = (SpdpSkl*) malloc(sizeof(SpdpSkl) * (c.size() + 1));

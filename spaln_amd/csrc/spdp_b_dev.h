@@ -10,6 +10,14 @@
 //   trace   uint8   forward only: one code per cell, tile after tile with a fixed stride of tstride steps; within a tile
 //                   the codes of four consecutive steps of a lane share a dword: byte ((t >> 2) * 64 + lane) * 4 + (t & 3)
 //   recs    int2    forward only: the path records in Vmf::traceback's order (end -> start), rec_cap per problem
+//
+// The thin form (spdp_b_sweep_thin, requests of 1 .. 16 rows: what the seeded walk mostly asks for): four requests per wave, one
+// per 16-lane DPP row; lane k of a row owns DP row a_left + 1 + k, the request is a single tile, the row above lane 0 is the
+// closed-form top boundary.  Per request:
+//   rowp    int32   ONE plane of (cols + 1) entries: H of the DP's last row (what lastB_ng reads)
+//   lastc   int32   as above
+//   trace   uint8   16 x steps4 bytes: the codes of four consecutive steps of a lane share a dword, byte
+//                   ((t >> 2) * 16 + k) * 4 + (t & 3) -- a row of lanes stores 64 contiguous bytes every fourth step
 #ifndef SPDP_B_DEV_H_
 #define SPDP_B_DEV_H_
 
@@ -51,7 +59,7 @@ struct DevProblemB {
     DevEdgeB top, left;            // boundary row / column (initB_ng with tgapf folded in; sinitB_ng in score mode)
     DevEdgeB endb, enda;           // lastB_ng: (int)(GapPenalty(1) * f), (int)(BasicGEP * f), (int)(LongGEP * f) for b's / a's right end
     int32_t end_mode;              // bit0: the last-column pass runs, bit1: the last-row pass runs (forward); score mode: b_exgr, a_exgr
-    int32_t pad;
+    int32_t thin;                  // 1: a request of at most 16 rows in the thin layout (spdp_b_sweep_thin); 0: the tiled layout
 };
 
 struct DevResultB {

@@ -187,6 +187,86 @@ __global__ __launch_bounds__(64) void spdp_b_sweep(const DevScoringB* __restrict
     }
 }
 
+// The thin form: requests of 1 .. 16 rows, four per wave, one per 16-lane DPP row (layout: spdp_b_dev.h).  Lane k of a row
+// owns DP row a_left + 1 + k of its request; the request is one tile, so the row above lane 0 is the closed-form top
+// boundary and only the last row and the last column go to memory.  H, F, F2 of the row above come from lane k - 1 by
+// row_shr1, which keeps `old` -- the boundary -- for lane 0 of every row.  The four rows of lanes stand at different columns:
+// each loads the residues of its next 16 columns every 16th step and lane 0 picks its column's from them by a row-local
+// permute (one ds_bpermute per step, no LDS traffic); the residue then travels down the lanes with the same shift.  The
+// wave runs to the longest of its four requests (the host groups requests of like step counts); a lane past its own last
+// step has no cell and stores nothing.  The cell itself is thin_step_b (spdp_b_walk.h), shared with the CPU checker.
+template <bool DAGP>
+__global__ __launch_bounds__(64) void spdp_b_sweep_thin(const DevScoringB* __restrict__ scp, const DevProblemB* __restrict__ probs, int n_probs,
+                                                         const uint8_t* __restrict__ codes, int32_t* __restrict__ rowp,
+                                                         int32_t* __restrict__ lastc, uint8_t* __restrict__ trace,
+                                                         DevResultB* __restrict__ res)
+{
+    __shared__ int mtx[32 * 32];
+    const int lane = lane_id();
+    for (int i = lane; i < 32 * 32; i += 64) mtx[i] = scp->mtx[i];
+    __syncthreads();
+    const int k = lane & 15, row0 = lane & 48;
+    const int idx = blockIdx.x * 4 + (lane >> 4);
+    const bool active = idx < n_probs;
+    const DevProblemB p = probs[active ? idx : n_probs - 1];
+    const GapsB gp = {scp->gop, scp->gep, scp->lgop, scp->lgep};
+    const int k1 = scp->k1;
+    const bool local = scp->local != 0;
+    const bool local_l = local && (p.flags & 1) && (p.flags & 4), local_r = local && (p.flags & 2) && (p.flags & 8);
+    ThinGeoB g = thin_geo_b(p);
+    if (!active) { g.rows = 0; g.steps = g.steps4 = 0; }
+    int32_t* rowH = rowp + p.row_off;
+    int32_t* lastcol = lastc + p.col_off;
+    const uint8_t* as = codes + p.a_off;
+    const uint8_t* bs = codes + p.b_off;
+    unsigned* tr = reinterpret_cast<unsigned*>(trace + p.trace_off);
+    if (active && k == 0) lastcol[0] = thin_top_b(p, g, k1, p.b_right);
+
+    int longest = g.steps4;                                   // of the wave's four requests
+    longest = max(longest, __shfl_xor(longest, 16));
+    longest = max(longest, __shfl_xor(longest, 32));
+    longest = __builtin_amdgcn_readfirstlane(longest);
+
+    const int x = k < g.rows ? as[g.m0 + k - 1] : 0;
+    ThinLaneB L;
+    thin_lane_init_b(p, g, k1, k, L);
+    int y = 0, blkY = 0;
+    unsigned pack = 0;
+    for (int t = 0; t < longest; ++t) {
+        if ((t & 15) == 0) {                                  // this row of lanes: the residues of its next 16 columns
+            const int c = g.nlo + t + k;
+            blkY = (t < g.steps && c <= p.b_right) ? bs[c - 1] : 0;
+        }
+        const int n0 = g.nlo + t;                             // lane 0's column
+        const int inH = (k == 0 && t < g.steps) ? thin_top_b(p, g, k1, n0) : BLACK;
+        const int inY = __shfl(blkY, row0 | (t & 15));
+        const int up_h = row_shr1(inH, L.H), up_f = row_shr1(BLACK, L.F);
+        const int up_f2 = DAGP ? row_shr1(BLACK, L.F2) : BLACK;
+        y = row_shr1(inY, y);
+        int code = 0;
+        if (t < g.steps) code = thin_step_b<DAGP>(p, g, gp, k1, local_l, local_r, mtx, k, t, x, y, up_h, up_f, up_f2, L, rowH, lastcol);
+        pack |= (unsigned) code << (8 * (t & 3));
+        if ((t & 3) == 3) {
+            if (t < g.steps4) tr[(t >> 2) * 16 + k] = pack;
+            pack = 0;
+        }
+    }
+
+    // the running maximum of the local form within the row of lanes: highest score, then the first cell in row-major order
+    // (every lane takes part: the four requests of a wave need not agree on LocalR)
+#pragma unroll
+    for (int d = 8; d; d >>= 1) {
+        const int ov = __shfl_xor(L.best, d), om = __shfl_xor(L.best_m, d), on_ = __shfl_xor(L.best_n, d);
+        const bool take = ov > L.best || (ov == L.best && (om < L.best_m || (om == L.best_m && on_ < L.best_n)));
+        if (take) { L.best = ov; L.best_m = om; L.best_n = on_; }
+    }
+    if (active && k == 0) {
+        DevResultB r;
+        r.score = L.best; r.best_m = L.best_m; r.best_n = L.best_n; r.n_rec = 0;
+        res[idx] = r;
+    }
+}
+
 // lastB_ng / slastB_ng and the record list, one problem per thread
 template <bool SCORE>
 __global__ __launch_bounds__(64) void spdp_b_finish(const DevScoringB* __restrict__ scp, const DevProblemB* __restrict__ probs, int n,
@@ -227,5 +307,26 @@ hipError_t spdp_b_launch(hipStream_t s, bool score, bool dagp, int n, const DevS
         else hipLaunchKernelGGL((spdp_b_sweep<false, false>), g, b, 0, s, sc, probs, codes, rowp, lastc, trace, res);
         hipLaunchKernelGGL((spdp_b_finish<false>), dim3((n + 63) / 64), b, 0, s, sc, probs, n, rowp, lastc, trace, recs, res);
     }
+    return hipGetLastError();
+}
+
+// one round of forward requests on resident codes: probs[0 .. n_wide) through the tiled sweep, probs[n_wide .. n_wide + n_thin)
+// through the thin one (four per wave, in the order given), then the record walk over all of them
+hipError_t spdp_b_launch_round(hipStream_t s, bool dagp, int n_wide, int n_thin, const DevScoringB* sc, const DevProblemB* probs,
+                               const uint8_t* codes, int32_t* rowp, int32_t* lastc, uint8_t* trace, int2* recs, DevResultB* res)
+{
+    const int n = n_wide + n_thin;
+    if (n <= 0) return hipSuccess;
+    const dim3 b(64);
+    if (n_wide > 0) {
+        if (dagp) hipLaunchKernelGGL((spdp_b_sweep<false, true>), dim3(n_wide), b, 0, s, sc, probs, codes, rowp, lastc, trace, res);
+        else hipLaunchKernelGGL((spdp_b_sweep<false, false>), dim3(n_wide), b, 0, s, sc, probs, codes, rowp, lastc, trace, res);
+    }
+    if (n_thin > 0) {
+        const dim3 g((n_thin + 3) / 4);
+        if (dagp) hipLaunchKernelGGL((spdp_b_sweep_thin<true>), g, b, 0, s, sc, probs + n_wide, n_thin, codes, rowp, lastc, trace, res + n_wide);
+        else hipLaunchKernelGGL((spdp_b_sweep_thin<false>), g, b, 0, s, sc, probs + n_wide, n_thin, codes, rowp, lastc, trace, res + n_wide);
+    }
+    hipLaunchKernelGGL((spdp_b_finish<false>), dim3((n + 63) / 64), b, 0, s, sc, probs, n, rowp, lastc, trace, recs, res);
     return hipGetLastError();
 }

@@ -39,6 +39,14 @@ SPDP_B_HD int edge_step_b(const DevEdgeB& e, bool first, int i, int k1) { return
 // byte of cell (m, n) in the problem's trace
 SPDP_B_HD int64_t trace_index_b(const DevProblemB& p, int m, int n)
 {
+    if (p.thin) {                                 // one tile of at most 16 rows, 16 lanes wide
+        const int k = m - p.a_left - 1;
+        int nlo = p.a_left + p.lw;
+        if (nlo < p.b_left) nlo = p.b_left;
+        ++nlo;
+        const int t = n - nlo + k;
+        return ((int64_t) (t >> 2) * 16 + k) * 4 + (t & 3);
+    }
     const int row = m - p.a_left - 1, tile = row >> 6, k = row & 63;
     const int m0 = p.a_left + 1 + (tile << 6);
     int nlo = m0 - 1 + p.lw;
@@ -190,6 +198,119 @@ SPDP_B_HD int finish_score_b(const ViewB& v, int local, int best)
         for (int r = rw; r < r9; ++r) { int hv; edge_cell_b(v, p.a_right, p.a_right + r, false, &hv, &d); if (hv > mx) mx = hv; }
     }
     return mx;
+}
+
+// ---- the cell of forwardB_ng and the thin form of the sweep -------------------------------------------------------------------
+// One cell: H, F, F2 of the row above, the left neighbour's H, this row's running e1 / e2.  Ties as the reference has them: `>=`
+// for a gap state opening and for the horizontal states against H, `>` for the vertical ones, order h, f, f2, e1, e2.  Returns
+// the trace code; gain: the cell's score where it may be a local maximum (it gains over its diagonal predecessor and does
+// not start a path of its own), else BLACK.
+struct GapsB { int gop, gep, lgop, lgep; };
+template <bool DAGP>
+SPDP_B_HD int cell_forward_b(const GapsB& g, bool local_l, int diag, int sub, int up_h, int up_f, int up_f2, int left,
+                             int& H, int& F, int& F2, int& e1, int& e2, int& gain)
+{
+    int code = 0;
+    const int hv = diag + sub;
+    int win = SPDP_B_FROM_DIAG, mx = hv;
+    int v = up_h + g.gop;
+    const bool fo = v >= up_f;
+    F = (fo ? v : up_f) + g.gep;
+    if (F > mx) { mx = F; win = SPDP_B_FROM_F; }
+    if (fo) code |= SPDP_B_F_OPEN;
+    if (DAGP) {
+        v = up_h + g.lgop;
+        const bool f2o = v >= up_f2;
+        F2 = (f2o ? v : up_f2) + g.lgep;
+        if (F2 > mx) { mx = F2; win = SPDP_B_FROM_F2; }
+        if (f2o) code |= SPDP_B_F2_OPEN;
+    }
+    v = left + g.gop;
+    const bool eo = v >= e1;
+    e1 = (eo ? v : e1) + g.gep;
+    if (e1 >= mx) { mx = e1; win = SPDP_B_FROM_E1; }
+    if (eo) code |= SPDP_B_E1_OPEN;
+    if (DAGP) {
+        v = left + g.lgop;
+        const bool e2o = v >= e2;
+        e2 = (e2o ? v : e2) + g.lgep;
+        if (e2 >= mx) { mx = e2; win = SPDP_B_FROM_E2; }
+        if (e2o) code |= SPDP_B_E2_OPEN;
+    }
+    code |= win;
+    gain = (win == SPDP_B_FROM_DIAG && hv > diag && !(local_l && diag == 0)) ? mx : SPDP_B_BLACK;
+    if (local_l && mx <= 0) { mx = 0; code |= SPDP_B_RESET; }
+    H = mx;
+    return code;
+}
+
+// a thin request's single tile: lane k owns row m0 + k and is at column nlo + t - k in step t
+struct ThinGeoB { int m0, rows, nlo, steps, steps4, top_hi; };
+SPDP_B_HD ThinGeoB thin_geo_b(const DevProblemB& p)
+{
+    ThinGeoB g;
+    g.m0 = p.a_left + 1;
+    g.rows = p.a_right - p.a_left;
+    int lo = g.m0 - 1 + p.lw;
+    if (lo < p.b_left) lo = p.b_left;
+    g.nlo = lo + 1;
+    int nhi = g.m0 + g.rows - 1 + p.up;
+    if (nhi > p.b_right) nhi = p.b_right;
+    g.steps = nhi < g.nlo ? 0 : (nhi - g.nlo + 1) + g.rows - 1;
+    g.steps4 = (g.steps + 3) & ~3;
+    g.top_hi = p.up - (p.b_left - p.a_left);
+    if (g.top_hi > p.b_right - p.b_left) g.top_hi = p.b_right - p.b_left;
+    return g;
+}
+SPDP_B_HD int64_t thin_trace_bytes_b(const DevProblemB& p) { return (int64_t) thin_geo_b(p).steps4 * 16; }
+// H of the top boundary row (initB_ng) at column n; columns the boundary does not reach, and those behind b_right, are black
+SPDP_B_HD int thin_top_b(const DevProblemB& p, const ThinGeoB& g, int k1, int n)
+{
+    const int i = n - p.b_left;
+    return (i >= 0 && i <= g.top_hi) ? edge_sum_b(p.top, i, k1) : SPDP_B_BLACK;
+}
+
+struct ThinLaneB {                                // what a lane carries from step to step
+    int H, F, F2, e1, e2;                         // its last cell
+    int up_h_prev;                                // H(m - 1, n - 1) of the coming step
+    int best, best_m, best_n;                     // LocalR: the running maximum
+};
+SPDP_B_HD void thin_lane_init_b(const DevProblemB& p, const ThinGeoB& g, int k1, int k, ThinLaneB& L)
+{
+    L.H = L.F = L.F2 = L.e1 = L.e2 = SPDP_B_BLACK;
+    L.up_h_prev = k == 0 ? thin_top_b(p, g, k1, g.nlo - 1) : SPDP_B_BLACK;
+    L.best = SPDP_B_BLACK; L.best_m = p.a_left; L.best_n = p.b_left;
+}
+// step t of lane k: up_h / up_f / up_f2 are what lane k - 1 held one step ago (lane 0: the top boundary, thin_top_b / black),
+// x / y the residues of row m and of column n; mtx has stride 32.  Returns the trace code (0 where the lane has no cell).
+template <bool DAGP>
+SPDP_B_HD int thin_step_b(const DevProblemB& p, const ThinGeoB& g, const GapsB& gp, int k1, bool local_l, bool local_r, const int* mtx,
+                          int k, int t, int x, int y, int up_h, int up_f, int up_f2, ThinLaneB& L, int32_t* rowH, int32_t* lastcol)
+{
+    const int m = g.m0 + k, n = g.nlo + t - k;
+    int rs = m - 1 + p.lw;
+    if (rs < p.b_left) rs = p.b_left;
+    ++rs;
+    int re = m + p.up;
+    if (re > p.b_right) re = p.b_right;
+    int code = 0;
+    if (k < g.rows && n >= rs && n <= re) {
+        int diag = L.up_h_prev;
+        if (n - 1 == p.b_left && m - 1 > p.a_left) diag = edge_sum_b(p.left, m - 1 - p.a_left, k1);
+        int left = L.H;
+        if (n == rs) {
+            L.e1 = L.e2 = SPDP_B_BLACK;
+            left = (n - 1 == p.b_left && p.b_left - m >= p.lw) ? edge_sum_b(p.left, m - p.a_left, k1) : SPDP_B_BLACK;
+        }
+        if (n - m + 1 > p.up) { up_h = SPDP_B_BLACK; up_f = SPDP_B_BLACK; up_f2 = SPDP_B_BLACK; }
+        int gain;
+        code = cell_forward_b<DAGP>(gp, local_l, diag, mtx[x * 32 + y], up_h, up_f, up_f2, left, L.H, L.F, L.F2, L.e1, L.e2, gain);
+        if (local_r && gain > L.best) { L.best = gain; L.best_m = m; L.best_n = n; }
+        if (n == p.b_right) lastcol[m - p.a_left] = L.H;
+        if (k == g.rows - 1) rowH[n - p.b_left] = L.H;
+    }
+    L.up_h_prev = up_h;
+    return code;
 }
 
 #endif

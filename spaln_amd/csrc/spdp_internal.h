@@ -342,6 +342,9 @@ struct TilePipe {
 // SpdpContext::pool: runs that may be in flight together never share one.  The first five: DevRun's (RUN_TRAITS below); H_POOL / HU_POOL: the
 // aa x genome path's inputs + traceback runs / linear-space runs; R_POOL: rescoring; SIDE_POOL: a DevRun on the side stream, of any flavour;
 // B_POOL: the unspliced aligner (spdp_b_api.cpp)
+// slots of pool[B_POOL]: a chunk of spdp_align_b / spdp_homscore_b or a round of spdp_align_b_seeded (never both at once on one
+// context), and the residues of a seeded call's pairs, resident for the whole call
+enum { BP_SC = 0, BP_PROBS, BP_CODES, BP_ROWP, BP_LASTC, BP_TRACE, BP_RECS, BP_RES, BP_RESIDENT };
 enum CtxPool { WIP_SCORE_POOL = 0, WIP_FORWARD_POOL, WIP_UDH_POOL, EXACT_FORWARD_POOL, EXACT_POOL, H_POOL, HU_POOL, R_POOL, SIDE_POOL, B_POOL, N_CTX_POOLS };
 struct SpdpContext {
     DevPool pool[N_CTX_POOLS];
@@ -355,6 +358,7 @@ struct SpdpContext {
     std::string err;
     std::vector<SpdpContext*> lanes;  // further lanes of this context (spdp_lane): chunks of a batch run side by side
     int64_t seed_stats[12] = {0};      // spdp_seeded_stats
+    int64_t seed_stats_b[16] = {0};    // spdp_seeded_stats_b
     // Seq::tlen of the problems of the seeded calls made while it is set (spdp_map_align_s_prep; problem i of spdp_align_s_seeded,
     // forward problems then reverse ones of _ori3): the walks' own HSP searches end their forward extension there.  Null: a_len
     const int32_t* seed_a_tlen = nullptr;
@@ -542,5 +546,28 @@ void trim_skl_of(std::vector<SpdpSkl>& s, const SpdpProblem& p);     // trimskl,
 int64_t spdp_cells_w(int a_left, int a_right, int b_left, int b_right, const SpdpWindow& w);
 // corner list of path records (spdp_host.cpp): M_UNIT = 1 nucleotide rows, 3 protein rows
 template <int M_UNIT> std::vector<SpdpSkl> corner_list(std::vector<SpdpSkl> pts);
+
+// ---- the unspliced aligner's requests on resident inputs (spdp_b_api.cpp; the seeded entry spdp_seeded_b.cpp asks) ----------
+// The residues of a call's pairs go to the device once (spdp_b_resident_open); a round of lspB_ng requests -- sub-ranges of those
+// pairs with their own end flags -- is then served in one go: the branches without a DP cell on the host, requests of at most
+// 16 rows by the thin sweep (unless SPDP_B_THIN=0), the others by the tiled sweep, in sub-rounds whose trace stores fit
+// max_trace_bytes.  A request above the budget comes back with status 1 ("not computed").
+struct SpdpBRequest {
+    int parent = 0;                 // the pair
+    SpdpProblem p{};                // the pair's sequences (host pointers) with the request's ranges and end flags
+    SpdpWindow w{};
+    int score = SPDP_NEVSEL;
+    int status = 0;                 // 0: served, 1: above max_trace_bytes
+    std::vector<SpdpSkl> rec;       // what lspB_ng wrote, in its order
+};
+struct SpdpBResident { std::vector<int64_t> a_off, b_off; };
+// [0] device launches (sub-rounds), [1] thin requests, [2] tiled requests, [3] served without a cell, [4] requests of at most 16
+// rows, [5] their cells, [6] cells of all device requests, [7] requests not computed
+enum { SPDP_BREQ_N_STATS = 8 };
+int spdp_b_resident_open(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n, SpdpBResident* res);
+int spdp_b_run_requests(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpBResident* res,
+                        SpdpBRequest* const* reqs, int n, int64_t* stats);
+const char* spdp_b_refused(const SpdpScoring* sc, const SpdpUnsplicedParams* up);
+const char* spdp_b_bad_problem(const SpdpScoring* sc, const SpdpProblem* p);
 
 #endif

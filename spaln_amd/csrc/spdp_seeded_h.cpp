@@ -338,7 +338,10 @@ extern "C" int spdp_wilip(const SpdpWilipModel* model, const SpdpProblem* p, con
              gc = {sc->intpen, sc->intpen_len, sc->gop, sc->gep, sc->lgop, sc->lgep, sc->codonk1}; }
     else { pr = {ph->a, ph->a_len, span[0], span[1], exg ? exg[0] : 0, exg ? exg[1] : 0, ph->b, ph->b_len, span[2], span[3], 3, ph->sigS, ph->sigE, ph->sigT};
            gc = {sch->intpen, sch->intpen_len, sch->gop, sch->gep, sch->lgop, sch->lgep, sch->codonk1}; }
-    if (!pr.a || !pr.b || !gc.intpen || gc.intpen_len <= 0) return -1;
+    // (the intron-length table prices links only where the genomic side may run ahead: a protein-pair model, lsg = 0, needs none;
+    // its gaps price as PwdB::GapPenalty does, codonk1 = LARGEN unless Noll == 3)
+    if (!pr.a || !pr.b || (model->lsg && (!gc.intpen || gc.intpen_len <= 0))) return -1;
+    if (p && model->dvsp == 3 && sc->noll != 3) gc.codonk1 = INT32_MAX / 4 * 3;
     if (pr.a_left < 0 || pr.a_right > pr.a_len || pr.a_left > pr.a_right || pr.b_left < 0 || pr.b_right > pr.b_len || pr.b_left > pr.b_right) return -1;
     std::vector<spdp_hsp::Unit> us;
     spdp_hsp::search(model, pr, gc, level, us);

@@ -122,6 +122,50 @@ def scoring_b(noll=2, local=0, sh=SH, **over) -> abi.Scoring:
     return abi.make_scoring(**kw)
 
 
+def _wilip_doc_b() -> dict:
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "b_aa_wilip.json")
+    with open(path) as f:
+        return json.load(f)
+
+
+def wilip_model_b() -> abi.WilipModel:
+    """the HSP-search model of protein pairs (DvsP = 3: the aaprm word parameters, getSimmtx(WlnPamNo) by amino-acid code,
+    EndBonus, crs / lsg / mlt) as the program sets it up for two protein files, recorded in tests/golden/b_aa_wilip.json"""
+    doc = _wilip_doc_b()
+    m = abi.WilipModel()
+    for i, lv in enumerate(doc["levels"]):
+        L = m.level[i]
+        for k in ("elem", "tpl", "mask", "width", "gain", "gain1", "thr", "xdrp", "cutoff", "vthr"):
+            setattr(L, k, int(lv[k]))
+        L.bitpat_len = len(lv["bitpat"])
+        for k, v in enumerate(lv["bitpat"]):
+            L.bitpat[k] = int(v)
+        for c in range(32):
+            L.convtab[c] = min(255, int(lv["convtab"][c])) if c < len(lv["convtab"]) else 127
+    m.mtx_rows, m.mtx_cols = int(doc["mtx_rows"]), int(doc["mtx_cols"])
+    for k, v in enumerate(np.asarray(doc["mtx"], dtype=np.int32).ravel()):
+        m.mtx[k] = int(v)
+    for k in ("dvsp", "end_bonus", "crs", "lsg", "mlt", "shortquery", "min_hit", "met", "ser", "ser2"):
+        setattr(m, k, int(doc[k]))
+    return m
+
+
+def seed_params_b(qck: int, lcl: int = 15) -> abi.SeedParams:
+    """SpdpSeedParams of spdp_align_b_seeded for `spaln -Q<qck> -L<lcl>` on protein pairs: what the entry reads (qck, the levels'
+    word widths, PwdB::Vthr, algmode.lcl); the model goes in with the call (Engine.align_b_seeded)"""
+    doc = _wilip_doc_b()
+    sp = abi.SeedParams()
+    sp.qck = int(qck)
+    for k in range(4):
+        sp.wl_width[k] = int(doc["wl_width"][k])
+    sp.vthr = int(doc["vthr"])
+    sp.lcl = int(lcl)
+    sp.crs = int(doc["crs"])
+    return sp
+
+
 # MakeBlk::prepacomp's per-class terms of the translated block index's word scores (src/blksrc.cc:844-877) for the reference's defaults
 # (twenty classes, -Xp20, -Xq1, its mdm tables) -- recorded from the compiled reference (`spaln_idxtap -W -KP`, oracle/ref_build/idx_tap.cc:
 # the "[idx_tap] acomp" line, exact hex floats); spdp_blk_index_build_p's acomp

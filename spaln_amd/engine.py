@@ -38,6 +38,7 @@ EXPORTS = [
     "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan", "spdp_ladder_plan", "spdp_ladder_postwork",
     "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
     "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
+    "spdp_align_b_seeded", "spdp_seeded_stats_b", "spdp_align_b_seeded_refusal",
 ]
 
 
@@ -67,6 +68,10 @@ def load_library() -> C.CDLL:
     lib.spdp_cells_b.restype = lib.spdp_trace_bytes_b.restype = C.c_int64
     lib.spdp_align_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
     lib.spdp_homscore_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+    lib.spdp_align_b_seeded.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
+    lib.spdp_seeded_stats_b.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.spdp_align_b_seeded_refusal.restype = C.c_char_p
+    lib.spdp_align_b_seeded_refusal.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int]
     lib.spdp_skl_rng_b.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.spdp_skl_edits_b.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.spdp_splice_signals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -718,6 +723,70 @@ class Engine:
             res.append((int(arr[i].score), skl))
         self.lib.spdp_free_alignments(arr, n)
         return res
+
+    def align_b_seeded(self, sc, up: abi.UnsplicedParams, sp: abi.SeedParams, ps, model=None, hsps=None, lowest_levels=None,
+                       allow_partial=False):
+        """alignB_ng with seeding on (-Q1 .. -Q3, spdp_align_b_seeded): result as align_b; a pair the program prints no record
+        for comes back with an empty skl.  model: an abi.WilipModel (defaults.wilip_model_b()), the library's own HSP search
+        at every level; hsps[i]: (n_i + 1, 5) int32 array (b->jxt with its free slot) or None, lowest_levels[i] = b->wllvl.
+        last_call_s = seconds spent in the library."""
+        import time
+        n = len(ps)
+        keep = []
+        jx = (C.c_void_p * n)()
+        nh = (C.c_int32 * n)()
+        lv = (C.c_int32 * n)(*[int(x) for x in (lowest_levels if lowest_levels is not None else [0] * n)])
+        for i, h in enumerate(hsps or []):
+            if h is None or len(h) < 2:
+                continue
+            a = np.ascontiguousarray(h, dtype=np.int32)
+            keep.append(a)
+            jx[i] = a.ctypes.data
+            nh[i] = a.shape[0] - 1
+        arr = (abi.Alignment * n)()
+        probs = ps.array()
+        sp.wilip = C.addressof(model) if model is not None else None
+        t0 = time.perf_counter()
+        rc = self.lib.spdp_align_b_seeded(self.ctx, C.byref(sc), C.byref(up), C.byref(sp), probs, n, jx, nh, lv, None, arr)
+        self.last_call_s = time.perf_counter() - t0
+        sp.wilip = None
+        if not (allow_partial and rc == 1):
+            self._check(rc, "spdp_align_b_seeded")
+        res = []
+        for i in range(n):
+            k = arr[i].n_skl
+            skl = np.ctypeslib.as_array(C.cast(arr[i].skl, C.POINTER(C.c_int32)), shape=(k, 2)).copy() if k else np.zeros((0, 2), dtype=np.int32)
+            res.append((int(arr[i].score), skl))
+        self.lib.spdp_free_alignments(arr, n)
+        return res
+
+    SEEDED_STATS_B = ("walks", "hsp_searches", "device_batches", "thin_requests", "wide_requests", "host_requests", "requests_le16_rows",
+                      "cells_le16_rows", "cells", "requests_not_computed", "us_walks", "us_device", "us_call")
+
+    def seeded_stats_b(self) -> dict:
+        """spdp_seeded_stats_b: the counters of the last align_b_seeded call on this engine"""
+        v = (C.c_int64 * len(self.SEEDED_STATS_B))()
+        self.lib.spdp_seeded_stats_b(self.ctx, v, len(self.SEEDED_STATS_B))
+        return dict(zip(self.SEEDED_STATS_B, (int(x) for x in v)))
+
+    def wilip_b(self, model: abi.WilipModel, p: abi.Problem, sc, level=0):
+        """spdp_wilip on a protein pair: the best unit's HSPs as an (n + 1, 5) int32 array (its closing slot last), or None"""
+        span = (C.c_int32 * 4)(p.a_left, p.a_right, p.b_left, p.b_right)
+        exg = (C.c_int32 * 2)(p.a_exgl, p.a_exgr)
+        flat = C.POINTER(C.c_int32)()
+        self.lib.spdp_wilip.restype = C.c_int
+        self.lib.spdp_wilip.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        k = self.lib.spdp_wilip(C.addressof(model), C.addressof(p), C.addressof(sc), None, None, int(level), span, exg, C.byref(flat))
+        if k < 1:
+            raise RuntimeError("spdp_wilip: refused")
+        v = np.array([int(flat[i]) for i in range(k)], dtype=np.int32)
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        libc.free(flat)                                      # (the record is malloc'ed: include/spdp.h)
+        if v[0] < 1:
+            return None
+        num = int(v[1])
+        return v[7:7 + 5 * (num + 1)].reshape(num + 1, 5).copy()
 
     def homscore_b(self, sc, up: abi.UnsplicedParams, ps) -> np.ndarray:
         """HomScoreB_ng under -A0 (scorealoneB_ng)"""

@@ -2,8 +2,12 @@
 """Protein pairs end to end: what `spaln -Q0 -A0 -ip -pw` prints for two protein files against the library's unspliced
 aligner (spdp_align_b + spdp_skl_rng_b), corner for corner and statistic for statistic, both timed.
 
-    python tools/b_pairs.py --pairs 300 [--seed 1] [--threads 16] [--mean-len 350] [--yl3] [--lcl 15]
+    python tools/b_pairs.py --pairs 300 [--seed 1] [--threads 16] [--mean-len 350] [--yl3] [--lcl 15] [--qck 3] [--repeat 5]
                                                                        (an MI355X box; oracle/_ref/spaln for the comparison)
+
+--qck N (1 .. 3): the program with -QN (its seeded path; -Q3 is its default) against spdp_align_b_seeded; the line then also
+carries the call's counters (spdp_seeded_stats_b), the share of DP requests of at most 16 rows and of the cells in them, and the
+time of the full DP (spdp_align_b) on the same pairs.  SPDP_B_THIN=0 in the environment sends every request through the tiled kernel.
 
 The pairs are generated here: mutated copies with indels, copies with a deleted block, an embedded domain between unrelated
 flanks.  The program reads its FIRST file as b and its second as a; so does this tool.  Prints one JSON line.
@@ -142,16 +146,16 @@ def exg_of(lcl: int):
     return (1 if lcl & 4 else 0, 1 if lcl & 8 else 0, 1 if lcl & 1 else 0, 1 if lcl & 2 else 0)
 
 
-def library_records(eng, sc, up, pairs, lcl):
+def library_records(eng, sc, up, pairs, lcl, seeded=None):
     """the library's record per pair: (corners 1-based after trimskl, stat dict, engine score); (None, None, score) where
-    there is no alignment"""
+    there is no alignment.  seeded = (SeedParams, WilipModel): through spdp_align_b_seeded instead of spdp_align_b"""
     from spaln_amd import abi, synth
     ps = abi.ProblemSet()
     for a, b in pairs:
         ps.add(synth.encode_protein(np.frombuffer(a.encode(), dtype=np.uint8)), synth.encode_protein(np.frombuffer(b.encode(), dtype=np.uint8)),
                None, None, exg=exg_of(lcl))
-    alns = eng.align_b(sc, up, ps)
-    dt = eng.last_call_s                   # the spdp_align_b call alone: upload, kernels, download, corner lists
+    alns = eng.align_b_seeded(sc, up, seeded[0], ps, model=seeded[1]) if seeded else eng.align_b(sc, up, ps)
+    dt = eng.last_call_s                   # the call alone: upload, walks, kernels, download, corner lists
     stats = eng.skl_rng_b(sc, up, ps, [s for _, s in alns])
     out = []
     for (score, skl), st in zip(alns, stats):
@@ -188,6 +192,8 @@ def main() -> int:
     ap.add_argument("--lcl", type=int, default=15)
     ap.add_argument("--yl3", action="store_true")
     ap.add_argument("--no-reference", action="store_true", help="library only (a profiler run): nothing is compared")
+    ap.add_argument("--qck", type=int, default=0, help="1 .. 3: the reference with -Q<n> against the seeded entry (spdp_align_b_seeded); 0: -Q0")
+    ap.add_argument("--repeat", type=int, default=1, help="timed repetitions of the library call (after the warm-up call)")
     args = ap.parse_args()
     from spaln_amd import abi, defaults, engine
 
@@ -197,7 +203,7 @@ def main() -> int:
     for i in range(args.pairs):
         n = int(np.clip(rng.normal(args.mean_len, args.mean_len / 4), 30, 3 * args.mean_len))
         pairs.append(make_pair(rng, kinds[i % 3], n))
-    opts = [f"-L{args.lcl}"] + (["-yl3"] if args.yl3 else [])
+    opts = [f"-L{args.lcl}"] + (["-yl3"] if args.yl3 else []) + ([f"-Q{args.qck}"] if args.qck else [])     # (the later -Q wins)
     a_seqs, b_seqs = [p[0] for p in pairs], [p[1] for p in pairs]
     want1 = want0 = None
     ref_s = float("nan")
@@ -209,8 +215,25 @@ def main() -> int:
     eng = engine.Engine(0)
     sc = defaults.scoring_b(noll=3 if args.yl3 else 2, local=1 if args.lcl & 16 else 0)
     up = abi.UnsplicedParams(1.0, 0)
-    library_records(eng, sc, up, pairs[:min(len(pairs), 64)], args.lcl)          # first call: allocations, module load
-    got, lib_s, ps = library_records(eng, sc, up, pairs, args.lcl)
+    seeded = (defaults.seed_params_b(args.qck, args.lcl), defaults.wilip_model_b()) if args.qck else None
+    library_records(eng, sc, up, pairs[:min(len(pairs), 64)], args.lcl, seeded)          # first call: allocations, module load
+    got, lib_s, ps = library_records(eng, sc, up, pairs, args.lcl, seeded)
+    times = [lib_s]
+    for _ in range(args.repeat - 1):
+        got, lib_s, ps = library_records(eng, sc, up, pairs, args.lcl, seeded)
+        times.append(lib_s)
+    lib_s = float(np.median(times))
+    extra = {}
+    if seeded:
+        st = eng.seeded_stats_b()
+        dp = st["thin_requests"] + st["wide_requests"] + st["requests_not_computed"]
+        extra = {"seeded_stats": st, "share_requests_le16_rows": round(st["requests_le16_rows"] / max(dp, 1), 4),
+                 "share_cells_le16_rows": round(st["cells_le16_rows"] / max(st["cells"], 1), 4)}
+        eng.align_b(sc, up, ps)                                                    # (warm) the full DP on the same pairs
+        eng.align_b(sc, up, ps)
+        extra["library_full_dp_align_s"] = round(eng.last_call_s, 4)
+    if args.repeat > 1:
+        extra["library_align_s_all"] = [round(t, 4) for t in times]
     t0 = time.perf_counter()
     eng.homscore_b(sc, up, ps)
     score_s = time.perf_counter() - t0
@@ -218,13 +241,13 @@ def main() -> int:
     bad = [] if want1 is None else [i for i in range(len(pairs))
            if not same_record(got[i], want1[i][0] if want1[i] else None, want1[i][1] if want1[i] else 0.0, want0[i], defaults.B_SCALE)]
     print(json.dumps({
-        "what": "every record `spaln -Q0 -A0 -ip -pw %s` prints against spdp_align_b + spdp_skl_rng_b" % " ".join(opts),
+        "what": "every record `spaln -Q0 -A0 -ip -pw %s` prints against %s + spdp_skl_rng_b" % (" ".join(opts), "spdp_align_b_seeded" if seeded else "spdp_align_b"),
         "pairs": len(pairs), "identical": None if want1 is None else len(pairs) - len(bad), "first_differing": bad[:5], "cells": cells,
         "library_align_s": round(lib_s, 4), "library_pairs_per_s": round(len(pairs) / lib_s, 1), "library_gcups": round(cells / lib_s / 1e9, 3),
         "library_homscore_s": round(score_s, 4),
         "reference_threads": args.threads, "reference_s": None if want1 is None else round(ref_s, 4),
         "reference_pairs_per_s": None if want1 is None else round(len(pairs) / ref_s, 1),
-        "reference_gcups": None if want1 is None else round(cells / ref_s / 1e9, 3), "device": eng.device_name()}))
+        "reference_gcups": None if want1 is None else round(cells / ref_s / 1e9, 3), "device": eng.device_name(), **extra}))
     eng.close()
     return 0 if not bad else 1
 
