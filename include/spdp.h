@@ -1266,6 +1266,19 @@ int spdp_seeded_stats_b(const SpdpContext* ctx, int64_t* out, int n);
  * refusal (a static string).  hsps_for_all: every pair brings its HSPs; has_src: an SpdpHspSource answers.  Host code. */
 const char* spdp_align_b_seeded_refusal(const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp,
                                         int hsps_for_all, int has_src);
+/* lspB_ng as the seeded walk calls it, as an entry of its own (what spdp_lsp_s / spdp_lsp_h are to their ladders): every problem
+ * is ONE request on its own pair -- its ranges and exg* flags, the window stripe() gives for them -- and goes the way of a
+ * round of spdp_align_b_seeded: the residues uploaded once, the branches without a DP cell on the host, a request of at most
+ * 16 rows through the thin form of the sweep (SPDP_B_THIN=0: the tiled form), the others through the tiled form, in launch
+ * sets whose trace stores fit max_trace_bytes.  Refusals and out[i] exactly as spdp_align_b (header + corners; a request
+ * above max_trace_bytes: score SPDP_NEVSEL, n_skl 0, and the call returns 1): for every problem the two entries agree.
+ * SPDP_B_THIN_SORT=0 in the environment (here and in spdp_align_b_seeded): the thin requests of a launch set share their waves
+ * in the order given, not sorted by length; the results do not depend on it.
+ * stats (8 entries, may be NULL): [0] device launch sets, requests [1] served by the thin kernel, [2] by the tiled kernel,
+ * [3] on the host without a cell; [4] requests of at most 16 rows among those with DP cells (whichever form served them), [5] their DP cells,
+ * [6] DP cells of all device requests, [7] requests above max_trace_bytes. */
+int spdp_lsp_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
+               const SpdpProblem* probs, int n_probs, SpdpAlignment* out, int64_t* stats);
 
 #ifdef __cplusplus
 }

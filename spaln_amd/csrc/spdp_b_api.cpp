@@ -1,6 +1,7 @@
 // spdp_b_api.cpp -- the unspliced aligner's entries (include/spdp.h "unspliced alignment"): alignB_ng with seeding off
 // (globalB_ng -> the direct part of lspB_ng -> trcbkalignB_ng -> stdskl, src/fwd2b1.cc:1104-1148, 1245-1269, 1531-1560),
-// HomScoreB_ng under -A0 (scorealoneB_ng), and skl_rngB_ng with its edit records on the host.
+// HomScoreB_ng under -A0 (scorealoneB_ng), skl_rngB_ng with its edit records on the host, and the rounds of lspB_ng requests on
+// resident inputs that the seeded entry asks for (spdp_b_run_requests; spdp_lsp_b: one request per problem, for callers and tests).
 //   host:    stripe(), the empty ranges and the one-diagonal window of lspB_ng (no DP cell), the record fix-up, stdskl
 //   device:  everything else (spdp_b_forward.hip), in chunks whose traceback stores fit SpdpUnsplicedParams::max_trace_bytes,
 //            longest problems first
@@ -146,6 +147,20 @@ int run_items(SpdpContext* ctx, const SpdpScoring& sc, const SpdpUnsplicedParams
     return 0;
 }
 
+// globalB_ng's tail for one problem: the score, and header {1, corners} + stdskl of the closed records (none: no alignment)
+bool hand_over(int score, const std::vector<SpdpSkl>& r, SpdpAlignment& out)
+{
+    out.score = score;
+    if (r.empty() || score <= SPDP_NEVSEL) return true;
+    const std::vector<SpdpSkl> c = corner_list<1>(r);
+    out.skl = (SpdpSkl*) malloc(sizeof(SpdpSkl) * (c.size() + 1));
+    if (!out.skl) return false;
+    out.skl[0].m = 1; out.skl[0].n = (int) c.size();
+    std::copy(c.begin(), c.end(), out.skl + 1);
+    out.n_skl = (int) c.size() + 1;
+    return true;
+}
+
 }   // namespace
 
 const char* spdp_b_refused(const SpdpScoring* sc, const SpdpUnsplicedParams* up) { return refused(sc, up); }
@@ -237,6 +252,9 @@ int spdp_b_run_requests(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnspl
 {
     const int64_t budget = up->max_trace_bytes ? up->max_trace_bytes : DEFAULT_TRACE_BYTES;
     const bool thin_on = spdp_knob_on("SPDP_B_THIN");
+    // SPDP_B_THIN_SORT=0: the thin requests run in the order given, so that a caller (the tests) decides which four share a
+    // wave and in which slot the longest of them sits; the kernel does not depend on the order
+    const bool thin_sorted = spdp_knob_on("SPDP_B_THIN_SORT");
     std::vector<RoundItem> items;
     for (int i = 0; i < n; ++i) {
         SpdpBRequest& q = *reqs[i];
@@ -257,9 +275,9 @@ int spdp_b_run_requests(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnspl
         items.push_back(it);
     }
     // tiled requests longest first, then the thin ones by step count, so that the four of a wave are alike
-    std::stable_sort(items.begin(), items.end(), [](const RoundItem& x, const RoundItem& y) {
+    std::stable_sort(items.begin(), items.end(), [thin_sorted](const RoundItem& x, const RoundItem& y) {
         if (x.thin != y.thin) return !x.thin;
-        return x.thin ? x.steps > y.steps : x.cells > y.cells; });
+        return x.thin ? (thin_sorted && x.steps > y.steps) : x.cells > y.cells; });
     (void) hipSetDevice(ctx->device);
     for (size_t at = 0; at < items.size(); ) {
         size_t end = at;
@@ -322,17 +340,46 @@ extern "C" int spdp_align_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpU
     for (int i = 0; i < n; ++i) {
         const SpdpProblem& p = probs[i];
         std::vector<SpdpSkl>& r = recs[i];
-        out[i].score = scores[i];
         if (on_device[i]) close_records(*sc, p, r);
-        if (r.empty() || scores[i] <= SPDP_NEVSEL) continue;
-        const std::vector<SpdpSkl> c = corner_list<1>(r);
-        out[i].skl = (SpdpSkl*) malloc(sizeof(SpdpSkl) * (c.size() + 1));
-        if (!out[i].skl) { ctx->err = "spdp_align_b: out of memory"; return -1; }
-        out[i].skl[0].m = 1; out[i].skl[0].n = (int) c.size();
-        std::copy(c.begin(), c.end(), out[i].skl + 1);
-        out[i].n_skl = (int) c.size() + 1;
+        if (!hand_over(scores[i], r, out[i])) { ctx->err = "spdp_align_b: out of memory"; return -1; }
     }
     if (not_computed) ctx->err = "spdp_align_b: " + std::to_string(not_computed) + " problem(s) above max_trace_bytes were not computed";
+    return not_computed ? 1 : 0;
+}
+
+extern "C" int spdp_lsp_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpProblem* probs, int n,
+                          SpdpAlignment* out, int64_t* stats)
+{
+    if (!ctx) return -1;
+    if (stats) memset(stats, 0, sizeof(int64_t) * SPDP_BREQ_N_STATS);
+    if (const char* why = refused(sc, up)) { ctx->err = std::string("spdp_lsp_b: ") + why; return -1; }
+    if (n <= 0) return 0;
+    if (!probs || !out) { ctx->err = "spdp_lsp_b: null argument"; return -1; }
+    for (int i = 0; i < n; ++i) {
+        out[i].score = SPDP_NEVSEL; out[i].n_skl = 0; out[i].skl = nullptr; out[i].flags = 0; out[i].reserved = 0;
+        if (const char* why = bad_problem(*sc, probs[i])) { ctx->err = "spdp_lsp_b: problem " + std::to_string(i) + ": " + why; return -1; }
+    }
+    SpdpBResident resident;
+    if (spdp_b_resident_open(ctx, sc, probs, n, &resident)) return -1;
+    std::vector<SpdpBRequest> rq(n);
+    std::vector<SpdpBRequest*> ptr(n);
+    for (int i = 0; i < n; ++i) {
+        rq[i].parent = i;
+        rq[i].p = probs[i];
+        // the walk's window of a request is ladder::stripe<1> on the request's ranges (spdp_b_seeded_walk.h); spdp_stripe is
+        // that very function on the problem's ranges (spdp_api.cpp)
+        spdp_stripe(&probs[i], sc->sh, &rq[i].w);
+        ptr[i] = &rq[i];
+    }
+    int64_t st[SPDP_BREQ_N_STATS] = {0};
+    if (spdp_b_run_requests(ctx, sc, up, &resident, ptr.data(), n, st)) return -1;
+    if (stats) memcpy(stats, st, sizeof st);
+    int not_computed = 0;
+    for (int i = 0; i < n; ++i) {
+        if (rq[i].status) { ++not_computed; continue; }
+        if (!hand_over(rq[i].score, rq[i].rec, out[i])) { ctx->err = "spdp_lsp_b: out of memory"; return -1; }
+    }
+    if (not_computed) ctx->err = "spdp_lsp_b: " + std::to_string(not_computed) + " request(s) above max_trace_bytes were not computed";
     return not_computed ? 1 : 0;
 }
 

@@ -551,7 +551,8 @@ template <int M_UNIT> std::vector<SpdpSkl> corner_list(std::vector<SpdpSkl> pts)
 // The residues of a call's pairs go to the device once (spdp_b_resident_open); a round of lspB_ng requests -- sub-ranges of those
 // pairs with their own end flags -- is then served in one go: the branches without a DP cell on the host, requests of at most
 // 16 rows by the thin sweep (unless SPDP_B_THIN=0), the others by the tiled sweep, in sub-rounds whose trace stores fit
-// max_trace_bytes.  A request above the budget comes back with status 1 ("not computed").
+// max_trace_bytes.  A request above the budget comes back with status 1 ("not computed").  The thin requests of a launch set run
+// sorted by step count, four of a kind per wave, unless SPDP_B_THIN_SORT=0 (then in the order given).
 struct SpdpBRequest {
     int parent = 0;                 // the pair
     SpdpProblem p{};                // the pair's sequences (host pointers) with the request's ranges and end flags

@@ -38,7 +38,7 @@ EXPORTS = [
     "spdp_rerun_stats", "spdp_sweep_stats", "spdp_chunk_stats", "spdp_chunk_plan", "spdp_ladder_plan", "spdp_ladder_postwork",
     "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
     "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
-    "spdp_align_b_seeded", "spdp_seeded_stats_b", "spdp_align_b_seeded_refusal",
+    "spdp_align_b_seeded", "spdp_seeded_stats_b", "spdp_align_b_seeded_refusal", "spdp_lsp_b",
 ]
 
 
@@ -68,6 +68,7 @@ def load_library() -> C.CDLL:
     lib.spdp_cells_b.restype = lib.spdp_trace_bytes_b.restype = C.c_int64
     lib.spdp_align_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
     lib.spdp_homscore_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+    lib.spdp_lsp_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.spdp_align_b_seeded.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
     lib.spdp_seeded_stats_b.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.spdp_align_b_seeded_refusal.restype = C.c_char_p
@@ -723,6 +724,26 @@ class Engine:
             res.append((int(arr[i].score), skl))
         self.lib.spdp_free_alignments(arr, n)
         return res
+
+    LSP_STATS_B = ("device_batches", "thin_requests", "wide_requests", "host_requests", "requests_le16_rows", "cells_le16_rows", "cells",
+                   "requests_not_computed")
+
+    def lsp_b(self, sc, up: abi.UnsplicedParams, ps, allow_partial=False):
+        """spdp_lsp_b: every problem as one lspB_ng request of the seeded path (the thin sweep for at most 16 rows unless
+        SPDP_B_THIN=0).  ([(score, skl)] as align_b returns them, the call's counters by the names of LSP_STATS_B)"""
+        n = len(ps)
+        arr = (abi.Alignment * n)()
+        st = (C.c_int64 * len(self.LSP_STATS_B))()
+        rc = self.lib.spdp_lsp_b(self.ctx, C.byref(sc), C.byref(up), ps.array(), n, arr, st)
+        if not (allow_partial and rc == 1):
+            self._check(rc, "spdp_lsp_b")
+        res = []
+        for i in range(n):
+            k = arr[i].n_skl
+            skl = np.ctypeslib.as_array(C.cast(arr[i].skl, C.POINTER(C.c_int32)), shape=(k, 2)).copy() if k else np.zeros((0, 2), dtype=np.int32)
+            res.append((int(arr[i].score), skl))
+        self.lib.spdp_free_alignments(arr, n)
+        return res, dict(zip(self.LSP_STATS_B, (int(x) for x in st)))
 
     def align_b_seeded(self, sc, up: abi.UnsplicedParams, sp: abi.SeedParams, ps, model=None, hsps=None, lowest_levels=None,
                        allow_partial=False):

@@ -13,7 +13,7 @@ from tests import unspliced_cases as uc
 from tests import unspliced_ref as ubr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b"]
+NEW = ["spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b", "spdp_lsp_b"]
 
 
 def test_symbols_are_declared_and_exported():
@@ -117,3 +117,22 @@ def test_host_edit_records_give_the_programs_cigar():
                     assert [out[i].sam_flag, out[i].sam_pos, out[i].sam_mapq, out[i].sam_left, out[i].sam_right] == sam
             lib.spdp_free_edits(out, n)
         assert lib.spdp_skl_edits_b(C.byref(sc), C.byref(up), ps.array(), n, arr, 7, (abi.Edits * n)()) == -1
+
+
+def test_lsp_b_without_a_context_is_refused():
+    """spdp_lsp_b takes spdp_align_b's arguments and a counter array; without a context (no device) it refuses like
+    spdp_align_b, before it reads anything else or writes the counters"""
+    lib = engine.load_library()
+    sc, up, ps, _ = uc.problems("shapes1", 0)
+    n = len(ps)
+    out = (abi.Alignment * n)()
+    stats = (C.c_int64 * 8)(*([7] * 8))
+    assert lib.spdp_lsp_b(None, C.byref(sc), C.byref(up), ps.array(), n, out, stats) == -1
+    assert lib.spdp_align_b(None, C.byref(sc), C.byref(up), ps.array(), n, out) == -1
+    assert list(stats) == [7] * 8 and all(out[i].n_skl == 0 and not out[i].skl for i in range(n))
+    assert lib.spdp_lsp_b(None, None, None, None, 0, None, None) == -1
+    # the refusals that carry a message name the fields spdp_align_b names (tests/test_gpu_thin_sweep.py reads them on a device);
+    # both go through the same two functions
+    src = open(os.path.join(ROOT, "spaln_amd", "csrc", "spdp_b_api.cpp")).read()
+    body = src[src.index('extern "C" int spdp_lsp_b('):src.index('extern "C" int spdp_homscore_b(')]
+    assert "refused(sc, up)" in body and "bad_problem(*sc, probs[i])" in body
