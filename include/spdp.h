@@ -167,6 +167,15 @@ int64_t spdp_cells(const SpdpProblem* p, const SpdpWindow* wdw);
 int spdp_splice_signals(SpdpContext* ctx, const SpdpSignalModel* model, const uint8_t* b, int32_t b_len,
                         int32_t left, int32_t right, int16_t* sig5, int16_t* sig3,
                         uint8_t* cano5, uint8_t* cano3, uint8_t* dinc);
+/* The column records the sweeps read, as spdp_align_s would lay them out for this batch (either path: sig5 / sig3 [+ cano5 /
+ * cano3 / dinc] supplied, or plain codes + SpdpScoring::sigmodel), read back for inspection and tests.  col_off receives
+ * n_probs + 1 entries: the first record of each problem and the total (a problem owns b_len + 1 records followed by zero
+ * padding).  With cols = aux = NULL only col_off and info are filled; otherwise cap >= col_off[n_probs] records must fit:
+ * cols takes two int32 per record {sig5 + ipen | sig3 << 16 (0 when spj = 0), the code of base n - 1}, aux two bytes per
+ * record {donor | acceptor << 1, dinc5 << 4 | dinc3} when the batch has the exact-model inputs (info[0] = 1; untouched
+ * otherwise).  info[1], info[2]: the largest sig5 + ipen and sig3 among the records (the fp32 sweeps' range guard). */
+int spdp_signal_records_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
+                          int64_t* col_off, int64_t cap, int32_t* cols, uint8_t* aux, int32_t* info);
 
 int spdp_wip_scoreonly(SpdpContext* ctx, const SpdpScoring* sc,
                        const SpdpProblem* probs, int n_probs, int32_t* scores);
@@ -691,6 +700,13 @@ int spdp_homscore_h(SpdpContext* ctx, const SpdpScoringH* sc,
  * missing; those come back with n_skl = 0, score NEVSEL. */
 int spdp_align_h(SpdpContext* ctx, const SpdpScoringH* sc,
                  const SpdpProblemH* probs, int n_probs, SpdpAlignment* out);
+/* The column records the protein engines read, as spdp_align_h would lay them out for this batch (all seven arrays supplied,
+ * or tron codes + SpdpScoringH::sigmodel), read back for inspection and tests: arguments as spdp_signal_records_s.  A problem
+ * owns b_len + 3 records followed by zero padding; cols takes four int32 per record {coding potential | tron code << 16 |
+ * phase flags << 24, the two acceptor candidates, the two donor candidates + ipen, dinc}, aux four int16 {sigS, sigT, sigE,
+ * sig5}. */
+int spdp_signal_records_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpProblemH* probs, int n_probs,
+                          int64_t* col_off, int64_t cap, int32_t* cols, int16_t* aux);
 
 /* Aln2h1::forwardH_ng (src/fwd2h1.cc:294-617, with initH_ng / lastH_ng): the scalar -A0 engine -- int32,
  * exact intron-length penalty, top-4 donor list per row and codon phase -- on the stripe31() band.

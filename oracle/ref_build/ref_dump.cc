@@ -31,6 +31,7 @@
 //   -Q n     seeded path (algmode.qck = n, 1..3): the HSPs of geneorient() as match_2 obtains them (spaln.cc:773-776) are
 //            dumped as inputs, alignS_ng(seqs, pwd, gsi, 1) runs with seeding on, and every Wilip the walk constructs on a
 //            sub-range (seededS_ng at the higher levels, fwd2s1.cc:2609) is recorded through the tap below
+//   -a N     algmode.any (-ya: which non-canonical dinucleotides count as splice sites, and at which level)
 //   -O       alignS_ng(ori = 3) fixture: both strands prepared as spaln.cc:1137-1152 does (genomicseq, ori = 3),
 //            the reverse-strand problem dumped under r_*, the result of alignS_ng(seqs, pwd, gsi, 3) under ori3_*
 
@@ -74,7 +75,7 @@ Wilip::Wilip(const Seq* seqs[], const PwdB* pwd, const int level)
 
 int main(int argc, const char** argv)
 {
-	int	ls = 2, sh = 100, local = 0, ubh = 0, nquant = 0, ori3 = 0, seeded_q = 0, crs = -1, sup_tcodon = 0;
+	int	ls = 2, sh = 100, local = 0, ubh = 0, nquant = 0, ori3 = 0, seeded_q = 0, crs = -1, sup_tcodon = 0, any_lvl = -1;
 	long	vmfspace = 0;
 const	char*	exg = 0;
 	std::vector<int>	udh_list, alg_list;
@@ -88,6 +89,7 @@ const	char*	exg = 0;
 		case 'w': sh = atoi(argv[++ai]); break;
 		case 'L': local = 1; break;
 		case 'O': ori3 = 1; break;
+		case 'a': any_lvl = atoi(argv[++ai]) & 3; break;
 		case 'Q': seeded_q = atoi(argv[++ai]) & 3; break;
 		case 'B': g_o12_mode = true; break;
 		case 'I': {			// query positions that carry a conserved intron (SigII of the query), -J weight
@@ -150,6 +152,7 @@ const	char*	outfn = argv[ai + 2];
 	if (local) algmode.lcl |= 16;
 	if (local == 3) algmode.lcl |= 32;
 	if (crs >= 0) algmode.crs = crs;
+	if (any_lvl >= 0) algmode.any = any_lvl;	// read by Exinon::intron53_c / intron53_p (both dumpers build their Exinon below)
 	if (vmfspace) MaxVmfSpace = (int) vmfspace;
 	if (nquant) IntronPrm.nquant = nquant;
 	OutPrm.all_out = 1;
@@ -251,6 +254,28 @@ const	char*	outfn = argv[ai + 2];
 		if (i - 1 >= 0) d5[i - 1] = nc;
 		d3[i + 1] = nc;
 	    }
+	    if (any_lvl >= 0) {
+		// the LEVELS of the sites (INT53::cano5 / cano3 are private and isDonor / isAccpt say only "some level"): read through
+		// Exinon::isCanon(d, a) against cells whose level no `any` changes -- an acceptor behind AG (3) and AC (2), a donor
+		// at GT (3) and AT (2) (codepot.cc:453-473; codepot.h:108-113).  Only with -a: other fixtures keep their keys
+		int	aAG = -1, aAC = -1, dGT = -1, dAT = -1;
+		for (int n = b->left + 2; n < b->right - 1; ++n) {
+		    if (aAG < 0 && d3[n] == 2) aAG = n;
+		    if (aAC < 0 && d3[n] == 1) aAC = n;
+		    if (dGT < 0 && d5[n] == 11) dGT = n;
+		    if (dAT < 0 && d5[n] == 3) dAT = n;
+		}
+		if (aAG < 0 || aAC < 0 || dGT < 0 || dAT < 0) { fprintf(stderr, "ref_dump -a: the window needs an AG, AC, GT and AT\n"); exit(4); }
+		std::vector<unsigned char> l5(b->len + 1, 0), l3(b->len + 1, 0);
+		for (int n = b->left; n <= b->right; ++n) {
+		    const int x5 = b->exin->isCanon(n, aAG), y5 = b->exin->isCanon(n, aAC);
+		    l5[n] = x5 == 6? 3: y5 == 4? 2: x5 == 4? 1: 0;
+		    const int x3 = b->exin->isCanon(dGT, n), y3 = b->exin->isCanon(dAT, n);
+		    l3[n] = x3 == 6? 3: y3 == 4? 2: x3 == 4? 1: 0;
+		}
+		w.put(pn("cano5_lvl"), 1, l5.data(), l5.size());
+		w.put(pn("cano3_lvl"), 1, l3.data(), l3.size());
+	    }
 	    w.put(pn("dinc5"), 1, d5.data(), b->len + 1);
 	    w.put(pn("dinc3"), 1, d3.data(), b->len + 1);
 	    std::vector<int> t53(256, 0), mrep(16, -1), nrep(16, -1);
@@ -338,6 +363,14 @@ const	char*	outfn = argv[ai + 2];
 	    }
 	    w.put_i32("sig53tab01", tab);
 	    w.put_i32("sigmodel", sm);
+	    if (any_lvl >= 0) {
+		// the thresholds of intron53_n's phase rule (th = (STYPE) (fS * tonic), codepot.cc:482-483): fS, tonic5, tonic3 as
+		// float bit patterns.  Only with -a, so that the fixtures made without it keep their set of keys
+		const float th[3] = {(float) b->exin->fS, (float) pwd->eijpat->tonic5, (float) pwd->eijpat->tonic3};
+		std::vector<int> tb(3);
+		memcpy(tb.data(), th, sizeof th);
+		w.put_i32("sigphase", tb);
+	    }
 	}
 	if (ori3) {
 	    a->comrev();

@@ -29,9 +29,12 @@ class PatMat:
 
 
 def model_of(fx: dict) -> dict:
-    return dict(pm5=PatMat(fx["pm5_hdr"], fx["pm5_f32"]), pm3=PatMat(fx["pm3_hdr"], fx["pm3_f32"]),
-                tab=np.asarray(fx["sig53tab01"], dtype=np.int64), any=int(fx["sigmodel"][1]), both_ori=int(fx["sigmodel"][3]),
-                fs=np.asarray(fx["sigmodel"][:1], dtype=np.int32).view(np.float32)[0])
+    md = dict(pm5=PatMat(fx["pm5_hdr"], fx["pm5_f32"]), pm3=PatMat(fx["pm3_hdr"], fx["pm3_f32"]),
+              tab=np.asarray(fx["sig53tab01"], dtype=np.int64), any=int(fx["sigmodel"][1]), both_ori=int(fx["sigmodel"][3]),
+              fs=np.asarray(fx["sigmodel"][:1], dtype=np.int32).view(np.float32)[0])
+    if "sigphase" in fx:                            # dumps made with ref_dump -a: fS, tonic5, tonic3 of the phase rule
+        md["fS"], md["tonic5"], md["tonic3"] = np.asarray(fx["sigphase"], dtype=np.int32).view(np.float32)
+    return md
 
 
 def scan(pm: PatMat, x: np.ndarray, pos: int) -> np.float32:
@@ -101,8 +104,9 @@ def classes(b_codes: np.ndarray, left: int, right: int, any_: int = 0, both_ori:
     b = np.asarray(b_codes, dtype=np.uint8)
     n = b.size
     c = RED[b]
-    prev = np.concatenate([[1], c[:-1]])
-    prev[left] = 1
+    prev = np.concatenate([[1], c])[:n]
+    if left < n:
+        prev[left] = 1
     nc = ((prev << 2) + c) & 0xf
     k5t, k3t = cano_tables(any_, both_ori)
     d5 = np.zeros(n + 3, dtype=np.uint8); d3 = np.zeros(n + 3, dtype=np.uint8)
@@ -129,3 +133,55 @@ def splice_signals(model: dict, b_codes: np.ndarray, left: int, right: int, lo: 
         s5[pos] = int(v5) + int(model["tab"][d5[pos]])          # (STYPE) truncates towards zero
         s3[pos] = int(v3) + int(model["tab"][16 + d3[pos]])
     return s5, s3
+
+
+def phases(model: dict, b_codes: np.ndarray, left: int, right: int, s5: np.ndarray, s3: np.ndarray):
+    """phs5, phs3 (int8, len(b) + 1) as intron53_n's loop leaves them (codepot.cc:498-521): a cell becomes 0 where a site of
+    any level sits or -- algmode.any == 2 -- the signal exceeds th = (short)(fS * tonic); a site above level 1 marks its
+    neighbours (GTGT / AGAG: the cell in front becomes 2 when the previous site had marked it 1)"""
+    n = np.asarray(b_codes).size
+    _, _, c5, c3 = classes(b_codes, left, right, int(model.get("any", 0)), int(model.get("both_ori", 0)))
+    th5 = th3 = 0                                   # (read under any == 2 only; the dumps made with -a carry fS and the tonics)
+    if model["any"] == 2:
+        th5 = int(np.float32(model["fS"] * model["tonic5"])); th3 = int(np.float32(model["fS"] * model["tonic3"]))
+    p5 = np.full(n + 2, -2, dtype=np.int8); p3 = np.full(n + 2, -2, dtype=np.int8)
+    for pos in range(left, right):
+        for sig, cano, ph, th in ((s5, c5, p5, th5), (s3, c3, p3, th3)):
+            if ph[pos] == -2 and ((model["any"] == 2 and int(sig[pos]) > th) or cano[pos]):
+                ph[pos] = 0
+                if cano[pos] > 1:
+                    ph[pos + 1] = 1
+                    if pos >= 1:
+                        ph[pos - 1] = 2 if ph[pos - 1] == 1 else -1
+    return p5[:n + 1], p3[:n + 1]
+
+
+def best_context(pm: PatMat, fixed: dict):
+    """the cols + 2 reduced codes under which the order-2 matrix scores highest, with the codes of `fixed` {index: code} held
+    (exact: dynamic programming over the last two codes; float64, so a bound on the float32 scan up to rounding).  Returns
+    (fit without tonic, codes); the scan's position `pos` = pm.offset in these coordinates"""
+    m = pm.mtx.reshape(pm.cols, pm.rows).astype(np.float64)
+    ok = lambda i, v: fixed.get(i, v) == v
+    neg = -1e18
+    f = np.full((4, 4), neg)
+    for a in range(4):
+        for b in range(4):
+            if ok(0, a) and ok(1, b):
+                f[a, b] = m[0][a] + m[0][4 * a + b + 4]
+    back = []
+    for s in range(pm.cols):
+        g = np.full((4, 4), neg); bk = np.zeros((4, 4), dtype=np.int64)
+        for a in range(4):
+            for b in range(4):
+                if f[a, b] <= neg / 2:
+                    continue
+                for c in range(4):
+                    v = f[a, b] + m[s][16 * a + 4 * b + c + 20]
+                    if ok(s + 2, c) and v > g[b, c]:
+                        g[b, c] = v; bk[b, c] = a
+        back.append(bk); f = g
+    b, c = (int(v) for v in np.unravel_index(int(np.argmax(f)), f.shape))
+    top, seq = float(f[b, c]), [c, b]
+    for s in range(pm.cols - 1, -1, -1):
+        a = int(back[s][b, c]); seq.append(a); b, c = a, b
+    return top, np.array(seq[::-1], dtype=np.int64)

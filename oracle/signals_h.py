@@ -110,7 +110,7 @@ def classes(b: np.ndarray, left: int, right: int, any_: int = 0):
     c = TNRED[b].copy()
     c[c > 3] = 1
     n = b.size
-    prev = np.concatenate([[1], c[:-1]])
+    prev = np.concatenate([[1], c])[:n]
     if left < n:
         prev[left] = 1
     nc = ((prev << 2) + c) & 0xf

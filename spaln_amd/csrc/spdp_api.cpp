@@ -408,6 +408,7 @@ int DevStore::upload(SpdpContext* c, const SpdpScoring* scp, const SpdpProblem* 
         for (int i = 0; i < n; ++i) { max_s5 = std::max(max_s5, p_s5[i]); max_s3 = std::max(max_s3, p_s3[i]); }
     }
     sc.sigmodel = nullptr;                                   // the caller's model is not ours to keep
+    this->max_s5 = max_s5; this->max_s3 = max_s3;
     // bounds for the fp32 sweeps (DevRun::build): best substitution score, best net gain of one intron
     fp_maxpos = 1;
     for (int i = 0; i < sc.mtx_dim * sc.mtx_dim; ++i) fp_maxpos = std::max(fp_maxpos, (int) sc.mtx[i]);

@@ -115,6 +115,9 @@ static int validate(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpProblemH
     if (p->a_left < 0 || p->a_right > p->a_len || p->a_left > p->a_right) return fail("bad query range");
     if (p->b_left < 0 || p->b_right > p->b_len || p->b_left > p->b_right) return fail("bad genomic range");
     if (p->b_left < p->exin_left || p->b_right > p->exin_right) return fail("active range outside the Exinon range");
+    // the device-made signals are computed over [exin_left, exin_right) and the phase rule writes the cells next to it
+    // (spdp_signals_h.hip): a range beyond the sequence would leave the problem's slot
+    if (p->exin_left < 0 || p->exin_right > p->b_len) return fail("Exinon range outside the sequence (exin_left < 0 or exin_right > b_len)");
     return 0;
 }
 
@@ -1271,6 +1274,26 @@ int spdp_lsp_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpProblemH* pro
     if (st.upload(ctx, sc, probs, n_probs)) return -1;
     HStats hs;
     return deliver(st, 2, out, hs);
+}
+
+// the column records of a batch as the engines find them: HStore::upload as spdp_align_h runs it (host packing of supplied
+// arrays, or spdp_signals_h.hip for tron codes + sigmodel), copied back with the padding between the problems
+int spdp_signal_records_h(SpdpContext* ctx, const SpdpScoringH* sc, const SpdpProblemH* probs, int n_probs,
+                          int64_t* col_off, int64_t cap, int32_t* cols, int16_t* aux)
+{
+    if (!ctx) return -1;
+    if (!sc || !probs || n_probs < 1 || !col_off) { ctx->err = "spdp_signal_records_h: null argument or empty batch"; return -1; }
+    HStore st;
+    if (st.upload(ctx, sc, probs, n_probs)) return -1;
+    const int64_t tot = st.col_off[n_probs - 1] + st.col_len[n_probs - 1];
+    for (int i = 0; i < n_probs; ++i) col_off[i] = st.col_off[i];
+    col_off[n_probs] = tot;
+    if (!cols && !aux) return 0;                // the sizes alone
+    if (cap < tot) { ctx->err = "spdp_signal_records_h: capacity below col_off[n]"; return -1; }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (cols) HIPCHK(hipMemcpy(cols, st.d_cols, (size_t) tot * sizeof(int4), hipMemcpyDeviceToHost));
+    if (aux) HIPCHK(hipMemcpy(aux, st.d_aux, (size_t) tot * sizeof(short4), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 struct SpdpBatchH {

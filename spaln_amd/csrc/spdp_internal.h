@@ -415,6 +415,7 @@ struct DevStore {
     std::vector<int32_t> cip_off;           // per parent: first entry of its cip row in d_cip, -1 = none
     bool has_exact = false;                 // exact-model inputs (cano / dinc / intpen) were supplied
     int fp_maxpos = 1, fp_gain = 0;         // largest substitution score; best net score of one intron (>= 0)
+    int max_s5 = INT32_MIN, max_s3 = INT32_MIN;   // largest sig5 + ipen / sig3 of the column records (what fp_gain was made from)
     DevStore() = default;
     DevStore(const DevStore&) = delete;
     DevStore& operator=(const DevStore&) = delete;

@@ -97,6 +97,26 @@ extern "C" int spdp_splice_signals(SpdpContext* ctx, const SpdpSignalModel* mode
     return 0;
 }
 
+// the column records of a batch as the sweeps find them: DevStore::upload as spdp_align_s runs it (host packing of supplied
+// arrays, or spdp_signals.hip for plain codes + sigmodel), copied back with the padding between the problems
+extern "C" int spdp_signal_records_s(SpdpContext* ctx, const SpdpScoring* sc, const SpdpProblem* probs, int n_probs,
+                                     int64_t* col_off, int64_t cap, int32_t* cols, uint8_t* aux, int32_t* info)
+{
+    if (!ctx) return -1;
+    if (!sc || !probs || n_probs < 1 || !col_off) { ctx->err = "spdp_signal_records_s: null argument or empty batch"; return -1; }
+    DevStore st;
+    if (st.upload(ctx, sc, probs, n_probs)) return -1;
+    const int64_t tot = st.col_off[n_probs - 1] + st.b_len[n_probs - 1] + 1 + SPDP_COL_PAD;
+    for (int i = 0; i < n_probs; ++i) col_off[i] = st.col_off[i];
+    col_off[n_probs] = tot;
+    if (info) { info[0] = st.d_aux ? 1 : 0; info[1] = st.max_s5; info[2] = st.max_s3; }
+    if (!cols && !aux) return 0;                // the sizes alone
+    if (cap < tot) { ctx->err = "spdp_signal_records_s: capacity below col_off[n]"; return -1; }
+    if (cols) HIPCHK(hipMemcpy(cols, st.d_cols, (size_t) tot * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (aux && st.d_aux) HIPCHK(hipMemcpy(aux, st.d_aux, (size_t) tot * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- protein side (spdp_signals_h.hip) ---------------------------------------------------------------------------
 #include "spdp_h_internal.h"
 

@@ -88,7 +88,7 @@ void spdh_signals(SignalArgsH A)
     if (pos >= N) return;
     const int base = p0 - SGH_HALO;
     auto tron = [&](int i) { return (int) s_b[i - base]; };
-    auto xs = [&](int i) { return (int) sgh_tnred[tron(i) & 31]; };
+    auto xs = [&](int i) { return (int) sgh_tnred[min(tron(i), 31)]; };       // codes above 31: no base, as 26 .. 31 (the pack gives them the zero row)
     auto xc = [&](int i) { const int c = xs(i); return c > 3 ? 1 : c; };
     auto nc = [&](int i) { return (((i == J.left ? 1 : xc(i - 1)) << 2) + xc(i)) & 0xf; };
     int v5 = 0, v3 = 0, vS = 0, vT = 0, vE = 0, d5 = 0, d3 = 0, c5 = 0, c3 = 0, vB = INT32_MIN;

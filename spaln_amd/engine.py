@@ -39,6 +39,7 @@ EXPORTS = [
     "spdp_dispersed_rests", "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed",
     "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
     "spdp_align_b_seeded", "spdp_seeded_stats_b", "spdp_align_b_seeded_refusal", "spdp_lsp_b",
+    "spdp_signal_records_s", "spdp_signal_records_h",
 ]
 
 
@@ -78,6 +79,8 @@ def load_library() -> C.CDLL:
     lib.spdp_splice_signals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.spdp_splice_signals_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+    lib.spdp_signal_records_s.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+    lib.spdp_signal_records_h.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 2
     lib.spdp_batch_upload.restype = C.c_void_p
     lib.spdp_batch_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.spdp_batch_free.argtypes = [C.c_void_p]
@@ -407,6 +410,37 @@ class Engine:
                                                                                   "phs5", "phs3", "dinc"))),
                     "spdp_splice_signals_h")
         return out
+
+    def signal_records_s(self, sc: abi.Scoring, ps: abi.ProblemSet) -> dict:
+        """spdp_signal_records_s: the column records of the batch as spdp_align_s lays them out (arrays supplied, or codes +
+        sigmodel): cols (records x 2 int32), aux (records x 2 uint8, or None), col_off (n + 1), max_s5, max_s3"""
+        n = len(ps)
+        arr = ps.array() if n else None
+        off = np.zeros(n + 1, dtype=np.int64)
+        info = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.spdp_signal_records_s(self.ctx, C.byref(sc), arr, n, off.ctypes.data, 0, None, None,
+                                                   info.ctypes.data), "spdp_signal_records_s")
+        tot = int(off[n])
+        cols = np.zeros((tot, 2), dtype=np.int32)
+        aux = np.zeros((tot, 2), dtype=np.uint8)
+        self._check(self.lib.spdp_signal_records_s(self.ctx, C.byref(sc), arr, n, off.ctypes.data, tot, cols.ctypes.data,
+                                                   aux.ctypes.data, info.ctypes.data), "spdp_signal_records_s")
+        return dict(cols=cols, aux=aux if info[0] else None, col_off=off, max_s5=int(info[1]), max_s3=int(info[2]))
+
+    def signal_records_h(self, sc: abi.ScoringH, ps: abi.ProblemSetH) -> dict:
+        """spdp_signal_records_h: the column records of the batch as spdp_align_h lays them out (arrays supplied, or tron
+        codes + sigmodel): cols (records x 4 int32), aux (records x 4 int16), col_off (n + 1)"""
+        n = len(ps)
+        arr = ps.array() if n else None
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._check(self.lib.spdp_signal_records_h(self.ctx, C.byref(sc), arr, n, off.ctypes.data, 0, None, None),
+                    "spdp_signal_records_h")
+        tot = int(off[n])
+        cols = np.zeros((tot, 4), dtype=np.int32)
+        aux = np.zeros((tot, 4), dtype=np.int16)
+        self._check(self.lib.spdp_signal_records_h(self.ctx, C.byref(sc), arr, n, off.ctypes.data, tot, cols.ctypes.data,
+                                                   aux.ctypes.data), "spdp_signal_records_h")
+        return dict(cols=cols, aux=aux, col_off=off)
 
     def wip_scoreonly(self, sc: abi.Scoring, ps: abi.ProblemSet) -> np.ndarray:
         out = np.zeros(len(ps), dtype=np.int32)

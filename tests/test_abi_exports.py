@@ -23,6 +23,17 @@ def test_library_exports_all_declared_symbols():
     missing = [s for s in _declared() if not hasattr(lib, s)]
     assert not missing, missing
     assert set(engine.EXPORTS) <= set(_declared())
+    # the read-back of the column records (tests/test_gpu_signal_cases.py): declared, exported, wrapped
+    for name in ("spdp_signal_records_s", "spdp_signal_records_h"):
+        assert name in _declared() and name in engine.EXPORTS and hasattr(lib, name)
+    assert hasattr(engine.Engine, "signal_records_s") and hasattr(engine.Engine, "signal_records_h")
+
+
+def test_signal_records_refuse_a_null_context():
+    """without a device the two entries can only refuse: -1, nothing touched"""
+    lib = engine.load_library()
+    assert lib.spdp_signal_records_s(None, None, None, 0, None, 0, None, None, None) == -1
+    assert lib.spdp_signal_records_h(None, None, None, 0, None, 0, None, None) == -1
 
 
 def test_struct_layout_matches_header(tmp_path):

@@ -27,6 +27,8 @@ def test_device_signals_equal_reference(path):
     assert np.array_equal(got["dinc"] >> 4, fx["dinc5"]) and np.array_equal(got["dinc"] & 15, fx["dinc3"])
     assert np.array_equal((got["cano5"] > 0)[ok5], (fx["cano5"] > 0)[ok5])
     assert np.array_equal((got["cano3"] > 0)[ok3], (fx["cano3"] > 0)[ok3])
+    if "cano5_lvl" in fx:                           # (sg_any*: dumped with the sites' levels)
+        assert np.array_equal(got["cano5"][ok5], fx["cano5_lvl"][ok5]) and np.array_equal(got["cano3"][ok3], fx["cano3_lvl"][ok3])
 
 
 def test_device_signals_equal_oracle_everywhere():
