@@ -921,6 +921,54 @@ int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDe
                   const struct SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
                   const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
                   SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status);
+/* Who served the HSP searches of the last spdp_blk_find on this context (a spdp_map_align_* call: of the last block search it
+ * made): out[0 .. n) of {search tasks, served on the device, handed back to the host form as too long,
+ * handed back as too many (shared words, segments or records beyond the wave's LDS), retry searches (tasks a machine asked for
+ * after its first regions: a protein query's looks at a grown region), device batches}.  served + handed back = tasks.  Host
+ * bookkeeping; returns 0, -1 on a null argument. */
+int spdp_blk_find_stats(const SpdpContext* ctx, int64_t* out, int n);
+
+/* ---- the HSP search of candidate regions by itself, for tests and tools (the product's own search runs underneath) ------------
+ * The LDS plan of one device launch of the search (spdp_hsp.hip): a wave's table of query words (hash_slots, a power of two, twice
+ * the words it can hold), its list of shared words (hit_cap, a power of two: the list is sorted in place), seed segments (seg_cap),
+ * records per task (out_cap) and the waves launched.  lds_bytes / waves_per_cu are outputs. */
+typedef struct SpdpHspPlan {
+    int32_t hash_slots, hit_cap, seg_cap, out_cap, n_waves;
+    int32_t lds_bytes, waves_per_cu, reserved;
+} SpdpHspPlan;
+/* The plan spdp_blk_find uses for a batch whose longest query range is `longest` residues, of n_tasks tasks on a device of n_cu
+ * compute units (0: one): every field of *want that is 0 (want may be NULL) is chosen as the product chooses it -- hash_slots from
+ * `longest`, hit_cap by hash_slots or from SPDP_HSP_HITS (rounded up to a power of two, at least 256), seg_cap 256, out_cap 96,
+ * n_waves = min(n_tasks, n_cu x waves_per_cu).  Refused, with the reason in err[0 .. err_len) (may be NULL): hash_slots or hit_cap
+ * that is no power of two of at least 64, a cap out of range, a plan whose LDS exceeds what a workgroup can have (160 KB).  Host
+ * code, no device.  Returns 0 / -1. */
+int spdp_hsp_plan(const SpdpHspPlan* want, int32_t longest, int32_t mtx_rows, int32_t mtx_cols, int32_t n_tasks, int32_t n_cu,
+                  SpdpHspPlan* plan, char* err, int32_t err_len);
+typedef struct SpdpHspTask {         /* region [base, base + len) of chromosome chr, read as the other strand when rvs, against   */
+    int32_t query, chr, base, len, rvs;                               /* the range of query `query`                                */
+} SpdpHspTask;
+typedef struct SpdpHspRequest {
+    const struct SpdpWilipModel* model;      /* level[0] (scaled below shortquery as FindHsp's level -1), mtx, end_bonus, crs, ser,  */
+    const SpdpGenome* genome;                /* ser2; dvsp = 1: protein queries, regions read as tron codes                          */
+    const uint8_t* codes; const int64_t* offs; const int32_t* left; const int32_t* right;
+    const int32_t* tlen;                     /* per query Seq::tlen, or NULL: the queries' lengths                                   */
+    int32_t n_queries;
+    const SpdpHspTask* tasks; int32_t n_tasks;
+    int32_t a_exgl, a_exgr;
+} SpdpHspRequest;
+/* The tasks on the device, the genome made resident for the call.  Per task flags[t] (0 served, 1 too long, 2 too many -- the
+ * tasks spdp_blk_find hands to the host form) and its raw records, unchained, 7 ints each {jx, jy, jlen, nid, jscr, diagonal, first
+ * word} in scan order (diagonal, first word): task t's are (*recs)[7 rec_off[t] .. 7 rec_off[t + 1]) (rec_off: n_tasks + 1; *recs
+ * malloc'ed, free() it).  A flagged task has no records.  *used (may be NULL): the plan as launched.  Refused by name
+ * (spdp_last_error): what spdp_hsp_plan refuses, a region outside its chromosome, left / right / tlen outside the query, a
+ * spaced pattern whose length differs from `width`, a query code at or above mtx_rows, a matrix without a column for every
+ * genomic code.  Returns 0 / -1. */
+int spdp_hsp_tasks(SpdpContext* ctx, const SpdpHspRequest* rq, const SpdpHspPlan* want, SpdpHspPlan* used,
+                   int32_t* flags, int64_t* rec_off, int32_t** recs);
+/* The same tasks through the host form (spdp_region.h + spdp_hsp_host.h, level -1), no device: records as above, and per task
+ * counts[3 t ..] = {shared words, seed segments, records above the threshold} -- what the device's caps are about.  The
+ * refusals of spdp_hsp_tasks, the reason in err. */
+int spdp_hsp_tasks_host(const SpdpHspRequest* rq, int32_t* counts, int64_t* rec_off, int32_t** recs, char* err, int32_t err_len);
 
 /* ---- block search, fourth slice (round 5): the index builder ------------------------------------------------------------
  * `spaln -W -KD genome.mfa` for the block index (<db>.bkn): MakeBlk::idxblk / m_idxblk + blkscrtab + findChrBbound

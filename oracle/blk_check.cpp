@@ -11,6 +11,9 @@
 #include "../spaln_amd/csrc/spdp_hsp_host.h"
 #include "../spaln_amd/csrc/spdp_region.h"
 
+// the searches loci_check_call made since the tap was last read: per search {chr, rvs, base, len, n, the n ints of its units, flattened}
+static std::vector<int32_t> g_tap;
+
 extern "C" {
 // One TestOutput call of one query: pairs (9 ints each: bscr chr lb rb ub db zl zr rvs), mmct[4], the run scores near the pairs
 // ((block | direction << 28, score) x n_runs), forced (the call is TestOutput(1)), critjscr in / out.  The log has the recorder's layout
@@ -47,6 +50,13 @@ int loci_check_call(const uint8_t* genome, const int64_t* chr_off, int n_chr, co
         spdp_region::materialize(genome, chr_off, r.chr, r.base, r.len, r.rvs != 0, P.bbt == 3, codes);
         const spdp_hsp::Seqs s = {q, q_len, left, right, P.a_exgl, P.a_exgr, codes.data(), r.len, 0, r.len, P.bbt == 3 ? 3 : 1, nullptr, nullptr, nullptr};
         spdp_hsp::search(model, s, gc, -1, units);
+        {
+            std::vector<int32_t> f;
+            spdp_hsp::flatten(units, f);
+            const int32_t head[5] = {r.chr, r.rvs, r.base, r.len, (int32_t) f.size()};
+            g_tap.insert(g_tap.end(), head, head + 5);
+            g_tap.insert(g_tap.end(), f.begin(), f.end());
+        }
         c.take(units);
     }
     *critjscr = c.critjscr; *verdict = c.result;
@@ -65,6 +75,35 @@ int loci_check_call(const uint8_t* genome, const int64_t* chr_off, int n_chr, co
         for (const spdp_hsp::Hsp& t : g.hsp) { PUT(t.jx); PUT(t.jy); PUT(t.jlen); PUT(t.nid); PUT(t.jscr); }
     }
 #undef PUT
+    return n;
+}
+
+// what the tap holds (tests/test_hsp_cases.py replays these searches through spdp_hsp_tasks_host): the ints it holds are returned, up
+// to cap of them copied, the tap emptied
+int blk_check_tap(int32_t* out, int cap)
+{
+    const int n = (int) g_tap.size();
+    if (out) memcpy(out, g_tap.data(), sizeof(int32_t) * (size_t) (n < cap ? n : cap));
+    g_tap.clear();
+    return n;
+}
+
+// raw records of one search (7 ints each, scan order) chained as the search itself chains its HSPs (spdp_hsp_host.h, search()):
+// the units, flattened; returns the ints, up to cap copied.  prm: find_prm of the fixture
+int blk_check_chain(const SpdpWilipModel* model, const int32_t* prm, const int16_t* intpen, int intpen_len, int a_len, int left, int right,
+                    int b_len, const int32_t* recs, int n_recs, int32_t* out, int cap)
+{
+    int vthr = model->level[0].vthr;
+    if (a_len < model->shortquery) vthr = vthr * a_len / model->shortquery;
+    const spdp_hsp::ChainCost C = {model, intpen, intpen_len, prm[13], prm[14], prm[15], prm[16], prm[17], prm[6] == 3 ? 3 : 1, vthr};
+    std::vector<spdp_hsp::Hsp> hsps;
+    for (int i = 0; i < n_recs; ++i) hsps.push_back({recs[7 * i], recs[7 * i + 1], recs[7 * i + 2], recs[7 * i + 3], recs[7 * i + 4]});
+    std::vector<spdp_hsp::Unit> units;
+    spdp_hsp::chain(hsps, C, left, right, 0, b_len, units);
+    std::vector<int32_t> f;
+    spdp_hsp::flatten(units, f);
+    const int n = (int) f.size();
+    memcpy(out, f.data(), sizeof(int32_t) * (size_t) (n < cap ? n : cap));
     return n;
 }
 

@@ -408,6 +408,107 @@ def find(index: "BlockIndex", genome_codes, chr_off, model, sc, prm: BlkFindPara
     return out, status
 
 
+def find_stats(eng) -> dict:
+    """spdp_blk_find_stats: who served the HSP searches of the last find / map_align call on this engine"""
+    v = (C.c_int64 * len(FIND_STATS))()
+    eng.lib.spdp_blk_find_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    eng.lib.spdp_blk_find_stats(eng.ctx, v, len(FIND_STATS))
+    return dict(zip(FIND_STATS, (int(x) for x in v)))
+
+
+FIND_STATS = ("tasks", "device", "too_long", "too_many", "retries", "batches")
+
+
+# ---- the HSP search by itself (include/spdp.h: spdp_hsp_plan, spdp_hsp_tasks, spdp_hsp_tasks_host) -- for tests and tools
+HSP_TOO_LONG, HSP_TOO_MANY = 1, 2
+HSP_FIELDS = ("jx", "jy", "jlen", "nid", "jscr", "diagonal", "first")
+
+
+class HspPlan(C.Structure):              # SpdpHspPlan
+    _fields_ = [(k, C.c_int32) for k in ("hash_slots", "hit_cap", "seg_cap", "out_cap", "n_waves", "lds_bytes", "waves_per_cu", "reserved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_[:7]}
+
+
+class HspTask(C.Structure):              # SpdpHspTask
+    _fields_ = [(k, C.c_int32) for k in ("query", "chr", "base", "len", "rvs")]
+
+
+class HspRequest(C.Structure):           # SpdpHspRequest
+    _fields_ = [("model", C.c_void_p), ("genome", C.c_void_p), ("codes", C.c_void_p), ("offs", C.c_void_p), ("left", C.c_void_p),
+                ("right", C.c_void_p), ("tlen", C.c_void_p), ("n_queries", C.c_int32), ("tasks", C.c_void_p), ("n_tasks", C.c_int32),
+                ("a_exgl", C.c_int32), ("a_exgr", C.c_int32)]
+
+
+def hsp_plan(lib, longest: int, mtx_rows: int, mtx_cols: int, n_tasks: int = 1, n_cu: int = 0, **want) -> dict:
+    """spdp_hsp_plan: the LDS plan spdp_blk_find picks for a batch whose longest query range is `longest` (want: fields given
+    explicitly; 0 or absent = the product's choice).  Host code.  Raises RuntimeError with the refusal's text."""
+    w, out = HspPlan(**{k: int(v) for k, v in want.items()}), HspPlan()
+    err = C.create_string_buffer(256)
+    lib.spdp_hsp_plan.restype = C.c_int
+    lib.spdp_hsp_plan.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_char_p, C.c_int32]
+    if lib.spdp_hsp_plan(C.byref(w), int(longest), int(mtx_rows), int(mtx_cols), int(n_tasks), int(n_cu), C.byref(out), err, 256):
+        raise RuntimeError(err.value.decode())
+    return out.as_dict()
+
+
+class _HspCall:
+    """the arrays a SpdpHspRequest points into, kept while the call runs.  tasks: (query, chr, base, len, rvs) each"""
+
+    def __init__(self, model, genome_codes, chr_off, queries, tasks, ranges=None, tlen=None, exg=(0, 0)):
+        n = len(queries)
+        self.codes, self.offs = _packed(queries)
+        self.left = np.array([0 if ranges is None else ranges[i][0] for i in range(n)], dtype=np.int32)
+        self.right = np.array([len(queries[i]) if ranges is None else ranges[i][1] for i in range(n)], dtype=np.int32)
+        self.tlen = None if tlen is None else np.ascontiguousarray(tlen, dtype=np.int32)
+        self._gc = np.ascontiguousarray(genome_codes, dtype=np.uint8)
+        self._go = np.ascontiguousarray(chr_off, dtype=np.int64)
+        self.g = Genome(self._gc.ctypes.data, self._go.ctypes.data, len(self._go) - 1)
+        self.tasks = np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 5))
+        self.n_tasks = self.tasks.shape[0]
+        self.model = model
+        self.rq = HspRequest(C.addressof(model), C.addressof(self.g), self.codes.ctypes.data, self.offs.ctypes.data, self.left.ctypes.data,
+                             self.right.ctypes.data, None if self.tlen is None else self.tlen.ctypes.data, n, self.tasks.ctypes.data,
+                             self.n_tasks, int(exg[0]), int(exg[1]))
+        self.rec_off = np.zeros(self.n_tasks + 1, dtype=np.int64)
+        self.recs = C.POINTER(C.c_int32)()
+
+    def records(self):
+        """per task its (k, 7) int32 records; frees what the entry handed out"""
+        tot = int(self.rec_off[-1])
+        flat = np.ctypeslib.as_array(self.recs, shape=(7 * tot,)).copy().reshape(tot, 7) if tot else np.zeros((0, 7), dtype=np.int32)
+        _free(self.recs)
+        return [flat[int(self.rec_off[k]):int(self.rec_off[k + 1])] for k in range(self.n_tasks)]
+
+
+def hsp_tasks_host(lib, model, genome_codes, chr_off, queries, tasks, ranges=None, tlen=None, exg=(0, 0)):
+    """spdp_hsp_tasks_host: the tasks through the host form of the search (level -1), no device.  Returns (per task its records as a
+    (k, 7) int32 array of HSP_FIELDS in scan order, counts as an (n_tasks, 3) int32 array of shared words, seed segments, records)."""
+    c = _HspCall(model, genome_codes, chr_off, queries, tasks, ranges, tlen, exg)
+    counts = np.zeros((c.n_tasks, 3), dtype=np.int32)
+    err = C.create_string_buffer(256)
+    lib.spdp_hsp_tasks_host.restype = C.c_int
+    lib.spdp_hsp_tasks_host.argtypes = [C.c_void_p] * 4 + [C.c_char_p, C.c_int32]
+    if lib.spdp_hsp_tasks_host(C.byref(c.rq), counts.ctypes.data, c.rec_off.ctypes.data, C.byref(c.recs), err, 256):
+        raise RuntimeError(err.value.decode())
+    return c.records(), counts
+
+
+def hsp_tasks(eng, model, genome_codes, chr_off, queries, tasks, ranges=None, tlen=None, exg=(0, 0), **want):
+    """spdp_hsp_tasks: the tasks through the device search under a plan (want: hash_slots, hit_cap, seg_cap, out_cap, n_waves; 0 or
+    absent = what find would choose).  Returns (per task its records as hsp_tasks_host gives them -- none for a flagged task --,
+    flags as an int32 array, the plan as launched)."""
+    c = _HspCall(model, genome_codes, chr_off, queries, tasks, ranges, tlen, exg)
+    w, used = HspPlan(**{k: int(v) for k, v in want.items()}), HspPlan()
+    flags = np.zeros(max(c.n_tasks, 1), dtype=np.int32)
+    eng.lib.spdp_hsp_tasks.restype = C.c_int
+    eng.lib.spdp_hsp_tasks.argtypes = [C.c_void_p] * 7
+    eng._check(eng.lib.spdp_hsp_tasks(eng.ctx, C.byref(c.rq), C.byref(w), C.byref(used), flags.ctypes.data, c.rec_off.ctypes.data,
+                                      C.byref(c.recs)), "spdp_hsp_tasks")
+    return c.records(), flags[:c.n_tasks], used.as_dict()
+
+
 def map_align(index: "BlockIndex", genome_codes, chr_off, sc, sp, sigmodel, prm: BlkFindParams, rescore, queries, ori: int = 1):
     """spdp_map_align_s: block search -> loci -> signals -> seeded alignment -> rescoring, one call for all queries.
     rescore = (codonk1, minl, jneibr, lsg).  Returns (per query None or dict(chr, rvs, score, val, n_loci,

@@ -13,14 +13,45 @@
 #include <cstring>
 #include <vector>
 
+// what the HSP searches read on the device besides a call's queries: the genome, the codon table, the matrix.  An index keeps one
+// across calls; spdp_hsp_tasks has one of its own for the call
+struct HspResident {
+    uint8_t* d_genome = nullptr; const uint8_t* genome_host = nullptr; int64_t genome_len = 0;
+    uint8_t* d_tron = nullptr; int32_t* d_mtx = nullptr;
+    ~HspResident()
+    {
+        if (d_genome) (void) hipFree(d_genome);
+        if (d_tron) (void) hipFree(d_tron);
+        if (d_mtx) (void) hipFree(d_mtx);
+    }
+    int ensure(SpdpContext* ctx, const SpdpGenome* genome, const SpdpWilipModel* model)
+    {
+        // the genome goes to the device once (the caller's array is the key: the same pointer and length again = resident)
+        const int64_t glen = genome->chr_off[genome->n_chr];
+        if (genome_host != genome->codes || genome_len != glen) {
+            if (d_genome) { (void) hipFree(d_genome); d_genome = nullptr; }
+            HIPCHK(hipMalloc((void**) &d_genome, (size_t) std::max<int64_t>(glen, 16)));
+            HIPCHK(hipMemcpy(d_genome, genome->codes, (size_t) glen, hipMemcpyHostToDevice));
+            genome_host = genome->codes; genome_len = glen;
+        }
+        if (!d_tron) {
+            uint8_t mid[32], tron_of[64];
+            spdp_genetic_code_tables(mid, tron_of);
+            HIPCHK(hipMalloc((void**) &d_tron, 64));
+            HIPCHK(hipMemcpy(d_tron, tron_of, 64, hipMemcpyHostToDevice));
+        }
+        if (!d_mtx) HIPCHK(hipMalloc((void**) &d_mtx, sizeof model->mtx));
+        HIPCHK(hipMemcpy(d_mtx, model->mtx, sizeof model->mtx, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
 struct SpdpBlkIndex {
     SpdpContext* ctx = nullptr;
     BlkDev dev;
     std::vector<void*> bufs;                    // device copies of the index arrays
     uint8_t* slabs = nullptr; uint32_t* next = nullptr;
-    // the genome, resident for the HSP searches (uploaded by the first spdp_blk_find that names it)
-    uint8_t* d_genome = nullptr; const uint8_t* genome_host = nullptr; int64_t genome_len = 0;
-    uint8_t* d_tron = nullptr; int32_t* d_mtx = nullptr;
+    HspResident hsp;                            // the genome, resident for the HSP searches (uploaded by the first spdp_blk_find that names it)
     BlkDev* d_dev = nullptr;                    // `dev` as the kernels read it
     size_t slab_bytes = 0;
     int n_waves = 0, hh_in_lds = 0;
@@ -30,9 +61,6 @@ struct SpdpBlkIndex {
         for (void* p : bufs) if (p) (void) hipFree(p);
         if (slabs) (void) hipFree(slabs);
         if (next) (void) hipFree(next);
-        if (d_genome) (void) hipFree(d_genome);
-        if (d_tron) (void) hipFree(d_tron);
-        if (d_mtx) (void) hipFree(d_mtx);
         if (d_dev) (void) hipFree(d_dev);
     }
 };
@@ -274,8 +302,53 @@ namespace {
 
 struct SearchTask { int machine, pair; spdp_loci::Region r; std::vector<spdp_hsp::Unit> units; };
 
+// ---- the LDS plan of a search launch (spdp_hsp_plan, include/spdp.h): one place for spdp_blk_find and spdp_hsp_tasks ----------------
+constexpr uint32_t HSP_LDS_BUDGET = 160u << 10;         // what a workgroup can have; the waves per CU follow from it
+
+bool pow2_from_64(int v) { return v >= 64 && (v & (v - 1)) == 0; }
+
+int hsp_plan(const SpdpHspPlan* want, int longest, int mtx_rows, int mtx_cols, int n_tasks, int n_cu, SpdpHspPlan* plan, std::string& why)
+{
+    SpdpHspPlan p;
+    memset(&p, 0, sizeof p);
+    if (want) { p.hash_slots = want->hash_slots; p.hit_cap = want->hit_cap; p.seg_cap = want->seg_cap; p.out_cap = want->out_cap; p.n_waves = want->n_waves; }
+    if (mtx_rows < 1 || mtx_cols < 1 || (int64_t) mtx_rows * mtx_cols > 32 * 32) { why = "spdp_hsp_plan: the matrix does not fit 32 x 32"; return -1; }
+    if (p.hash_slots < 0 || p.hit_cap < 0 || p.seg_cap < 0 || p.out_cap < 0 || p.n_waves < 0 || p.hash_slots > (1 << 17) || p.hit_cap > (1 << 24) || p.seg_cap > (1 << 13) || p.out_cap > (1 << 12) || p.n_waves > (1 << 16)) {
+        why = "spdp_hsp_plan: a cap out of range (hash_slots <= 2^17, hit_cap <= 2^24, seg_cap <= 8192, out_cap <= 4096, n_waves <= 65536, none negative)"; return -1;
+    }
+    // the wave's LDS: query words (twice their number, a power of two), shared words, segments -- sized for the batch's longest query,
+    // capped where one wave per CU is left; what does not fit comes back flagged
+    if (!p.hash_slots) {
+        int slots = 256;
+        while (slots < 2 * (int64_t) std::max(longest, 1) && slots < 8192) slots <<= 1;
+        p.hash_slots = slots;
+    } else if (!pow2_from_64(p.hash_slots)) { why = "spdp_hsp_plan: hash_slots is not a power of two of at least 64"; return -1; }
+    if (!p.hit_cap) {
+        p.hit_cap = p.hash_slots <= 1024 ? 4096 : 8192;
+        // the sort pads the list to the next power of two in place: any other size would let it write past the list
+        if (const char* e = getenv("SPDP_HSP_HITS")) {
+            const long v = std::min<long>(std::max<long>(256, atol(e)), 1l << 24);
+            int c = 256;
+            while (c < v) c <<= 1;
+            p.hit_cap = c;
+        }
+    } else if (!pow2_from_64(p.hit_cap)) { why = "spdp_hsp_plan: hit_cap is not a power of two of at least 64"; return -1; }
+    if (!p.seg_cap) p.seg_cap = 256;
+    if (!p.out_cap) p.out_cap = 96;
+    HspArgs A;
+    memset(&A, 0, sizeof A);
+    A.mtx_rows = mtx_rows; A.mtx_cols = mtx_cols; A.hash_slots = p.hash_slots; A.hit_cap = p.hit_cap; A.seg_cap = p.seg_cap;
+    const uint64_t lds = spdp_hsp_lds_bytes(&A);
+    if (lds > HSP_LDS_BUDGET) { why = "spdp_hsp_plan: the plan's LDS exceeds the 160 KB a wave can have (hash_slots / hit_cap / seg_cap / SPDP_HSP_HITS too large)"; return -1; }
+    p.lds_bytes = (int32_t) lds;
+    p.waves_per_cu = (int) std::max<uint32_t>(1, std::min<uint32_t>(8, HSP_LDS_BUDGET / std::max<uint32_t>((uint32_t) lds, 1)));
+    if (!p.n_waves) p.n_waves = (int) std::min<int64_t>(std::max(n_tasks, 1), (int64_t) std::max(1, n_cu) * p.waves_per_cu);
+    *plan = p;
+    return 0;
+}
+
 struct HspBatch {                                       // what a call's searches share
-    SpdpContext* ctx; SpdpBlkIndex* ix; const SpdpGenome* genome; const SpdpWilipModel* model; const SpdpScoring* sc;
+    SpdpContext* ctx; HspResident* res; const SpdpGenome* genome; const SpdpWilipModel* model; const SpdpScoring* sc;
     const spdp_loci::Params* P;
     const uint8_t* codes; const int64_t* offs; const int32_t* left; const int32_t* right;       // the call's queries (host)
     const int32_t* tlen;                                // per query Seq::tlen, or null: the queries' lengths
@@ -284,22 +357,7 @@ struct HspBatch {                                       // what a call's searche
 
     int prepare(int n)
     {
-        // the genome goes to the device once per index (the caller's array is the key: the same pointer and length again = resident)
-        const int64_t glen = genome->chr_off[genome->n_chr];
-        if (ix->genome_host != genome->codes || ix->genome_len != glen) {
-            if (ix->d_genome) { (void) hipFree(ix->d_genome); ix->d_genome = nullptr; }
-            HIPCHK(hipMalloc((void**) &ix->d_genome, (size_t) std::max<int64_t>(glen, 16)));
-            HIPCHK(hipMemcpy(ix->d_genome, genome->codes, (size_t) glen, hipMemcpyHostToDevice));
-            ix->genome_host = genome->codes; ix->genome_len = glen;
-        }
-        if (!ix->d_tron) {
-            uint8_t mid[32], tron_of[64];
-            spdp_genetic_code_tables(mid, tron_of);
-            HIPCHK(hipMalloc((void**) &ix->d_tron, 64));
-            HIPCHK(hipMemcpy(ix->d_tron, tron_of, 64, hipMemcpyHostToDevice));
-        }
-        if (!ix->d_mtx) HIPCHK(hipMalloc((void**) &ix->d_mtx, sizeof model->mtx));
-        HIPCHK(hipMemcpy(ix->d_mtx, model->mtx, sizeof model->mtx, hipMemcpyHostToDevice));
+        if (res->ensure(ctx, genome, model)) return -1;
         const size_t nb = (size_t) (offs[n] - offs[0]);
         HIPCHK(hipMalloc((void**) &d_codes, std::max<size_t>(nb, 16)));
         HIPCHK(hipMemcpy(d_codes, codes + offs[0], nb, hipMemcpyHostToDevice));
@@ -311,16 +369,63 @@ struct HspBatch {                                       // what a call's searche
         if (a_len < model->shortquery) vthr = vthr * a_len / model->shortquery;       // (as the search scaled it)
         return {model, sc->intpen, sc->intpen_len, sc->gop, sc->gep, sc->lgop, sc->lgep, sc->codonk1, P->bbt == 3 ? 3 : 1, vthr};
     }
+    HspTask task(int q, int chr, int base, int len, int rvs) const
+    {
+        HspTask T;
+        T.a_off = offs[q] - offs[0]; T.a_len = (int32_t) (offs[q + 1] - offs[q]); T.a_left = left[q]; T.a_right = right[q];
+        T.g_off = genome->chr_off[chr] + base; T.b_len = len; T.rvs = rvs;
+        T.a_exgl = P->a_exgl; T.a_exgr = P->a_exgr; T.a_tlen = tlen ? tlen[q] : T.a_len;
+        return T;
+    }
+    // the host's form of one search: its seeds and, of those above the threshold, the HSPs
+    void host_search(int q, const spdp_loci::Region& r, std::vector<uint8_t>& reg, spdp_hsp::Seqs& s) const
+    {
+        spdp_region::materialize(genome->codes, genome->chr_off, r.chr, r.base, r.len, r.rvs != 0, P->bbt == 3, reg);
+        const int a_len = (int) (offs[q + 1] - offs[q]);
+        s = {codes + offs[q], a_len, left[q], right[q], P->a_exgl, P->a_exgr, reg.data(), r.len, 0, r.len,
+             P->bbt == 3 ? 3 : 1, nullptr, nullptr, nullptr, tlen ? tlen[q] : -1};
+    }
     // the host's form, for a task the device hands back
     void on_host(SearchTask& t, int q) const
     {
         std::vector<uint8_t> reg;
-        spdp_region::materialize(genome->codes, genome->chr_off, t.r.chr, t.r.base, t.r.len, t.r.rvs != 0, P->bbt == 3, reg);
-        const int a_len = (int) (offs[q + 1] - offs[q]);
-        const spdp_hsp::Seqs s = {codes + offs[q], a_len, left[q], right[q], P->a_exgl, P->a_exgr, reg.data(), t.r.len, 0, t.r.len,
-                                  P->bbt == 3 ? 3 : 1, nullptr, nullptr, nullptr, tlen ? tlen[q] : -1};
+        spdp_hsp::Seqs s;
+        host_search(q, t.r, reg, s);
         const spdp_hsp::GapCosts gc = {sc->intpen, sc->intpen_len, sc->gop, sc->gep, sc->lgop, sc->lgep, sc->codonk1};
         spdp_hsp::search(model, s, gc, -1, t.units);
+    }
+    // the device search of a list of tasks under a plan: counts[2 k] records, [2 k + 1] flags; out: out_cap records of 8 ints per task
+    int device(const std::vector<HspTask>& ht, const SpdpHspPlan& plan, std::vector<int32_t>& counts, std::vector<int32_t>& out)
+    {
+        const int n = (int) ht.size();
+        HspArgs A;
+        memset(&A, 0, sizeof A);
+        A.codes = d_codes; A.genome = res->d_genome; A.n_tasks = n;
+        A.level = model->level[0];
+        A.mtx = res->d_mtx; A.mtx_rows = model->mtx_rows; A.mtx_cols = model->mtx_cols; A.tron_of = res->d_tron;
+        A.bbt = P->bbt == 3 ? 3 : 1; A.shortquery = model->shortquery; A.end_bonus = model->end_bonus; A.crs = model->crs;
+        A.ser = model->ser; A.ser2 = model->ser2;
+        A.hash_slots = plan.hash_slots; A.hit_cap = plan.hit_cap; A.seg_cap = plan.seg_cap; A.out_cap = plan.out_cap;
+        struct Dev { void* p = nullptr; ~Dev() { if (p) (void) hipFree(p); } } d_tasks, d_out, d_counts;
+        HIPCHK(hipMalloc(&d_tasks.p, sizeof(HspTask) * (size_t) n));
+        HIPCHK(hipMalloc(&d_out.p, sizeof(int32_t) * 8 * (size_t) A.out_cap * n));
+        HIPCHK(hipMalloc(&d_counts.p, sizeof(int32_t) * 2 * (size_t) n));
+        HIPCHK(hipMemcpyAsync(d_tasks.p, ht.data(), sizeof(HspTask) * (size_t) n, hipMemcpyHostToDevice, ctx->stream));
+        A.tasks = (const HspTask*) d_tasks.p; A.out = (int32_t*) d_out.p; A.counts = (int32_t*) d_counts.p;
+        HIPCHK(spdp_hsp_launch(&A, plan.n_waves, ctx->stream));
+        counts.resize(2 * (size_t) n); out.resize(8 * (size_t) A.out_cap * n);
+        HIPCHK(hipMemcpyAsync(counts.data(), d_counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out.data(), d_out.p, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+    struct Rec { int v[8]; };
+    // task k's records in scan order: diagonal, position
+    static void in_scan_order(const std::vector<int32_t>& counts, const std::vector<int32_t>& out, int out_cap, int k, std::vector<Rec>& recs)
+    {
+        const Rec* r = (const Rec*) (out.data() + 8 * (size_t) out_cap * k);
+        recs.assign(r, r + counts[2 * k]);
+        std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.v[5] != y.v[5] ? x.v[5] < y.v[5] : x.v[6] < y.v[6]; });
     }
     // all tasks: device search, then the chains on the host threads.  query_of[machine] = the query
     int run(std::vector<SearchTask>& tasks, const std::vector<int>& query_of)
@@ -330,48 +435,24 @@ struct HspBatch {                                       // what a call's searche
         std::vector<HspTask> ht(n);
         int longest = 1;
         for (int k = 0; k < n; ++k) {
-            const int q = query_of[tasks[k].machine];
-            HspTask& T = ht[k];
-            T.a_off = offs[q] - offs[0]; T.a_len = (int32_t) (offs[q + 1] - offs[q]); T.a_left = left[q]; T.a_right = right[q];
-            T.g_off = genome->chr_off[tasks[k].r.chr] + tasks[k].r.base; T.b_len = tasks[k].r.len; T.rvs = tasks[k].r.rvs;
-            T.a_exgl = P->a_exgl; T.a_exgr = P->a_exgr; T.a_tlen = tlen ? tlen[q] : T.a_len;
-            longest = std::max(longest, T.a_right - T.a_left);
+            ht[k] = task(query_of[tasks[k].machine], tasks[k].r.chr, tasks[k].r.base, tasks[k].r.len, tasks[k].r.rvs);
+            longest = std::max(longest, ht[k].a_right - ht[k].a_left);
         }
-        HspArgs A;
-        memset(&A, 0, sizeof A);
-        A.codes = d_codes; A.genome = ix->d_genome; A.n_tasks = n;
-        A.level = model->level[0];
-        A.mtx = ix->d_mtx; A.mtx_rows = model->mtx_rows; A.mtx_cols = model->mtx_cols; A.tron_of = ix->d_tron;
-        A.bbt = P->bbt == 3 ? 3 : 1; A.shortquery = model->shortquery; A.end_bonus = model->end_bonus; A.crs = model->crs;
-        A.ser = model->ser; A.ser2 = model->ser2;
-        // the wave's LDS: query words (twice their number, a power of two), shared words, segments -- sized for the batch's longest query,
-        // capped where one wave per CU is left; what does not fit comes back flagged
-        int slots = 256;
-        while (slots < 2 * longest && slots < 8192) slots <<= 1;
-        A.hash_slots = slots; A.hit_cap = slots <= 1024 ? 4096 : 8192; A.seg_cap = 256; A.out_cap = 96;
-        if (const char* e = getenv("SPDP_HSP_HITS")) A.hit_cap = std::max(256, atoi(e));
-        const uint32_t lds = spdp_hsp_lds_bytes(&A);
-        struct Dev { void* p = nullptr; ~Dev() { if (p) (void) hipFree(p); } } d_tasks, d_out, d_counts;
-        HIPCHK(hipMalloc(&d_tasks.p, sizeof(HspTask) * (size_t) n));
-        HIPCHK(hipMalloc(&d_out.p, sizeof(int32_t) * 8 * (size_t) A.out_cap * n));
-        HIPCHK(hipMalloc(&d_counts.p, sizeof(int32_t) * 2 * (size_t) n));
-        HIPCHK(hipMemcpyAsync(d_tasks.p, ht.data(), sizeof(HspTask) * (size_t) n, hipMemcpyHostToDevice, ctx->stream));
-        A.tasks = (const HspTask*) d_tasks.p; A.out = (int32_t*) d_out.p; A.counts = (int32_t*) d_counts.p;
-        const int per_cu = (int) std::max<uint32_t>(1, std::min<uint32_t>(8, (160u << 10) / std::max<uint32_t>(lds, 1)));
-        const int waves = std::min(n, std::max(1, ctx->n_cu) * per_cu);
-        HIPCHK(spdp_hsp_launch(&A, waves, ctx->stream));
-        std::vector<int32_t> counts(2 * (size_t) n), out(8 * (size_t) A.out_cap * n);
-        HIPCHK(hipMemcpyAsync(counts.data(), d_counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(out.data(), d_out.p, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        SpdpHspPlan plan;
+        std::string why;
+        if (hsp_plan(nullptr, longest, model->mtx_rows, model->mtx_cols, n, ctx->n_cu, &plan, why)) { ctx->err = why; return -1; }
+        std::vector<int32_t> counts, out;
+        if (device(ht, plan, counts, out)) return -1;
+        int64_t too_long = 0, too_many = 0;
+        for (int k = 0; k < n; ++k) { const int f = counts[2 * k + 1]; if (f & HSP_TOO_LONG) ++too_long; else if (f) ++too_many; }
+        ctx->hsp_stats[0] += n; ctx->hsp_stats[1] += n - too_long - too_many; ctx->hsp_stats[2] += too_long; ctx->hsp_stats[3] += too_many;
+        ctx->hsp_stats[5] += 1;
         on_host_threads(n, [&](int k) {
             SearchTask& t = tasks[k];
             const int q = query_of[t.machine];
             if (counts[2 * k + 1]) { on_host(t, q); return; }
-            struct Rec { int v[8]; };
-            const Rec* r = (const Rec*) (out.data() + 8 * (size_t) A.out_cap * k);
-            std::vector<Rec> recs(r, r + counts[2 * k]);
-            std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.v[5] != y.v[5] ? x.v[5] < y.v[5] : x.v[6] < y.v[6]; });    // scan order: diagonal, position
+            std::vector<Rec> recs;
+            in_scan_order(counts, out, plan.out_cap, k, recs);
             std::vector<spdp_hsp::Hsp> hsps;
             for (const Rec& x : recs) hsps.push_back({x.v[0], x.v[1], x.v[2], x.v[3], x.v[4]});
             spdp_hsp::chain(hsps, cost(ht[k].a_len), left[q], right[q], 0, t.r.len, t.units);
@@ -399,7 +480,7 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
     const spdp_loci::Chromosomes G = {genome->chr_off, genome->n_chr, hix->chr};
     const spdp_loci::RandomScore rnd = {hix->rscrtab, hix->rbscoef, hix->rbscons, hix->gdb};
     (void) hipSetDevice(ctx->device);
-    HspBatch B = {ctx, ix, genome, model, sc, &P, codes, offs, left, right, tlen};
+    HspBatch B = {ctx, &ix->hsp, genome, model, sc, &P, codes, offs, left, right, tlen};
     if (B.prepare(n)) return -1;
     int out_cap = 4096;                                 // (a record that does not fit makes the round run again with room for it)
     const bool verbose = getenv("SPDP_FIND_VERBOSE") != nullptr;
@@ -486,7 +567,7 @@ static int blk_find(SpdpContext* ctx, const SpdpBlkIndex* cix, const SpdpBlkInde
                     c.take(u);
                 }
             });
-            for (int k = 0; k < m; ++k) if (asks[k]) tasks.push_back(std::move(more[k]));
+            for (int k = 0; k < m; ++k) if (asks[k]) { tasks.push_back(std::move(more[k])); ++ctx->hsp_stats[4]; }
             t_advance += secs(t4, now());
         }
         std::vector<int> again;
@@ -540,6 +621,7 @@ int spdp_blk_find_tlen(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIn
     }
     if ((model->dvsp == 0) != (hix->drna != 0)) { ctx->err = "spdp_blk_find: the block table is incompatible with the query type (src/blksrc.cc:2186)"; return -1; }
     if (ix->ctx != ctx) { ctx->err = "spdp_blk_find: the index belongs to another context"; return -1; }
+    memset(ctx->hsp_stats, 0, sizeof ctx->hsp_stats);
     try { return blk_find(ctx, ix, hix, genome, model, sc, prm, codes, offs, left, right, tlen, n, loci, n_loci, hsps, status); }
     catch (...) {                                       // (nothing of C++ crosses the C boundary; the worker threads have been joined)
         if (*loci) { free(*loci); *loci = nullptr; }
@@ -556,4 +638,153 @@ extern "C" int spdp_blk_find(SpdpContext* ctx, const SpdpBlkIndex* ix, const Spd
                              SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status)
 {
     return spdp_blk_find_tlen(ctx, ix, hix, genome, model, sc, prm, codes, offs, left, right, nullptr, n, loci, n_loci, hsps, status);
+}
+
+extern "C" int spdp_blk_find_stats(const SpdpContext* ctx, int64_t* out, int n)
+{
+    if (!ctx || !out) return -1;
+    for (int i = 0; i < n && i < 8; ++i) out[i] = ctx->hsp_stats[i];
+    return 0;
+}
+
+// ---- the HSP search by itself (include/spdp.h): the product's device step and host form on tasks the caller names -----------------
+namespace {
+
+void say(char* err, int err_len, const std::string& why)
+{
+    if (err && err_len > 0) { strncpy(err, why.c_str(), (size_t) err_len - 1); err[err_len - 1] = 0; }
+}
+
+// everything the two forms later use as an index, checked once; -> the longest query range
+int hsp_request_ok(const SpdpHspRequest* rq, int& longest, std::string& why)
+{
+    if (!rq || !rq->model || !rq->genome || !rq->genome->codes || !rq->genome->chr_off || !rq->codes || !rq->offs || !rq->left || !rq->right ||
+        (!rq->tasks && rq->n_tasks > 0) || rq->n_queries < 0 || rq->n_tasks < 0 || rq->genome->n_chr < 1) { why = "spdp_hsp_tasks: null argument"; return -1; }
+    const SpdpWilipModel* m = rq->model;
+    const SpdpWilipLevel& L = m->level[0];
+    const int bbt = m->dvsp == 1 ? 3 : 1;
+    if (L.width < 1 || L.width > 32 || L.elem < 1 || L.tpl < 1 || m->shortquery < 1) { why = "spdp_hsp_tasks: level 0 of the model out of range (width 1 .. 32, elem, tpl, shortquery >= 1)"; return -1; }
+    if (L.bitpat_len != 0 && L.bitpat_len != L.width) { why = "spdp_hsp_tasks: the spaced pattern's length differs from width"; return -1; }
+    if (m->mtx_rows < 1 || m->mtx_cols < 1 || (int64_t) m->mtx_rows * m->mtx_cols > 32 * 32 || m->mtx_cols < (bbt == 3 ? 26 : 17)) {
+        why = "spdp_hsp_tasks: the matrix has no column for every genomic code (17 nucleotide codes, 26 tron codes; at most 32 x 32)"; return -1;
+    }
+    longest = 1;
+    for (int q = 0; q < rq->n_queries; ++q) {
+        const int64_t len = rq->offs[q + 1] - rq->offs[q];
+        if (len < 0 || len > INT32_MAX) { why = "spdp_hsp_tasks: offs do not ascend"; return -1; }
+        if (rq->left[q] < 0 || rq->right[q] > len || rq->right[q] < rq->left[q] || (rq->tlen && (rq->tlen[q] < 0 || rq->tlen[q] > len))) {
+            why = "spdp_hsp_tasks: left / right / tlen outside the query"; return -1;
+        }
+        for (int64_t i = rq->offs[q]; i < rq->offs[q + 1]; ++i)
+            if (rq->codes[i] >= m->mtx_rows) { why = "spdp_hsp_tasks: a query code at or above mtx_rows"; return -1; }
+    }
+    for (int c = 0; c < rq->genome->n_chr; ++c)
+        if (rq->genome->chr_off[c + 1] < rq->genome->chr_off[c] || rq->genome->chr_off[0] < 0) { why = "spdp_hsp_tasks: chr_off does not ascend"; return -1; }
+    for (int k = 0; k < rq->n_tasks; ++k) {
+        const SpdpHspTask& t = rq->tasks[k];
+        if (t.query < 0 || t.query >= rq->n_queries || t.chr < 0 || t.chr >= rq->genome->n_chr || (t.rvs != 0 && t.rvs != 1)) { why = "spdp_hsp_tasks: a task names no query / chromosome / strand"; return -1; }
+        const int64_t clen = rq->genome->chr_off[t.chr + 1] - rq->genome->chr_off[t.chr];
+        if (t.base < 0 || t.len < 0 || (int64_t) t.base + t.len > clen) { why = "spdp_hsp_tasks: a region lies outside its chromosome"; return -1; }
+        longest = std::max(longest, rq->right[t.query] - rq->left[t.query]);
+    }
+    return 0;
+}
+
+spdp_loci::Params hsp_params(const SpdpHspRequest* rq)
+{
+    spdp_loci::Params P{};
+    P.bbt = rq->model->dvsp == 1 ? 3 : 1; P.dvsp = rq->model->dvsp; P.a_exgl = rq->a_exgl; P.a_exgr = rq->a_exgr;
+    return P;
+}
+
+int hsp_hand_out(const std::vector<std::vector<int32_t>>& per_task, int64_t* rec_off, int32_t** recs)
+{
+    rec_off[0] = 0;
+    for (size_t k = 0; k < per_task.size(); ++k) rec_off[k + 1] = rec_off[k] + (int64_t) per_task[k].size() / 7;
+    *recs = (int32_t*) malloc(sizeof(int32_t) * std::max<size_t>(7 * (size_t) rec_off[per_task.size()], 1));
+    if (!*recs) return -1;
+    for (size_t k = 0; k < per_task.size(); ++k)
+        if (!per_task[k].empty()) memcpy(*recs + 7 * rec_off[k], per_task[k].data(), sizeof(int32_t) * per_task[k].size());
+    return 0;
+}
+
+}   // namespace
+
+extern "C" int spdp_hsp_plan(const SpdpHspPlan* want, int32_t longest, int32_t mtx_rows, int32_t mtx_cols, int32_t n_tasks, int32_t n_cu,
+                             SpdpHspPlan* plan, char* err, int32_t err_len)
+{
+    std::string why;
+    if (!plan) { say(err, err_len, "spdp_hsp_plan: null argument"); return -1; }
+    if (hsp_plan(want, longest, mtx_rows, mtx_cols, n_tasks, n_cu, plan, why)) { say(err, err_len, why); return -1; }
+    return 0;
+}
+
+extern "C" int spdp_hsp_tasks(SpdpContext* ctx, const SpdpHspRequest* rq, const SpdpHspPlan* want, SpdpHspPlan* used,
+                              int32_t* flags, int64_t* rec_off, int32_t** recs)
+{
+    if (!ctx) return -1;
+    if (!flags || !rec_off || !recs) { ctx->err = "spdp_hsp_tasks: null argument"; return -1; }
+    *recs = nullptr;
+    int longest = 1;
+    std::string why;
+    if (hsp_request_ok(rq, longest, why)) { ctx->err = why; return -1; }
+    SpdpHspPlan plan;
+    if (hsp_plan(want, longest, rq->model->mtx_rows, rq->model->mtx_cols, rq->n_tasks, ctx->n_cu, &plan, why)) { ctx->err = why; return -1; }
+    if (used) *used = plan;
+    const int n = rq->n_tasks;
+    try {
+        std::vector<std::vector<int32_t>> per_task((size_t) n);
+        if (n) {
+            (void) hipSetDevice(ctx->device);
+            const spdp_loci::Params P = hsp_params(rq);
+            HspResident res;
+            HspBatch B = {ctx, &res, rq->genome, rq->model, nullptr, &P, rq->codes, rq->offs, rq->left, rq->right, rq->tlen};
+            if (B.prepare(rq->n_queries)) return -1;
+            std::vector<HspTask> ht((size_t) n);
+            for (int k = 0; k < n; ++k) { const SpdpHspTask& t = rq->tasks[k]; ht[k] = B.task(t.query, t.chr, t.base, t.len, t.rvs); }
+            std::vector<int32_t> counts, out;
+            if (B.device(ht, plan, counts, out)) return -1;
+            std::vector<HspBatch::Rec> r;
+            for (int k = 0; k < n; ++k) {
+                flags[k] = counts[2 * k + 1];
+                if (flags[k]) continue;
+                HspBatch::in_scan_order(counts, out, plan.out_cap, k, r);
+                for (const HspBatch::Rec& x : r) per_task[k].insert(per_task[k].end(), x.v, x.v + 7);
+            }
+        }
+        if (hsp_hand_out(per_task, rec_off, recs)) { ctx->err = "spdp_hsp_tasks: out of memory"; return -1; }
+    } catch (...) { ctx->err = "spdp_hsp_tasks: out of host memory"; return -1; }
+    return 0;
+}
+
+extern "C" int spdp_hsp_tasks_host(const SpdpHspRequest* rq, int32_t* counts, int64_t* rec_off, int32_t** recs, char* err, int32_t err_len)
+{
+    if (!counts || !rec_off || !recs) { say(err, err_len, "spdp_hsp_tasks: null argument"); return -1; }
+    *recs = nullptr;
+    int longest = 1;
+    std::string why;
+    if (hsp_request_ok(rq, longest, why)) { say(err, err_len, why); return -1; }
+    try {
+        const spdp_loci::Params P = hsp_params(rq);
+        const HspBatch B = {nullptr, nullptr, rq->genome, rq->model, nullptr, &P, rq->codes, rq->offs, rq->left, rq->right, rq->tlen};
+        std::vector<std::vector<int32_t>> per_task((size_t) rq->n_tasks);
+        std::vector<uint8_t> reg;
+        std::vector<spdp_hsp::Search::Seed> seeds;
+        for (int k = 0; k < rq->n_tasks; ++k) {
+            const SpdpHspTask& t = rq->tasks[k];
+            spdp_hsp::Seqs s;
+            B.host_search(t.query, spdp_loci::Region{t.chr, t.rvs, t.base, t.len}, reg, s);
+            const spdp_hsp::Search S(rq->model, &s, -1);
+            size_t words = 0;
+            seeds.clear();
+            if (S.usable) S.seeds(seeds, &words);
+            for (const spdp_hsp::Search::Seed& sd : seeds) {            // (already in scan order: diagonal, first word)
+                spdp_hsp::Hsp h;
+                if (S.stretch_and_trim(sd, h)) { const int32_t v[7] = {h.jx, h.jy, h.jlen, h.nid, h.jscr, sd.diag, sd.first}; per_task[k].insert(per_task[k].end(), v, v + 7); }
+            }
+            counts[3 * k] = (int32_t) std::min<size_t>(words, INT32_MAX); counts[3 * k + 1] = (int32_t) seeds.size(); counts[3 * k + 2] = (int32_t) (per_task[k].size() / 7);
+        }
+        if (hsp_hand_out(per_task, rec_off, recs)) { say(err, err_len, "spdp_hsp_tasks: out of memory"); return -1; }
+    } catch (...) { say(err, err_len, "spdp_hsp_tasks: out of host memory"); return -1; }
+    return 0;
 }

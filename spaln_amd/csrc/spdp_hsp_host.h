@@ -58,8 +58,8 @@ struct Search {
     }
 
     struct Seed { int first, diag, last, score; };      // a seed segment: words first .. last of the query on one diagonal
-    // ---- the words both sides share, by diagonal; every diagonal scored
-    void seeds(std::vector<Seed>& out) const
+    // ---- the words both sides share, by diagonal; every diagonal scored.  n_shared (optional): how many words were shared
+    void seeds(std::vector<Seed>& out, size_t* n_shared = nullptr) const
     {
         const int nk = mm - (L.width - 1);
         const int span_b = bbt == 3 ? 3 * L.width - 1 : L.width - 1;
@@ -76,6 +76,7 @@ struct Search {
                 shared.push_back((uint64_t) (n - (int64_t) bbt * it->second + bias) << 32 | (uint32_t) it->second);
         }
         std::sort(shared.begin(), shared.end());
+        if (n_shared) *n_shared = shared.size();
         const int tplwt = L.tpl * L.gain;
         for (size_t i = 0; i < shared.size(); ) {
             const uint64_t dkey = shared[i] >> 32;

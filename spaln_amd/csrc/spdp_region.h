@@ -37,8 +37,10 @@ inline void to_tron(uint8_t* s, int len)
 inline void materialize_into(const uint8_t* genome, const int64_t* chr_off, int chr, int base, int len, bool rvs, bool tron, uint8_t* dst)
 {
     const uint8_t* src = genome + chr_off[chr] + base;
-    if (!rvs) memcpy(dst, src, (size_t) len);
-    else for (int i = 0; i < len; ++i) dst[i] = other_strand(src[len - 1 - i]);
+    // codes beyond the alphabet read as N (16) on both strands, as the device form reads them (Region::nuc, spdp_hsp.hip): what follows
+    // indexes convtab and the matrix with them
+    if (!rvs) for (int i = 0; i < len; ++i) dst[i] = src[i] > 16 ? 16 : src[i];
+    else for (int i = 0; i < len; ++i) dst[i] = other_strand(src[len - 1 - i] > 16 ? 16 : src[len - 1 - i]);
     dst[len] = 0;
     if (tron) to_tron(dst, len);
 }

@@ -40,6 +40,7 @@ EXPORTS = [
     "spdp_align_b", "spdp_homscore_b", "spdp_skl_rng_b", "spdp_skl_edits_b", "spdp_cells_b", "spdp_trace_bytes_b",
     "spdp_align_b_seeded", "spdp_seeded_stats_b", "spdp_align_b_seeded_refusal", "spdp_lsp_b",
     "spdp_signal_records_s", "spdp_signal_records_h",
+    "spdp_blk_find_stats", "spdp_hsp_plan", "spdp_hsp_tasks", "spdp_hsp_tasks_host",
 ]
 
 

@@ -27,6 +27,20 @@ def test_library_exports_all_declared_symbols():
     for name in ("spdp_signal_records_s", "spdp_signal_records_h"):
         assert name in _declared() and name in engine.EXPORTS and hasattr(lib, name)
     assert hasattr(engine.Engine, "signal_records_s") and hasattr(engine.Engine, "signal_records_h")
+    # the HSP search's request path and the block search's counters (tests/test_hsp_cases.py, tests/test_gpu_hsp_cases.py)
+    from spaln_amd import blocks
+    for name, wrapper in (("spdp_hsp_plan", "hsp_plan"), ("spdp_hsp_tasks", "hsp_tasks"), ("spdp_hsp_tasks_host", "hsp_tasks_host"), ("spdp_blk_find_stats", "find_stats")):
+        assert name in _declared() and name in engine.EXPORTS and hasattr(lib, name) and hasattr(blocks, wrapper)
+
+
+def test_hsp_entries_refuse_null_arguments():
+    """without a device: the device entry and the counters can only refuse, the host entries say why"""
+    lib = engine.load_library()
+    assert lib.spdp_hsp_tasks(None, None, None, None, None, None, None) == -1
+    assert lib.spdp_blk_find_stats(None, None, 0) == -1
+    err = C.create_string_buffer(128)
+    assert lib.spdp_hsp_tasks_host(None, None, None, None, err, 128) == -1 and b"null argument" in err.value
+    assert lib.spdp_hsp_plan(None, 1, 17, 17, 1, 1, None, err, 128) == -1 and b"null argument" in err.value
 
 
 def test_signal_records_refuse_a_null_context():

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from spaln_amd import abi, blocks, defaults
-from tests import spdg
+from tests import envknobs, spdg
 from tests.conftest import golden_files
 from oracle import blk
 from tests.test_blk_find import CASES, PROTEIN_CASES, PROTEIN_NAMES, genome_of, parse_find
@@ -83,6 +83,24 @@ def test_random_queries_device_path_equals_host_path(eng, name, n_genes, seed, p
         b[hits] = rng.choice(letters, size=int(hits.sum()))
         queries.append(np.ascontiguousarray(b))
     got, status = blocks.find(dix, gen, off, model, sc, prm, queries)
+    # who served the HSP searches: the device at least once, and every task either there or handed back to the host form
+    stats = blocks.find_stats(eng)
+    assert stats["device"] >= 1 and stats["tasks"] >= len(queries) // 2, stats
+    assert stats["device"] + stats["too_long"] + stats["too_many"] == stats["tasks"], stats
+    # with room for 256 shared words only, strictly more tasks come back and the host form gives the same loci
+    with envknobs.Env(SPDP_HSP_HITS=256):
+        got_small, status_small = blocks.find(dix, gen, off, model, sc, prm, queries)
+    small = blocks.find_stats(eng)
+    # (blk_iupacp: measured, no search of its 837 shares more than 256 words -- nothing can come back; its protein words are rare)
+    assert small["too_many"] > stats["too_many"] or (name == "blk_iupacp" and small["too_many"] == stats["too_many"] == 0), (stats, small)
+    assert small["too_long"] == stats["too_long"] and small["tasks"] == stats["tasks"], (stats, small)
+    assert small["device"] + small["too_long"] + small["too_many"] == small["tasks"], small
+    assert status_small.tolist() == status.tolist()
+    for a, b in zip(got, got_small):
+        assert [{k: (v.tolist() if k == "hsps" else v) for k, v in d.items()} for d in a] == [{k: (v.tolist() if k == "hsps" else v) for k, v in d.items()} for d in b]
+    print("\n%s: HSP search tasks %d, served on the device %d, handed back %d too long + %d too many (%.2f %%), retries %d, batches %d; with SPDP_HSP_HITS=256: %d too many"
+          % (name, stats["tasks"], stats["device"], stats["too_long"], stats["too_many"], 100. * (stats["too_long"] + stats["too_many"]) / stats["tasks"],
+             stats["retries"], stats["batches"], small["too_many"]))
     lib = C.CDLL(oracle._BLK_SO)
     prm_i = np.ascontiguousarray(fx["find_prm"], dtype=np.int32)
     ip = np.ascontiguousarray(fx["find_intpen"], dtype=np.int16)
