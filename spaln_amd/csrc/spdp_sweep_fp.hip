@@ -85,7 +85,10 @@ template <bool B> struct BoolTag { static constexpr bool value = B; };
 // ---------------------------------------------------------------------------
 // WPB / CROSS / work mapping / progress words: exactly as spdp_sweep (spdp_kernels.hip).
 // SPJ: splice signals on (PwdB::DvsP != 0): with it off there is no donor / acceptor state at all.
-// A 4-wave block of one CU asks for five waves per SIMD: <= 32 KB of LDS and <= 96 VGPRs.
+// A 4-wave block of one CU asks for five waves per SIMD: <= 96 VGPRs, and LDS well below a fifth of the CU's 160 KB:
+// at 32 592 B (163 840 / 5 = 32 768) the UDH form still ran four blocks per CU, at 26 448 B it runs five; the
+// occupancy query of the runtime says five for both (profiles/rows2_c2.txt).  The forward and
+// score-only forms keep their 30 416 B and with them five blocks: at 24 272 B six are resident and C4 loses 7 %.
 // SIG: the instantiation a gated launch of the chunk pipeline runs (SweepArgs::started); every other launch runs the kernel
 // without the entry block, whose few instructions cost the SPJ form five spilled registers in its pass loop
 template <int FL, int WPB, bool CROSS, bool SPJ, bool SIG = false>
@@ -105,15 +108,22 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
     //  * column records as two rings (signals 8 B, matrix column offset 4 B) instead of one 16-byte record: the 16
     //    lanes of a row read 16 consecutive slots = 32 (16) consecutive banks; all rows of a wave are at the same
     //    ring position (their lag, 4 blocks, is a multiple of the 2-block ring), and the rings of consecutive rows
-    //    lie RS = 80 slots apart (160 dwords = 32 mod 64 banks for the 8-byte reads, 80 = 16 mod 32 for the 4-byte
-    //    ones): the two rows of a 32-lane half read the two halves of the banks;
+    //    lie RS slots apart, 48 in the UDH form and 80 in the others (96 dwords = 160 = 32 mod 64 banks for the 8-byte
+    //    reads, 48 = 80 = 16 mod 32 for the 4-byte ones): the two rows of a 32-lane half read the two halves of the banks.
+    //    48 slots are what is touched: a lane reads slots myslot .. myslot + 15 with myslot <= 31, i.e. 0 .. 46, and
+    //    the second copy of a record (slot + 32) is read only out of the odd blocks (lbm == 16, slot = k: 32 .. 47);
+    //    in an even block it would lie at 48 + k, nothing reads it, and with 48 slots it is not written (lbm is a
+    //    scalar: a branch).  The other forms keep the 80 slots they had, not for the slots but for the bytes: with
+    //    48 their 4-wave blocks take 24 272 B, six of them are resident per CU instead of five, and the C4 step,
+    //    which is its forward sweeps, goes from 47.3 to 50.7 ms (profiles/rows2_c2.txt);
     //  * the feed of a row is padded by one entry, so the entries the rows of a wave broadcast in one
     //    instruction lie in different banks.
-    constexpr int RS = 80;
+    constexpr int RS = UDH ? 48 : 80;
+    static_assert(RS >= 32 + 16 && (2 * RS) % 64 == 32 && RS % 32 == 16, "ring stride: every slot read exists, bank geometry as described");
     __shared__ float  s_mtx[32 * 36];
     __shared__ int    s_perm[32];
     __shared__ float2 s_pen[SPDP_FPEN_LEAD + SPDP_FPEN_TAB + SPDP_FPEN_PAD];
-    // per wave, per DPP row: 2 x 32-slot rings of column records (each record written twice, 32 slots apart: the
+    // per wave, per DPP row: 2 x 32-slot rings of column records (an odd block's records written twice, 32 slots apart: the
     // 31-column window of a block is contiguous) and the 16 boundary entries of the block
     __shared__ float2 s_sig[WPB][4][RS];                // {sig5 + ipen, sig3}
     __shared__ int    s_bof[WPB][4][RS];                // byte offset of the base's matrix column
@@ -433,8 +443,14 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WPB ==
                         const float2 srec = make_float2((float) (short) sg, (float) (sg >> 16));
                         const int bof = s_perm[bs & 31] * 4;
                         const int slot = (lbm + k + 16) & 31;                    // (16 lb + k + 16) mod 32
-                        if constexpr (SPJ) { sigring[slot] = srec; sigring[slot + 32] = srec; }
-                        bofring[slot] = bof; bofring[slot + 32] = bof;
+                        if constexpr (SPJ) sigring[slot] = srec;
+                        bofring[slot] = bof;
+                        // the copy 32 slots on: read by lanes k > 0 of an odd block (slots 32 - k .. 47 - k), whose slot is k;
+                        // an even block's (slot 16 + k) would lie behind a ring of 48 slots
+                        if (RS >= 64 || lbm) {
+                            if constexpr (SPJ) sigring[slot + 32] = srec;
+                            bofring[slot + 32] = bof;
+                        }
                     }
                     // ---- ... and the next block's loads are issued now, to land while this one computes
                     if (lb + 1 < nb) prefetch(lb + 1);
