@@ -882,6 +882,49 @@ int spdp_blk_vote_resident(SpdpContext* ctx, const SpdpBlkIndex* ix, const uint8
                            const int32_t* d_left, const int32_t* d_right, const int32_t* d_stop_at, int32_t n,
                            int32_t* d_out, int32_t out_cap, float* kernel_ms);
 
+/* ---- protein database search: the vote of SrchBlk::finds (protein queries against the amino-acid index of a protein database,
+ * `spaln -W -KA`; QRYvsDB == AvsA) -----------------------------------------------------------------------------------------------
+ * Replaces SrchBlk::finds (src/blksrc.cc:3271-3362) with init2 (:1925-1938), Bhit2 (:3147-3179), Randbs::randbs / lencor / base
+ * (:2047-2069, src/blksrc.h:459-461), setSegLen (:1966-1983), findChrNo (:1985-2002) and the one-argument Qwords::querywords
+ * (:2836-2878): the words of a query are looked up from both ends inwards (two directions x Nshift phases per round), every
+ * (round, direction, phase) starts a fresh run of continuous hits, a block's score rscr accumulates over all runs and rounds, a
+ * block enters the Ncand heap when rscr >= randbs(nmmc) + lencor(SegLen[blk]).  One query per wave (spdp_blk_finds.hip).  The
+ * index is the one spdp_blk_index_read makes of <db>.bka with SpdpBlkSearchOpts.genomic_db = 0 (the program's defaults there:
+ * rbs_fact = 0 and rbs_base = 0.5, Randbs' cross-species constants RbsFactSqrX / RbsBaseX, :65-67, 2053-2057 -- algmode.crs is
+ * set unless -yX0, which gives rbs_fact = 0.606, rbs_base = 3) and max_out = OutPrm.MaxOut; hix its host description.
+ *
+ * SpdpBlkFindsParams: what SrchBlk::initialize derives with gnmdb = false that the descriptor does not hold
+ * (spdp_blk_finds_params_default fills it from a read index). */
+typedef struct SpdpBlkFindsParams {
+    int32_t max_out;                 /* OutPrm.MaxOut: the candidates handed on (the index has Ncand = max_out + 10)         */
+    int32_t local;                   /* algmode.lcl & 16: maxmmc = INT_MAX, the scan ends where its two directions meet      */
+    float   rln_coef;                /* Randbs::RlnCoef = RlnFact x avr x Nbitpat, avr = AvrScr x weight / Nshift (:2058)    */
+    int32_t ptpl;                    /* SrchBlk::ptpl = base() / AvrScr (:2211)                                              */
+    int32_t avrscr;                  /* pbwc->AvrScr, for the record (not read by the vote)                                  */
+    int32_t reserved[3];
+} SpdpBlkFindsParams;
+int spdp_blk_finds_params_default(const SpdpBlkIndexHost* h, int32_t max_out, int32_t local, SpdpBlkFindsParams* p);   /* -1: null / no AvrScr */
+/* n protein queries (codes / offs / left / right as spdp_blk_vote).  out: n records of out_cap ints each: [0] ints used, [1] the
+ * round nmmc the scan ended in, [2] flags (SPDP_BLK_REACHED: the query was searched and the record follows; SPDP_BLK_SHORT: the
+ * range is shorter than Nshift + width + 1 (or longer than 65535), finds returns ERROR and nothing follows; SPDP_BLK_CUT: out_cap
+ * too small; SPDP_BLK_TABLE: the index is malformed -- a posting list outside blkb, a block number not below nseg, a run hash that
+ * ran full), [3] [4] testword[2], [5] sigm, (block, score) x sigm: the heap in hsort order (score: rscr when the block last entered
+ * or rose), n_cand = min(max_out, sigm) and the candidate sequences in the order finds fills sqs[1..] (findChrNo of each block;
+ * -1 - c for a sequence met before, whose slot keeps what it held: the shash rule, :3353-3354).  sigm = 0: finds returns ERROR.
+ * Refused by name: a null argument, a nucleotide index, an index read for a genomic database, Ncand != max_out + 10, a database
+ * of more than 2^24 blocks (what holds rscr: DESIGN.md 5b), out_cap < 6, a bad range.  kernel_ms (may be NULL): HIP-event time.
+ * The run hash of a wave lives in LDS when its reference-sized table takes at most 24 KB, else in the wave's slab of HBM;
+ * SPDP_FINDS_HH_LDS=0 in the environment when an index is first searched puts it in the slab whatever its size (the records do
+ * not depend on it: tests/test_gpu_finds_cases.py). */
+#define SPDP_BLK_SHORT   16
+int spdp_blk_finds(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpBlkFindsParams* prm,
+                   const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                   int32_t* out, int32_t out_cap, float* kernel_ms);
+/* the same with queries and records resident on the device (d_* are device pointers), for timing */
+int spdp_blk_finds_resident(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpBlkFindsParams* prm,
+                            const uint8_t* d_codes, const int64_t* d_offs, const int32_t* d_left, const int32_t* d_right, int32_t n,
+                            int32_t* d_out, int32_t out_cap, float* kernel_ms);
+
 /* ---- block search, third slice (round 5): from the vote to candidate loci ------------------------------------------------
  * What SrchBlk::findblock returns to its caller: TestOutput's second half (src/blksrc.cc:2677-2692: the candidate block pairs
  * against the random expectation of their mismatch counts) and FindHsp (:2346-2545: the region of a pair cut from the genome,
@@ -1343,6 +1386,42 @@ const char* spdp_align_b_seeded_refusal(const SpdpScoring* sc, const SpdpUnsplic
  * [6] DP cells of all device requests, [7] requests above max_trace_bytes. */
 int spdp_lsp_b(SpdpContext* ctx, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
                const SpdpProblem* probs, int n_probs, SpdpAlignment* out, int64_t* stats);
+
+/* ---- protein database search: from the vote to the printed hits (blkaln for AvsA, src/spaln.cc:846-1014) ----------------------
+ * `spaln -Q4 .. -Q7 -a<db> query.faa` in one call: every query below MinQuery = 2 Ktuple + Nshift residues is refused as the
+ * program refuses it (:1087, 1104); finds runs on the others (spdp_blk_finds); every candidate becomes a pair -- query = a,
+ * database sequence = b, the exg* flags from sp->lcl as :865-866, 908-909 set them --; the pairs run as ONE spdp_align_b_seeded
+ * call (sp->qck = 1 .. 3: no HSPs given and no src, the library's own word search as setaaseq sets no jxt; sp->qck = 0: spdp_align_b)
+ * and spdp_skl_rng_b; a pair whose fstat.val (what Gsinfo::scr holds after skl_rngB_ng) is <= sp->vthr is dropped unless all_out (-pw); the insertion sort by fstat.val
+ * (:957-970: stable, the first of equal values first) orders all candidates and the first min(max_out, pairs kept) are reported.
+ * db: the database sequences (chromosome = sequence, amino-acid codes) in the index's order.  The chain is a short one of its
+ * own beside the map + align chain of the genome entries (spdp_map_api.cpp): it shares none of their steps -- no loci, no
+ * regions, no signals, no rescoring kernels, one alignment call instead of chunks that hand the device on.
+ * Out: hit_off[n + 1] and the malloc'ed *hits and *corners (free() them): query i's hits are hits[hit_off[i] .. hit_off[i + 1]) in
+ * print order, the corners of a hit (trimskl's, 0-based m, n as spdp_skl_rng_b's first .. first + n_trim) at
+ * corners[corner_off .. corner_off + n_corners).  seconds (may be NULL): [0] the vote, [1] alignment, [2] host work, [3] the call.
+ * The ranges of a hit are the ALIGNED ranges, first corner to last.  The program prints something else in the range columns of -O4
+ * and of -O0: the sequences' own Seq::left + 1 and right, which in this chain are 1 and the length of the query and of the database
+ * sequence; the aligned range is where the first (m, n, length) triple of its -O4 record begins and the last one ends.
+ * Refused by name: what spdp_blk_finds refuses, a database whose sequence count differs from the index's, a query longer than
+ * 65535 residues, what spdp_align_b_seeded_refusal refuses, a null argument. */
+typedef struct SpdpMapHitB {
+    int32_t seq;                     /* the database sequence (its number in db)                                              */
+    int32_t a_left, a_right;         /* the query's aligned range: first and last corner (0-based, half open)                 */
+    int32_t b_left, b_right;         /* the same of the database sequence                                                     */
+    int32_t score;                   /* the engine's score (SpdpAlignment.score); sp->vthr is held against val                */
+    int32_t val, mch, mmc;           /* fstat of skl_rngB_ng: val / alprm.scale is printed                                    */
+    float   gap, unp;
+    int32_t n_corners;
+    int64_t corner_off;
+} SpdpMapHitB;
+int spdp_map_align_b(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* db,
+                     const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp, const SpdpBlkFindsParams* fprm,
+                     const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                     int64_t* hit_off, SpdpMapHitB** hits, SpdpSkl** corners, double* seconds);
+/* counters of the last spdp_map_align_b call on this context: queries [0] searched, [1] refused as too short; [2] candidates
+ * aligned, [3] pairs dropped by the threshold; microseconds in [4] the vote kernel, [5] the alignment calls, [6] host work */
+int spdp_blk_finds_stats(const SpdpContext* ctx, int64_t* out, int n);
 
 #ifdef __cplusplus
 }

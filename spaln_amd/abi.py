@@ -551,3 +551,13 @@ def wilip_model_from_fixture(fx) -> WilipModel:
         # to 8 * Ktuple, and findblock reads that one; Wlp::Wlp (src/wln.cc:222) reads the copy of wln.cc, which nobody sets
         m.shortquery = 50
     return m
+
+
+class BlkFindsParams(C.Structure):       # SpdpBlkFindsParams (include/spdp.h, "protein database search")
+    _fields_ = [("max_out", C.c_int32), ("local", C.c_int32), ("rln_coef", C.c_float), ("ptpl", C.c_int32), ("avrscr", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class MapHitB(C.Structure):              # SpdpMapHitB
+    _fields_ = [(k, C.c_int32) for k in ("seq", "a_left", "a_right", "b_left", "b_right", "score", "val", "mch", "mmc")] + [
+        ("gap", C.c_float), ("unp", C.c_float), ("n_corners", C.c_int32), ("corner_off", C.c_int64)]

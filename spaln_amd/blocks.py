@@ -178,6 +178,135 @@ def _host_index_to_dict(lib, h) -> dict:
     return out
 
 
+def read_protein_db_index(lib, path: str, max_out: int = 1, local: int = 0, cross_species: bool = True):
+    """<db>.bka of `spaln -W -KA` read for SrchBlk::finds: (the arrays as read_index_file gives them, for BlockIndex;
+    abi.BlkFindsParams as spdp_blk_finds_params_default fills it).  The index serves this max_out only (Ncand = max_out + 10)."""
+    from . import abi, defaults
+    lib.spdp_blk_index_read.restype = C.c_void_p
+    lib.spdp_blk_index_read.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib.spdp_blk_index_host_free.argtypes = [C.c_void_p]
+    lib.spdp_blk_finds_params_default.restype = C.c_int
+    lib.spdp_blk_finds_params_default.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    o = SearchOpts()
+    lib.spdp_blk_search_opts_default(C.byref(o))
+    for k, v in defaults.search_opts_protein_db(max_out, local, cross_species).items():
+        setattr(o, k, v)
+    err = C.create_string_buffer(256)
+    h = lib.spdp_blk_index_read(path.encode(), C.byref(o), err, 256)
+    if not h:
+        raise RuntimeError(err.value.decode())
+    try:
+        prm = abi.BlkFindsParams()
+        if lib.spdp_blk_finds_params_default(h, int(max_out), int(local), C.byref(prm)):
+            raise RuntimeError("spdp_blk_finds_params_default: the index holds no average word score")
+        out = _host_index_to_dict(lib, h)
+    finally:
+        lib.spdp_blk_index_host_free(h)
+    return out, prm
+
+
+SHORT = 16                               # SPDP_BLK_SHORT
+
+
+def finds(index: "BlockIndex", prm, queries, ranges=None, out_cap: int = 64, resident: bool = False):
+    """spdp_blk_finds (resident: spdp_blk_finds_resident on device arrays made here): the vote of SrchBlk::finds for protein
+    queries (uint8 code arrays) against the index of a protein database; prm: abi.BlkFindsParams.
+    Returns (records as an (n, out_cap) int32 array -- see split_finds_record --, kernel ms)."""
+    eng, lib, n = index.eng, index.lib, len(queries)
+    codes, offs = _packed(queries)
+    left = np.array([0 if ranges is None else ranges[i][0] for i in range(n)], dtype=np.int32)
+    right = np.array([len(queries[i]) if ranges is None else ranges[i][1] for i in range(n)], dtype=np.int32)
+    out = np.zeros((n, out_cap), dtype=np.int32)
+    ms = C.c_float()
+    fn = lib.spdp_blk_finds_resident if resident else lib.spdp_blk_finds
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    if not resident:
+        rc = fn(eng.ctx, index.h, C.byref(index.desc), C.byref(prm), codes.ctypes.data, offs.ctypes.data, left.ctypes.data, right.ctypes.data, n,
+                out.ctypes.data, out_cap, C.byref(ms))
+        eng._check(rc, "spdp_blk_finds")
+        return out, ms.value
+    hip = _hip_runtime()
+    hosts = (codes, offs, left, right, out)
+    bufs = [C.c_void_p() for _ in hosts]
+    try:
+        for b, a in zip(bufs, hosts):
+            if hip.hipMalloc(C.byref(b), C.c_size_t(max(a.nbytes, 16))):
+                raise RuntimeError("hipMalloc failed")
+            if a.nbytes and hip.hipMemcpy(b, a.ctypes.data, C.c_size_t(a.nbytes), 1):
+                raise RuntimeError("hipMemcpy failed")
+        rc = fn(eng.ctx, index.h, C.byref(index.desc), C.byref(prm), bufs[0], bufs[1], bufs[2], bufs[3], n, bufs[4], out_cap, C.byref(ms))
+        eng._check(rc, "spdp_blk_finds_resident")
+        if out.nbytes and hip.hipMemcpy(out.ctypes.data, bufs[4], C.c_size_t(out.nbytes), 2):
+            raise RuntimeError("hipMemcpy failed")
+    finally:
+        for b in bufs:
+            if b:
+                hip.hipFree(b)
+    return out, ms.value
+
+
+FINDS_STATS = ("searched", "refused_short", "candidates", "dropped_by_threshold", "vote_us", "align_us", "host_us")
+
+
+def finds_stats(eng) -> dict:
+    """spdp_blk_finds_stats: the counters of the last map_align_b call on this engine"""
+    v = (C.c_int64 * len(FINDS_STATS))()
+    eng.lib.spdp_blk_finds_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    eng.lib.spdp_blk_finds_stats(eng.ctx, v, len(FINDS_STATS))
+    return dict(zip(FINDS_STATS, (int(x) for x in v)))
+
+
+def map_align_b(index: "BlockIndex", db_codes, seq_off, sc, up, sp, fprm, queries, all_out: bool = False):
+    """spdp_map_align_b: what `spaln -Q4 .. -Q7 -a<db> [-M N] [-pw]` prints of protein queries against a protein database -- the
+    vote of finds, every candidate aligned (spdp_align_b_seeded with sp.qck = 1 .. 3, spdp_align_b with 0), the threshold sp.vthr
+    unless all_out, the hits ordered by fstat.val, at most fprm.max_out.  db_codes / seq_off: the database sequences in the
+    index's order; sp: abi.SeedParams with its model set (defaults.seed_params_b + wilip_model_b); fprm: abi.BlkFindsParams.
+    Returns (per query a list of dicts seq, a_rng, b_rng, score, val, mch, mmc, gap, unp, corners (k, 2) int32; seconds [vote,
+    alignment, host, call])."""
+    from . import abi
+    eng, lib, n = index.eng, index.lib, len(queries)
+    codes, offs = _packed(queries)
+    dc = np.ascontiguousarray(db_codes, dtype=np.uint8)
+    do = np.ascontiguousarray(seq_off, dtype=np.int64)
+    g = Genome(dc.ctypes.data, do.ctypes.data, len(do) - 1)
+    hit_off = np.zeros(n + 1, dtype=np.int64)
+    hits, corners = C.POINTER(abi.MapHitB)(), C.POINTER(C.c_int32)()
+    sec = (C.c_double * 4)()
+    lib.spdp_map_align_b.restype = C.c_int
+    lib.spdp_map_align_b.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4
+    rc = lib.spdp_map_align_b(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(up), C.byref(sp), C.byref(fprm),
+                              codes.ctypes.data, offs.ctypes.data, n, int(bool(all_out)), hit_off.ctypes.data, C.byref(hits), C.byref(corners), sec)
+    if rc < 0:
+        eng._check(rc, "spdp_map_align_b")
+    out = []
+    for i in range(n):
+        lst = []
+        for k in range(int(hit_off[i]), int(hit_off[i + 1])):
+            h = hits[k]
+            c = np.array([[corners[2 * (h.corner_off + j)], corners[2 * (h.corner_off + j) + 1]] for j in range(h.n_corners)], dtype=np.int32).reshape(-1, 2)
+            lst.append(dict(seq=h.seq, a_rng=(h.a_left, h.a_right), b_rng=(h.b_left, h.b_right), score=h.score, val=h.val, mch=h.mch, mmc=h.mmc,
+                            gap=h.gap, unp=h.unp, corners=c))
+        out.append(lst)
+    _free(hits, corners)
+    return out, list(sec)
+
+
+def split_finds_record(rec: np.ndarray) -> dict:
+    """one query's record of spdp_blk_finds -> dict(flags, nmmc, testword, sigm, heap = [(block, score)] in hsort order,
+    cands = the candidate sequences in the order finds fills sqs[1..]); a refused or cut record: its flags alone"""
+    n, nmmc, flags = int(rec[0]), int(rec[1]), int(rec[2])
+    if flags & SHORT or flags & CUT or not flags & REACHED:
+        return dict(flags=flags, nmmc=nmmc)
+    sigm = int(rec[5])
+    heap = [(int(rec[6 + 2 * i]), int(rec[7 + 2 * i])) for i in range(sigm)]
+    j = 6 + 2 * sigm
+    nc = int(rec[j])
+    cands = [int(x) for x in rec[j + 1:j + 1 + nc]]
+    assert j + 1 + nc == n, (j, nc, n)
+    return dict(flags=flags, nmmc=nmmc, testword=[int(rec[3]), int(rec[4])], sigm=sigm, heap=heap, cands=cands)
+
+
 class BlkBuildParams(C.Structure):       # SpdpBlkBuildParams
     _fields_ = [("ktuple", C.c_int32), ("nshift", C.c_int32), ("blklen", C.c_int32), ("maxgene", C.c_int32), ("nbitpat", C.c_int32),
                 ("afact", C.c_int32), ("bitpat", C.c_uint32), ("bitpat2", C.c_uint32), ("threaded", C.c_int32)]

@@ -2,6 +2,7 @@
 // once, a call uploads its queries, runs spdp_blk_vote_wave (a wave per query, waves persistent) and brings the records back.
 #include "spdp_internal.h"
 #include "spdp_blk_dev.h"
+#include "spdp_blk_finds_dev.h"
 #include "spdp_hsp_dev.h"
 #include "spdp_loci.h"
 #include "spdp_hsp_host.h"
@@ -56,8 +57,11 @@ struct SpdpBlkIndex {
     size_t slab_bytes = 0;
     int n_waves = 0, hh_in_lds = 0;
     uint32_t lds_bytes = 0;
+    BlkFindsKept* finds_kept = nullptr;         // what the finds vote keeps between calls (spdp_blk_finds_api.cpp)
+    int64_t n_words = 0;                        // entries of blkb as uploaded
     ~SpdpBlkIndex()
     {
+        delete finds_kept;
         for (void* p : bufs) if (p) (void) hipFree(p);
         if (slabs) (void) hipFree(slabs);
         if (next) (void) hipFree(next);
@@ -116,7 +120,7 @@ extern "C" SpdpBlkIndex* spdp_blk_index_create(SpdpContext* ctx, const SpdpBlkIn
     }
     (void) hipSetDevice(ctx->device);
     SpdpBlkIndex* ix = new SpdpBlkIndex;
-    ix->ctx = ctx;
+    ix->ctx = ctx; ix->n_words = d->n_words;
     BlkDev& v = ix->dev;
     memset(&v, 0, sizeof v);
     v.nalpha = d->nalpha; v.tabsize = d->tabsize; v.nshift = d->nshift; v.nbitpat = d->nbitpat; v.convts = d->convts;
@@ -202,6 +206,23 @@ extern "C" void spdp_blk_index_destroy(SpdpBlkIndex* ix)
     if (!ix) return;
     (void) hipSetDevice(ix->ctx->device);
     delete ix;
+}
+
+// ---- the index as the finds entries see it (spdp_blk_finds_dev.h)
+SpdpContext* spdp_blk_index_ctx(const SpdpBlkIndex* ix) { return ix->ctx; }
+const BlkDev* spdp_blk_index_view(const SpdpBlkIndex* ix) { return &ix->dev; }
+BlkFindsKept*& spdp_blk_index_finds_kept(SpdpBlkIndex* ix) { return ix->finds_kept; }
+int64_t spdp_blk_index_n_words(const SpdpBlkIndex* ix) { return ix->n_words; }
+const BlkDev* spdp_blk_index_on_device(SpdpBlkIndex* ix)
+{
+    if (!ix->d_dev) {
+        SpdpContext* ctx = ix->ctx;
+        BlkDev* d = nullptr;
+        if (hipMalloc((void**) &d, sizeof(BlkDev)) != hipSuccess) { ctx->err = "spdp_blk_finds: no device memory for the index header"; return nullptr; }
+        if (hipMemcpy(d, &ix->dev, sizeof(BlkDev), hipMemcpyHostToDevice) != hipSuccess) { (void) hipFree(d); ctx->err = "spdp_blk_finds: the index header could not be uploaded"; return nullptr; }
+        ix->d_dev = d;
+    }
+    return ix->d_dev;
 }
 
 static int ensure_waves(SpdpContext* ctx, SpdpBlkIndex* ix, int n)

@@ -191,6 +191,21 @@ extern "C" SpdpBlkIndexHost* spdp_blk_index_read(const char* path, const SpdpBlk
 extern "C" const SpdpBlkIndexDesc* spdp_blk_index_host_desc(const SpdpBlkIndexHost* h) { return h ? &((const HostIndex*) h)->d : nullptr; }
 extern "C" void spdp_blk_index_host_free(SpdpBlkIndexHost* h) { delete (HostIndex*) h; }
 
+// what SrchBlk::initialize derives with gnmdb = false beside the descriptor (src/blksrc.cc:2202, 2211; Randbs::Randbs :2058)
+extern "C" int spdp_blk_finds_params_default(const SpdpBlkIndexHost* hh, int32_t max_out, int32_t local, SpdpBlkFindsParams* p)
+{
+    const HostIndex* h = (const HostIndex*) hh;
+    if (!h || !p || !h->wc.AvrScr || h->bitpat.empty() || h->rscrtab.empty()) return -1;
+    memset(p, 0, sizeof *p);
+    const double avr = (double) h->wc.AvrScr * h->bitpat[0] / h->wcp.Nshift;
+    const float rln_fact = (float) (0.00520 * 2);                       // RlnFact (src/blksrc.h:390)
+    p->max_out = max_out; p->local = local ? 1 : 0;
+    p->rln_coef = (float) (rln_fact * avr * h->wcp.Nbitpat);
+    p->avrscr = h->wc.AvrScr;
+    p->ptpl = (int32_t) (int16_t) (h->rscrtab[0] / (int) h->wc.AvrScr);      // (SHORT ptpl)
+    return 0;
+}
+
 // ---- the index builder (include/spdp.h "the index builder"): host side -----------------------------------------------------
 #include "spdp_internal.h"
 #include "spdp_blk_build.h"

@@ -174,3 +174,13 @@ BLOCK_ACOMP_20 = [float.fromhex(x) for x in (
     "0x1.9dac9b7222838p+0 -0x1.2fef0207cbap+1 0x1.44fd3d196c1cfp+3 -0x1.4611967298f91p+2 -0x1.7045848bd36fcp+2 "
     "0x1.157df2a1998dep+2 0x1.b29309c2da184p-3 -0x1.9e5b95c02c5ccp+1 0x1.aeb2e0dfc9daep+2 0x1.8ffa6b1bb2d76p+1 "
     "-0x1.785b7311540c6p+3 -0x1.f7373e897ef4ap+2 0x1.7b75b1ad70547p+3 0x1.3672571d50d5bp+3 -0x1.ae4b8287ac8dp+0").split()]
+
+
+# ---- the block search of a protein database (`spaln -Q7 -a<db>`: SrchBlk::finds) ------------------------------------------------
+# SrchBlk::initialize with gnmdb = false (src/blksrc.cc:2179-2226): Randbs takes its square-root form, and -- algmode.crs being set
+# unless -yX0 -- the cross-species constants RbsFactSqrX = 0 and RbsBaseX = 0.5 (:65-67, 2053-2057); with -yX0 RbsFactSqr =
+# 0.303 x 2 and RbsBase = 3
+def search_opts_protein_db(max_out: int = 1, local: int = 0, cross_species: bool = True) -> dict:
+    """the fields of SpdpBlkSearchOpts to read a <db>.bka with (blocks.read_index_file(lib, path, **opts))"""
+    return dict(max_out=int(max_out), local=int(local), genomic_db=0, max_mmc=15,
+                rbs_fact=0.0 if cross_species else float(np.float32(0.303 * 2)), rbs_base=0.5 if cross_species else 3.0)

@@ -1,0 +1,212 @@
+#!/usr/bin/env python3
+"""Protein queries against a protein database inside the library, against the reference's own program.
+
+    python tools/aa_search.py [--queries 300] [--sequences 580] [--threads 16] [--max-out N] [--all-out]
+                                                                      (an MI355X box; oracle/_ref for the comparison)
+
+A synthetic protein database with paralog families and queries of eight classes (mutated at 15 / 35 / 50 %, fragments, every tenth
+residue X, unrelated, tiny) is formatted by the compiled reference's own `spaln -W -KA`.  Two runs on the same files:
+
+  * reference:  oracle/_ref/spaln -Q7 -A0 -O4 -t<threads> [-M N] [-pw] -aprot q.faa      (-A0: the scalar engine of Aln2b1, the one
+                the library's unspliced aligner reproduces)
+  * library:    prot.bka read by spdp_blk_index_read, the database's residue codes, and then ONE spdp_map_align_b call = the vote
+                of SrchBlk::finds on the device -> every candidate a pair -> spdp_align_b_seeded -> spdp_skl_rng_b -> the
+                threshold and the order of the printed hits.
+
+Compared per query: the ordered hit list (name, printed score, the corners as -O4 prints them, the aligned ranges).  One JSON line: reference
+aligned, library aligned, identical, seconds of both (the library's call warm: the median of --repeat calls after a first one),
+the library's split from spdp_blk_finds_stats and the vote kernel's HIP-event time.  Reads nothing of the reference's sources."""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from spaln_amd import abi, blocks, defaults, engine  # noqa: E402
+
+REF = os.path.join(ROOT, "oracle", "_ref", "spaln")
+ENV = dict(os.environ, ALN_TAB=os.path.join(ROOT, "oracle", "_ref", "table"))
+AA = "ARNDCQEGHILKMFPSTWYV"
+CLASSES = ("m15", "frag", "xx", "m35", "m50", "unr", "tiny", "para")
+
+
+def encode(s: str) -> np.ndarray:
+    lut = np.full(256, 2, dtype=np.uint8)               # X and anything else: AMB
+    for i, c in enumerate(AA):
+        lut[ord(c)] = i + 3
+    return lut[np.frombuffer(s.encode(), dtype=np.uint8)]
+
+
+def rand_protein(rng, n):
+    return "".join(AA[i] for i in rng.integers(0, 20, size=n))
+
+
+def mutate(rng, s, sub, indel=0.0):
+    out = []
+    for c in s:
+        r = rng.random()
+        if r < indel / 2:
+            continue
+        if r < indel:
+            out.append(AA[rng.integers(0, 20)])
+        out.append(AA[rng.integers(0, 20)] if rng.random() < sub else c)
+    return "".join(out)
+
+
+def make_data(rng, n_seq, n_queries):
+    db = [rand_protein(rng, int(rng.integers(60, 701))) for _ in range(n_seq)]
+    n_fam = max(1, n_seq // 8)
+    for k in range(n_fam):                              # paralogs of others
+        db[n_seq - 1 - k] = mutate(rng, db[k], 0.25, 0.04)
+    queries = []
+    for i in range(n_queries):
+        cls = CLASSES[i % len(CLASSES)]
+        src = int(rng.integers(n_fam, n_seq - n_fam)) if cls != "para" else int(rng.integers(0, n_fam))
+        s = db[src]
+        if cls == "m15":
+            q = mutate(rng, s, 0.15, 0.03)
+        elif cls == "frag":
+            a = int(rng.integers(0, len(s) - 59))
+            q = s[a:a + int(rng.integers(12, 61))]
+        elif cls == "xx":
+            q = "".join("X" if k % 10 == 9 else c for k, c in enumerate(mutate(rng, s, 0.10)))
+        elif cls == "m35":
+            q = mutate(rng, s, 0.35)
+        elif cls == "m50":
+            q = mutate(rng, s, 0.50)
+        elif cls == "unr":
+            q, src = rand_protein(rng, int(rng.integers(60, 400))), -1
+        elif cls == "tiny":
+            q = s[5:5 + int(rng.integers(3, 12))]
+        else:
+            q = mutate(rng, s, 0.10)
+        queries.append((f"q{i}", cls, src, q))
+    return db, queries
+
+
+def parse_o4(txt):
+    out = {}
+    for ln in txt.splitlines():
+        f = ln.split()
+        if f and f[0] == "XYL:":
+            at = f.index(":", 1)
+            out.setdefault(f[1], []).append((f[5], f[9], [int(x) for x in f[at + 1:]]))
+    return out
+
+
+def segments(corners):
+    out = []
+    for (m0, n0), (m1, n1) in zip(corners[:-1], corners[1:]):
+        if m1 - m0 == n1 - n0 and m1 > m0:
+            out += [int(m0) + 1, int(n0) + 1, int(m1 - m0)]
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--queries", type=int, default=300)
+    ap.add_argument("--sequences", type=int, default=580)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--max-out", type=int, default=1)
+    ap.add_argument("--all-out", action="store_true")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--no-reference", action="store_true", help="library only (a profiler run): nothing is compared")
+    args = ap.parse_args()
+    rng = np.random.default_rng(args.seed)
+    db, queries = make_data(rng, args.sequences, args.queries)
+    with tempfile.TemporaryDirectory() as td:
+        with open(os.path.join(td, "prot.faa"), "w") as f:
+            for i, s in enumerate(db):
+                f.write(f">p{i}\n{s}\n")
+        with open(os.path.join(td, "q.faa"), "w") as f:
+            for name, _, _, q in queries:
+                f.write(f">{name}\n{q}\n")
+        t0 = time.perf_counter()
+        r = subprocess.run([REF, "-W", "-KA", f"-t{args.threads}", "prot.faa"], cwd=td, env=ENV, capture_output=True, text=True)
+        format_s = time.perf_counter() - t0
+        if r.returncode or not os.path.exists(os.path.join(td, "prot.bka")):
+            print("spaln -W -KA failed: " + r.stderr[-400:], file=sys.stderr)
+            return 2
+        want, ref_s, ref_default_s, default_differs = None, None, None, None
+        if not args.no_reference:
+            opts = ([f"-M{args.max_out}"] if args.max_out > 1 else []) + (["-pw"] if args.all_out else [])
+            cmd = [REF, "-Q7", "-A0", "-O4", f"-t{args.threads}"] + opts + ["-aprot", "q.faa"]
+            subprocess.run(cmd, cwd=td, env=ENV, capture_output=True, text=True)        # (warm: the files in the page cache)
+            t0 = time.perf_counter()
+            r = subprocess.run(cmd, cwd=td, env=ENV, capture_output=True, text=True)
+            ref_s = time.perf_counter() - t0
+            if r.returncode:
+                print("spaln ended with %d: %s" % (r.returncode, r.stderr[-400:]), file=sys.stderr)
+                return 2
+            want = parse_o4(r.stdout)
+            # the program as it runs without -A0 (its default engine of Aln2b1), on the same files: its time, and how many queries'
+            # records differ from the -A0 run's
+            cmd_d = [c for c in cmd if c != "-A0"]
+            subprocess.run(cmd_d, cwd=td, env=ENV, capture_output=True, text=True)
+            t0 = time.perf_counter()
+            r = subprocess.run(cmd_d, cwd=td, env=ENV, capture_output=True, text=True)
+            ref_default_s = time.perf_counter() - t0
+            want_d = parse_o4(r.stdout) if r.returncode == 0 else None
+            default_differs = None if want_d is None else sum(1 for name, _, _, _ in queries if want_d.get(name, []) != want.get(name, []))
+        eng = engine.Engine(0)
+        t0 = time.perf_counter()
+        arrays, fprm = blocks.read_protein_db_index(eng.lib, os.path.join(td, "prot.bka"), max_out=args.max_out)
+        dix = blocks.BlockIndex(eng, arrays)
+        load_s = time.perf_counter() - t0
+    seqs = [encode(s) for s in db]
+    db_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    db_off[1:] = np.cumsum([len(s) for s in seqs])
+    db_codes = np.concatenate(seqs)
+    sc, up, model = defaults.scoring_b(), abi.UnsplicedParams(1.0, 0), defaults.wilip_model_b()
+    sp = defaults.seed_params_b(3, 15)
+    sp.wilip = C.addressof(model)
+    q_codes = [encode(q) for _, _, _, q in queries]
+    blocks.map_align_b(dix, db_codes, db_off, sc, up, sp, fprm, q_codes[:min(64, len(q_codes))], all_out=args.all_out)     # first call: allocations, module load
+    times, splits, kernel_ms = [], [], []
+    for _ in range(max(1, args.repeat)):
+        t0 = time.perf_counter()
+        got, sec = blocks.map_align_b(dix, db_codes, db_off, sc, up, sp, fprm, q_codes, all_out=args.all_out)
+        times.append(time.perf_counter() - t0)
+        splits.append(blocks.finds_stats(eng))
+    k = int(np.argsort(times)[len(times) // 2])
+    lib_s, st = times[k], splits[k]
+    _, ms = blocks.finds(dix, fprm, q_codes)             # the vote alone: HIP-event time
+    dix.free()
+    def spans(t):                                       # where the first triple begins and the last one ends
+        return (t[0], t[-3] + t[-1] - 1, t[1], t[-2] + t[-1] - 1)
+    want = None if want is None else {k: [(b, v, t, spans(t)) for b, v, t in recs] for k, recs in want.items()}
+    mine = {name: [(f"p{h['seq']}", "%.1f" % (h["val"] / defaults.B_SCALE), segments(h["corners"].tolist()),
+                    (h["a_rng"][0] + 1, h["a_rng"][1], h["b_rng"][0] + 1, h["b_rng"][1])) for h in hits]
+            for (name, _, _, _), hits in zip(queries, got) if hits}
+    bad = None if want is None else [name for name, _, _, _ in queries if mine.get(name, []) != want.get(name, [])]
+    per_class = {}
+    for (name, cls, src, _), hits in zip(queries, got):
+        c = per_class.setdefault(cls, dict(queries=0, aligned=0, source_first=0))
+        c["queries"] += 1
+        c["aligned"] += bool(hits)
+        c["source_first"] += bool(hits) and hits[0]["seq"] == src
+    print(json.dumps({
+        "what": "every record `spaln -Q7 -A0 -O4%s%s -a<db>` prints against one spdp_map_align_b call" %
+                (f" -M{args.max_out}" if args.max_out > 1 else "", " -pw" if args.all_out else ""),
+        "sequences": len(db), "queries": len(queries), "reference_aligned": None if want is None else len(want), "library_aligned": len(mine),
+        "identical": None if bad is None else len(queries) - len(bad), "of": len(queries), "first_differing": None if bad is None else bad[:5],
+        "reference_threads": args.threads, "reference_s": None if ref_s is None else round(ref_s, 3),
+        "reference_default_engine_s": None if ref_default_s is None else round(ref_default_s, 3), "queries_whose_records_differ_without_A0": default_differs, "library_s": round(lib_s, 4),
+        "library_s_all": [round(t, 4) for t in times], "index_load_s": round(load_s, 3), "format_s": round(format_s, 3),
+        "library_over_reference": None if ref_s is None else round(ref_s / lib_s, 2),
+        "split": st, "vote_kernel_ms": round(ms, 3), "vote_queries_per_s": round(len(queries) / (ms * 1e-3), 1) if ms > 0 else None,
+        "candidates_per_query": round(st["candidates"] / max(st["searched"], 1), 3), "per_class": per_class, "device": eng.device_name()}))
+    eng.close()
+    return 0 if not bad else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
