@@ -868,7 +868,7 @@ void spdp_blk_index_host_free(SpdpBlkIndexHost* h);
  * one of the reference-sized hash tables ran full, where the reference would grow it), then sign[4] mmct[4] nhit[4] maxs[4]
  * testword[4] (Bhit4); per direction n, (block, score) x n: the significant blocks (prqueue_b, heap order); n_pairs and
  * nine ints per candidate pair, best first (BPAIR: bscr chr lb rb ub db zl zr rvs); n_runs and (block | direction << 28,
- * score) x n_runs: the run scores (Bhit4::bscr) FindHsp can look at -- within 4 x max(ExtBlockL, ExtBlock) blocks of a reported pair (its reach over three moves of an end), inside its
+ * score) x n_runs (ints of a row behind its record: zero): the run scores (Bhit4::bscr) FindHsp can look at -- within 4 x max(ExtBlockL, ExtBlock) blocks of a reported pair (its reach over three moves of an end), inside its
  * chromosome, on its strand -- unordered.  kernel_ms (may be NULL): HIP-event time. */
 #define SPDP_BLK_REACHED 1
 #define SPDP_BLK_CUT     2
@@ -881,6 +881,16 @@ int spdp_blk_vote(SpdpContext* ctx, const SpdpBlkIndex* ix, const uint8_t* codes
 int spdp_blk_vote_resident(SpdpContext* ctx, const SpdpBlkIndex* ix, const uint8_t* d_codes, const int64_t* d_offs,
                            const int32_t* d_left, const int32_t* d_right, const int32_t* d_stop_at, int32_t n,
                            int32_t* d_out, int32_t out_cap, float* kernel_ms);
+/* Which paths the vote took on this index since it was created, summed over every query of every spdp_blk_vote / _resident call
+ * (and of the block searches made with it): out[0 .. n) of {queries, posting lists cut short by a zero entry, merges of two lists done by the wave
+ * in LDS, merges done by one lane (a list longer than 128), groups a chunk's run-hash updates were split into beyond its first,
+ * entries that went through the run hash alone (the table was full), growths of the run hash, growths of the hit lists'
+ * position tables, growths of the run lists' position tables, wipes of the run hash, queries longer than the wave's residue
+ * cache, directions whose posting lists were not fetched ahead (Nshift > 12), queries ended as SPDP_BLK_TABLE}.
+ * (Words voted and chunks of 64 entries beyond a word's first are not counted: they cost the scan's inner loops, and follow from
+ * the index and the queries.)  Reads the waves' counters from the device; returns 0, -1 on a null argument or a failed copy. */
+#define SPDP_BLK_VOTE_STATS_N 13
+int spdp_blk_vote_stats(SpdpContext* ctx, const SpdpBlkIndex* ix, int64_t* out, int n);
 
 /* ---- protein database search: the vote of SrchBlk::finds (protein queries against the amino-acid index of a protein database,
  * `spaln -W -KA`; QRYvsDB == AvsA) -----------------------------------------------------------------------------------------------

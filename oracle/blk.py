@@ -166,6 +166,34 @@ def grows() -> int:
     return int(C.c_int.in_dll(_o.lib(), "spdp_oracle_blk_grows").value)
 
 
+def last_grows() -> dict:
+    """the growths of the last vote() call table by table: dict(run_hash, hits, runs), the lists' counts the largest over the
+    four directions.  The product reports a query as TABLE at the fourth growth of one table; the oracle goes on growing."""
+    v = (C.c_int * 3).in_dll(_o.lib(), "spdp_oracle_blk_last_grows")
+    return dict(run_hash=int(v[0]), hits=int(v[1]), runs=int(v[2]))
+
+
+PATHS = ("words", "more_chunks", "zero_ended", "lds_merges", "lane_merges", "phases", "longest", "in_both")
+
+
+def last_paths() -> dict:
+    """what the last vote() call walked, in the terms of the product's path counters (spdp_blk_vote_stats): words voted, chunks of
+    64 merged entries beyond a word's first, voting lists with a zero entry, words whose two voting lists both have at most 128
+    entries / not, phases opened, the longest voting list, entries that stood in both lists of a word.  The product's own choices (splits, where level 0 lies) are not the oracle's to tell."""
+    v = (C.c_int * len(PATHS)).in_dll(_o.lib(), "spdp_oracle_blk_last_paths")
+    return dict(zip(PATHS, (int(x) for x in v)))
+
+
+def last_calls() -> int:
+    """TestOutput calls the last vote() call met, the asked one included: what the product writes into its record's second int"""
+    return int(C.c_int.in_dll(_o.lib(), "spdp_oracle_blk_last_calls").value)
+
+
+def last_rounds() -> int:
+    """rounds the scan of the last vote() call made (every round opens up to 4 x Nshift phases of the run hash)"""
+    return int(C.c_int.in_dll(_o.lib(), "spdp_oracle_blk_last_rounds").value)
+
+
 def runs_near_pairs(ix: BlkIndex, runs, pairs):
     """the part of the recorded run scores the product reports: blocks within ExtBlockL of a reported pair, inside its
     chromosome, on its strand (runs: per direction [(block, score)], pairs: rows of nine ints)"""

@@ -49,7 +49,7 @@ typedef struct {
 
 /* ---- Dhash<key, int>, literally ---------------------------------------------------------------------------------- */
 typedef struct { uint32_t key; int32_t val; } KV;
-typedef struct { KV* t; uint32_t size1, size2; int32_t undef; int overflow; } DH;
+typedef struct { KV* t; uint32_t size1, size2; int32_t undef; int overflow; int grows; } DH;
 
 static void dh_clear(DH* h) { for (uint32_t i = 0; i < h->size1; ++i) { h->t[i].key = 0; h->t[i].val = h->undef; } }
 static uint32_t next_prime(uint32_t n)          /* supprime(n), src/supprime.cc:375: the smallest prime >= n */
@@ -65,6 +65,16 @@ static uint32_t next_prime(uint32_t n)          /* supprime(n), src/supprime.cc:
 static KV* dh_map(DH* h, uint32_t key, int record);
 int spdp_oracle_blk_last_forced = 0;            /* the snapshot of the last call is findblock's closing TestOutput(1) (tests: the loci checker) */
 int spdp_oracle_blk_grows = 0;                  /* how often a table grew (tests: the fixtures must reach this path) */
+/* the growths of the last call, table by table: the run hash, the position table of the hit lists, that of the run lists (the
+ * largest over the four directions for the lists).  The product gives a query up at the fourth growth of one table. */
+int spdp_oracle_blk_last_grows[3] = {0, 0, 0};
+/* what the last call walked, for the product's path counters (spdp_blk_vote_stats): words voted, chunks of 64 merged entries
+ * beyond a word's first, voting lists that hold a zero entry, words with two voting lists both of at most 128 entries, words
+ * with two voting lists one of which is longer, phases opened (run hash cleared), the longest voting list, entries that
+ * stood in both lists of a word (merged into one) */
+int spdp_oracle_blk_last_paths[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+int spdp_oracle_blk_last_calls = 0;             /* TestOutput calls the last call met, the asked one included (the product's record, [1]) */
+int spdp_oracle_blk_last_rounds = 0;            /* rounds of the last call's scan (each: four directions x Nshift phases at most) */
 /* Dhash::resize() (src/clib.h:341-355): a table of the next prime >= twice the size, live entries re-entered in slot order */
 static void dh_grow(DH* h)
 {
@@ -72,6 +82,7 @@ static void dh_grow(DH* h)
     const uint32_t n_old = h->size1;
     if (n_old > (1u << 24)) { h->overflow = 1; return; }
     ++spdp_oracle_blk_grows;
+    ++h->grows;
     h->size1 = next_prime(2 * n_old);
     h->t = (KV*) malloc(sizeof(KV) * h->size1);
     dh_clear(h);
@@ -246,8 +257,9 @@ static uint32_t next_merge(ST* s)
         if (s->front[j] && s->front[j] < blk) blk = s->front[j];
     }
     if (blk == 0) return 0;
-    for (int j = 0; j + 1 < ix->kk; ++j) {
+    for (int j = 0, both = 0; j + 1 < ix->kk; ++j) {
         if (s->xx[j] < 0) continue;
+        if (blk == s->front[j] && both++) ++spdp_oracle_blk_last_paths[7];
         if (blk == s->front[j])
             s->front[j] = (++s->xx[j] < (int) ix->nblk[s->ww[j]]) ? list_at(ix, s->ww[j], s->xx[j]) : 0;
     }
@@ -436,6 +448,9 @@ int spdp_oracle_blk_vote_carry(const BlkIndex* ix, const uint8_t* q, int q_len, 
         for (int k = 0; k < ix->kk; ++k) { s.pat[k] = p; p += 3 + 2 * p[0]; }
     }
     const int qlen = right - left;
+    memset(spdp_oracle_blk_last_paths, 0, sizeof spdp_oracle_blk_last_paths);
+    memset(spdp_oracle_blk_last_grows, 0, sizeof spdp_oracle_blk_last_grows);
+    spdp_oracle_blk_last_forced = spdp_oracle_blk_last_rounds = spdp_oracle_blk_last_calls = 0;
     if (qlen - (nshift + s.pat[0][1]) < 1) return 0;
     s.app_c = ix->kk > 1 ? pow((double) ix->nbitpat, ix->cfact) : 1.;
     for (int k = 0; k < ix->kk; ++k) s.endss[k] = right - s.pat[k][1];
@@ -466,7 +481,6 @@ int spdp_oracle_blk_vote_carry(const BlkIndex* ix, const uint8_t* q, int q_len, 
         }
     }
     int n_out = 0, calls = 0;
-    spdp_oracle_blk_last_forced = 0;
     int nohit = 0, sigpr = 0;
     int c = qlen / (nshift + nshift) - 1;
     const int is_short = qlen < ix->shortquery;
@@ -493,6 +507,7 @@ int spdp_oracle_blk_vote_carry(const BlkIndex* ix, const uint8_t* q, int q_len, 
                 if (!is_short) ms = as[e][sft];
                 int cscr = 0, qq = 0, p = 0;
                 dh_clear(&s.hh);
+                ++spdp_oracle_blk_last_paths[5];
                 do {
                     const int ss = *ws;
                     if (prty) *ws -= nshift; else *ws += nshift;
@@ -502,10 +517,26 @@ int spdp_oracle_blk_vote_carry(const BlkIndex* ix, const uint8_t* q, int q_len, 
                     s.testword[d] += ix->kk;
                     if (wdscr == 0) { qq = 1; continue; }
                     init_merge(&s);
+                    {
+                        int nl = 0, longest = 0;
+                        for (int j = 0; j < (ix->kk == 1 ? 1 : ix->kk - 1); ++j) {
+                            if (s.xx[j] < 0 || s.ww[j] >= (uint32_t) ix->tabsize || !ix->blkp[s.ww[j]] || !ix->nblk[s.ww[j]]) continue;
+                            const int len = ix->nblk[s.ww[j]];
+                            ++nl;
+                            if (len > longest) longest = len;
+                            if (len > spdp_oracle_blk_last_paths[6]) spdp_oracle_blk_last_paths[6] = len;
+                            for (int x = 0; x < len; ++x) if (!list_at(ix, s.ww[j], x)) { ++spdp_oracle_blk_last_paths[2]; break; }
+                        }
+                        ++spdp_oracle_blk_last_paths[0];
+                        if (nl == 2) ++spdp_oracle_blk_last_paths[longest <= 128 ? 3 : 4];
+                    }
+                    int n_entries = 0;
                     ++p; qq = 0;
                     cscr += wdscr;
                     uint32_t blk;
                     while ((blk = next_merge(&s)) != 0) {
+                        if (n_entries && n_entries % 64 == 0) ++spdp_oracle_blk_last_paths[1];
+                        ++n_entries;
                         KV* h = dh_incr(&s.hh, blk);
                         acr[blk] += wdscr;
                         { BS sb = {blk, acr[blk]}; pq_update(&s.qa[d], sb); }
@@ -553,7 +584,13 @@ int spdp_oracle_blk_vote_carry(const BlkIndex* ix, const uint8_t* q, int q_len, 
     }
 #undef SNAP
     int overflow = s.hh.overflow;
+    spdp_oracle_blk_last_grows[0] = s.hh.grows;
+    spdp_oracle_blk_last_grows[1] = spdp_oracle_blk_last_grows[2] = 0;
+    spdp_oracle_blk_last_rounds = (int) nmmc;
+    spdp_oracle_blk_last_calls = calls;
     for (int d = 0; d < 4; ++d) {
+        if (s.qa[d].hpos.grows > spdp_oracle_blk_last_grows[1]) spdp_oracle_blk_last_grows[1] = s.qa[d].hpos.grows;
+        if (s.qb[d].hpos.grows > spdp_oracle_blk_last_grows[2]) spdp_oracle_blk_last_grows[2] = s.qb[d].hpos.grows;
         if (carry) {
             memcpy(carry + 2 * d * (ix->nascr + 1), s.qa[d].data, sizeof(BS) * (ix->nascr + 1));
             carry[8 * (ix->nascr + 1) + d] = (int) s.qa[d].hpos.size1;

@@ -561,3 +561,8 @@ class BlkFindsParams(C.Structure):       # SpdpBlkFindsParams (include/spdp.h, "
 class MapHitB(C.Structure):              # SpdpMapHitB
     _fields_ = [(k, C.c_int32) for k in ("seq", "a_left", "a_right", "b_left", "b_right", "score", "val", "mch", "mmc")] + [
         ("gap", C.c_float), ("unp", C.c_float), ("n_corners", C.c_int32), ("corner_off", C.c_int64)]
+
+
+# spdp_blk_vote_stats (include/spdp.h): the path counters of the block vote, in the order the library writes them
+BLK_VOTE_STATS = ("queries", "zero_ended", "lds_merges", "lane_merges", "splits", "lane_entries",
+                  "hash_growths", "hits_growths", "runs_growths", "wipes", "hbm_queries", "no_prefetch", "table")

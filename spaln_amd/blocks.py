@@ -27,7 +27,7 @@ class BlkIndexDesc(C.Structure):
 _PRM = dict(nalpha=0, tabsize=3, nshift=5, nbitpat=8, convts=10, n_chr=12, maxblk=14, kk=15, drna=16, maxmmc=17, nseg=19,
             minsigpr=22, ncand=23, nascr=24, maxblock=25, extblock=26, extblockl=27, shortquery=28, hh_size=29, hh_step=30, hb_size=31,
             hb_step=32, ha_size=33, ha_step=34, gdb=38, blklen=6)
-REACHED, CUT, TABLE = 1, 2, 4
+REACHED, CUT, TABLE, FORCED = 1, 2, 4, 8
 
 
 def desc_from_arrays(fx: dict):
@@ -63,6 +63,7 @@ class BlockIndex:
         self.lib.spdp_blk_index_destroy.argtypes = [C.c_void_p]
         self.lib.spdp_blk_vote.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         self.lib.spdp_blk_vote_resident.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        self.lib.spdp_blk_vote_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self.desc, self._keep = desc_from_arrays(fx)
         self.h = self.lib.spdp_blk_index_create(eng.ctx, C.byref(self.desc))
         if not self.h:
@@ -103,6 +104,17 @@ class BlockIndex:
                                              C.byref(ms))
         self.eng._check(rc, "spdp_blk_vote_resident")
         return ms.value
+
+    def vote_stats(self) -> dict:
+        return vote_stats(self)
+
+
+def vote_stats(index: "BlockIndex") -> dict:
+    """spdp_blk_vote_stats: which paths the vote kernel took on this index since it was created (abi.BLK_VOTE_STATS)"""
+    from . import abi
+    v = (C.c_int64 * len(abi.BLK_VOTE_STATS))()
+    index.eng._check(index.lib.spdp_blk_vote_stats(index.eng.ctx, index.h, v, len(abi.BLK_VOTE_STATS)), "spdp_blk_vote_stats")
+    return dict(zip(abi.BLK_VOTE_STATS, (int(x) for x in v)))
 
 
 def split_record(rec: np.ndarray):

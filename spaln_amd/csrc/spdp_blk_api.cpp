@@ -59,6 +59,7 @@ struct SpdpBlkIndex {
     uint32_t lds_bytes = 0;
     BlkFindsKept* finds_kept = nullptr;         // what the finds vote keeps between calls (spdp_blk_finds_api.cpp)
     int64_t n_words = 0;                        // entries of blkb as uploaded
+    int64_t vote_stats[SPDP_BLK_VOTE_STATS] = {0};     // the path counters of slabs that have been given up (spdp_blk_vote_stats adds the live ones)
     ~SpdpBlkIndex()
     {
         delete finds_kept;
@@ -225,13 +226,29 @@ const BlkDev* spdp_blk_index_on_device(SpdpBlkIndex* ix)
     return ix->d_dev;
 }
 
+static_assert(SPDP_BLK_VOTE_STATS == SPDP_BLK_VOTE_STATS_N && 8 + 8 * SPDP_BLK_VOTE_STATS <= SPDP_BLK_SLAB_HEADER, "the slab header holds every counter the header file names");
+// the path counters of the live slabs, added to `sum`
+static int add_slab_stats(SpdpContext* ctx, const SpdpBlkIndex* ix, int64_t* sum)
+{
+    if (!ix->slabs || !ix->n_waves) return 0;
+    std::vector<uint64_t> h((size_t) ix->n_waves * SPDP_BLK_VOTE_STATS);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy2D(h.data(), sizeof(uint64_t) * SPDP_BLK_VOTE_STATS, ix->slabs + 8, ix->slab_bytes, sizeof(uint64_t) * SPDP_BLK_VOTE_STATS,
+                       (size_t) ix->n_waves, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) sum[i % SPDP_BLK_VOTE_STATS] += (int64_t) h[i];
+    return 0;
+}
+
 static int ensure_waves(SpdpContext* ctx, SpdpBlkIndex* ix, int n)
 {
     int want = pick_waves(ctx, ix->slab_bytes, ix->lds_bytes);
     want = std::min(want, std::max(1, n));
     if (!ix->next) { HIPCHK(hipMalloc((void**) &ix->next, 16)); }
     if (want <= ix->n_waves) return 0;
-    if (ix->slabs) { (void) hipFree(ix->slabs); ix->slabs = nullptr; }
+    if (ix->slabs) {
+        if (add_slab_stats(ctx, ix, ix->vote_stats)) return -1;     // (what the smaller set of slabs has counted is kept)
+        (void) hipFree(ix->slabs); ix->slabs = nullptr;
+    }
     ix->n_waves = 0;
     HIPCHK(hipMalloc((void**) &ix->slabs, (size_t) want * ix->slab_bytes));
     HIPCHK(hipMemsetAsync(ix->slabs, 0, (size_t) want * ix->slab_bytes, ctx->stream));     // (tags of no query: every score slot reads as zero)
@@ -266,16 +283,23 @@ extern "C" int spdp_blk_vote_resident(SpdpContext* ctx, const SpdpBlkIndex* cix,
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-    if (getenv("SPDP_BLK_VERBOSE")) {                  // how often the run hash met a full table (one-lane path) and grew, over the slabs' lifetime
-        uint64_t slow = 0, grown = 0;
-        for (int w = 0; w < A.n_waves; ++w) {
-            uint32_t h[4];
-            HIPCHK(hipMemcpy(h, ix->slabs + (size_t) w * ix->slab_bytes, sizeof h, hipMemcpyDeviceToHost));
-            slow += h[1]; grown += h[2];
-        }
-        fprintf(stderr, "[blk] %d queries on %d waves: so far %llu entries took the one-lane path, %llu table growths\n", n, A.n_waves,
-                (unsigned long long) slow, (unsigned long long) grown);
+    if (getenv("SPDP_BLK_VERBOSE")) {                  // how often the run hash met a full table (one-lane path) and grew, since the index was made
+        int64_t v[SPDP_BLK_VOTE_STATS];
+        if (spdp_blk_vote_stats(ctx, ix, v, SPDP_BLK_VOTE_STATS)) return -1;
+        fprintf(stderr, "[blk] %d queries on %d waves: so far %lld entries took the one-lane path, %lld run-hash growths\n", n, A.n_waves,
+                (long long) v[BLK_VS_LANE_ENTRIES], (long long) v[BLK_VS_HASH_GROWTHS]);
     }
+    return 0;
+}
+
+extern "C" int spdp_blk_vote_stats(SpdpContext* ctx, const SpdpBlkIndex* ix, int64_t* out, int n)
+{
+    if (!ctx || !ix || !out || ix->ctx != ctx) return -1;
+    (void) hipSetDevice(ctx->device);
+    int64_t v[SPDP_BLK_VOTE_STATS];
+    for (int i = 0; i < SPDP_BLK_VOTE_STATS; ++i) v[i] = ix->vote_stats[i];
+    if (add_slab_stats(ctx, ix, v)) return -1;
+    for (int i = 0; i < n; ++i) out[i] = i < SPDP_BLK_VOTE_STATS ? v[i] : 0;
     return 0;
 }
 
@@ -300,6 +324,7 @@ extern "C" int spdp_blk_vote(SpdpContext* ctx, const SpdpBlkIndex* ix, const uin
     HIPCHK(hipMalloc(&d_l.p, (size_t) n * 4)); HIPCHK(hipMalloc(&d_r.p, (size_t) n * 4));
     if (stop_at) HIPCHK(hipMalloc(&d_s.p, (size_t) n * 4));
     HIPCHK(hipMalloc(&d_out.p, (size_t) n * out_cap * 4));
+    HIPCHK(hipMemsetAsync(d_out.p, 0, (size_t) n * out_cap * 4, ctx->stream));     // (what a record does not use reads as zero, not as an older call's)
     std::vector<int64_t> rel(n + 1);
     for (int i = 0; i <= n; ++i) rel[i] = offs[i] - offs[0];
     HIPCHK(hipMemcpyAsync(d_codes.p, codes + offs[0], nb, hipMemcpyHostToDevice, ctx->stream));

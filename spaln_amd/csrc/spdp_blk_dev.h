@@ -13,6 +13,14 @@
 #define SPDP_BLK_RES_CAP 2048            // query residues a wave keeps in LDS (longer queries are read where they lie)
 #define SPDP_BLK_HASH_LEVELS 4          // the run hash may grow three times (x ~8) before a query is reported as SPDP_BLK_TABLE
 
+// A wave's slab opens with a header: the query tag it has come to (word 0), and from byte 8 the path counters of every query
+// the wave has served, 64 bits each.  spdp_blk_vote_stats sums them over the waves (the order of the BLK_VS_* numbers below and of abi.BLK_VOTE_STATS).
+#define SPDP_BLK_SLAB_HEADER 128
+#define SPDP_BLK_VOTE_STATS 13
+enum { BLK_VS_QUERIES, BLK_VS_ZERO_ENDED, BLK_VS_LDS_MERGES, BLK_VS_LANE_MERGES, BLK_VS_SPLITS,
+       BLK_VS_LANE_ENTRIES, BLK_VS_HASH_GROWTHS, BLK_VS_HITS_GROWTHS, BLK_VS_RUNS_GROWTHS, BLK_VS_WIPES, BLK_VS_HBM_QUERIES,
+       BLK_VS_NO_PREFETCH, BLK_VS_TABLE };
+
 struct BlkDev {                         // the index and the search parameters (pointers into HBM on the device side)
     int32_t nalpha, tabsize, nshift, nbitpat, convts, n_chr, kk, drna, maxmmc, nseg, minsigpr, ncand, nascr;
     int32_t maxblock, extblock, extblockl, shortquery, hh_size1, hh_size2, hb_size1, hb_size2, ha_size1, ha_size2, gdb;

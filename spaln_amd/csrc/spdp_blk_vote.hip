@@ -39,7 +39,9 @@ constexpr int OWN_SLOTS = 256;                      // owner marks, slot number 
 constexpr uint32_t NOBODY = 0xffffffffu;
 // status words of the wave (LDS)
 enum { ST_SIGN = 0, ST_MMCT = 4, ST_NHIT = 8, ST_MAXS = 12, ST_TESTWORD = 16, ST_MAXBSCR = 20, ST_QA_FRONT = 24, ST_QB_FRONT = 28,
-       ST_HH_LEVEL = 32, ST_TROUBLE = 33, ST_Q_LEVEL = 40 /* 8: the position tables' levels */, ST_WORDS = 64 };
+       ST_HH_LEVEL = 32, ST_TROUBLE = 33, ST_Q_LEVEL = 40 /* 8: the position tables' levels */,
+       ST_PATHS = 48 /* SPDP_BLK_VOTE_STATS: which paths this query took (spdp_blk_dev.h, BLK_VS_*) */, ST_WORDS = 64 };
+static_assert(ST_PATHS + SPDP_BLK_VOTE_STATS < ST_WORDS, "the path counters sit below the stand-in flag");
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint32_t uniu(uint32_t x) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) x); }
@@ -104,12 +106,13 @@ struct RunHash {
         const KV z = {0u, 0};
         for (uint32_t i = lane_id(); i < size.n; i += 64) { if (in_lds()) lds[i] = z; else glob[i] = z; }
     }
-    __device__ __forceinline__ void new_phase()                     // all lanes, uniform
+    __device__ __forceinline__ bool new_phase()                     // all lanes, uniform.  -> the table was wiped
     {
-        if (epochs && ++epoch < 256) return;
+        if (epochs && ++epoch < 256) return false;
         wipe();
         if (epochs) epoch = 1;
         wave_sync();
+        return true;
     }
 };
 
@@ -210,7 +213,7 @@ struct SlowHash {
 // replace = true over Dhash<INT,int>(.., -1): src/clib.h:570-688).  The table is probed like the run hash and entries leave it by
 // being marked empty, so a block CAN be lost from sight and entered twice: kept as it is, results depend on it.
 struct BestOf {
-    KV* heap; KV* place; int cap; Modulus size; uint32_t step_mod; int* front; int* trouble;
+    KV* heap; KV* place; int cap; Modulus size; uint32_t step_mod; int* front; int* trouble; int* grows;
     KV* level0; KV* grown; uint32_t b_off; const int32_t* sizes; int* level;      // the table's home in LDS, its larger forms in the slab
     __device__ __forceinline__ uint32_t stride(uint32_t key) const { return step_mod - ((step_mod & (step_mod - 1)) ? key % step_mod : (key & (step_mod - 1))); }
     __device__ __forceinline__ uint32_t next(uint32_t s, uint32_t u) const { s += u; while (s >= size.n) s -= size.n; return s; }
@@ -241,6 +244,7 @@ struct BestOf {
         const KV* old = place;
         const uint32_t n_old = size.n;
         bind(++*level);
+        ++*grows;
         for (uint32_t i = 0; i < size.n; ++i) place[i] = KV{0u, -1};
         for (uint32_t i = 0; i < n_old; ++i) {
             const KV kv = old[i];
@@ -446,6 +450,7 @@ struct Wave {
         KV* g = qh_grown + (size_t) d * qh_grown_words;
         Q.grown = g; Q.b_off = (uint32_t) Q.sizes[SPDP_BLK_HASH_LEVELS - 1];
         Q.step_mod = qh_step; Q.front = st + ST_QA_FRONT + d; Q.trouble = st + ST_TROUBLE; Q.level = st + ST_Q_LEVEL + d;
+        Q.grows = st + ST_PATHS + BLK_VS_HITS_GROWTHS;
         Q.bind(*Q.level);
         return Q;
     }
@@ -457,15 +462,18 @@ struct Wave {
         KV* g = qr_grown + (size_t) d * qr_grown_words;
         Q.grown = g; Q.b_off = (uint32_t) Q.sizes[SPDP_BLK_HASH_LEVELS - 1];
         Q.step_mod = qr_step; Q.front = st + ST_QB_FRONT + d; Q.trouble = st + ST_TROUBLE; Q.level = st + ST_Q_LEVEL + 4 + d;
+        Q.grows = st + ST_PATHS + BLK_VS_RUNS_GROWTHS;
         Q.bind(*Q.level);
         return Q;
     }
     RunHash hh;
-    Score* score; uint32_t* stage; int32_t* scratch; uint32_t* header;
+    Score* score; uint32_t* stage; int32_t* scratch; uint32_t* header; u64* stats;
+    __device__ __forceinline__ void took(int path, int n = 1) const { if (lane_id() == 0) st[ST_PATHS + path] += n; }     // this query's path counters
     uint8_t* res; int res_cap;
     uint32_t* mrg;                                      // two posting lists and their merge (512 words)
     uint32_t* pre;                                      // the first 64 entries of the posting lists of a direction's phases (fetched together)
     uint32_t tag;
+    int n_splits;                                       // groups a chunk's updates were split into beyond its first, this query
 };
 
 struct Pair { int32_t bscr, chr; uint32_t lb, rb, ub, db, zl, zr; int32_t rvs; };
@@ -653,6 +661,8 @@ __device__ __forceinline__ const uint32_t* entries_of(const Wave& W, const Word&
             if (za) na = min(na, i - me + first_lane(za));
             if (zb) nb = min(nb, i - me + first_lane(zb));
         }
+        W.took(BLK_VS_LDS_MERGES);
+        if (na < w.len0 || nb < w.len1) W.took(BLK_VS_ZERO_ENDED, (na < w.len0) + (nb < w.len1));
         auto below = [](const uint32_t* L, int n, uint32_t x, bool or_equal) {        // entries of L below x (or up to x)
             int lo = 0, hi = n;
             while (lo < hi) { const int mid = (lo + hi) >> 1; const uint32_t v = L[mid]; if (v < x || (or_equal && v == x)) lo = mid + 1; else hi = mid; }
@@ -685,13 +695,17 @@ __device__ __forceinline__ const uint32_t* entries_of(const Wave& W, const Word&
     if (me == 0) {
         const uint32_t* a = X.blkb + w.off0; const uint32_t* b = X.blkb + w.off1;
         int i = 0, j = 0;
-        while (i < w.len0 || j < w.len1) {
-            const uint32_t x = i < w.len0 ? a[i] : 0xffffffffu, y = j < w.len1 ? b[j] : 0xffffffffu;
+        int na = w.len0, nb = w.len1;
+        while (i < na || j < nb) {
+            const uint32_t x = i < na ? a[i] : 0xffffffffu, y = j < nb ? b[j] : 0xffffffffu;
+            // (a zero ends ITS list, the other one goes on: the reference's merge takes a front of 0 for a list that is through)
+            if (!x) { na = i; W.took(BLK_VS_ZERO_ENDED); continue; }
+            if (!y) { nb = j; W.took(BLK_VS_ZERO_ENDED); continue; }
             const uint32_t m = x < y ? x : y;
-            if (!m) break;                              // (a zero ends a list)
             W.stage[k++] = m;
             i += x == m; j += y == m;
         }
+        W.took(BLK_VS_LANE_MERGES);
     }
     wave_sync();
     n = uni(k);
@@ -713,7 +727,7 @@ __device__ __forceinline__ int vote_of_word(Wave& W, const Word& w, int d, int s
         bool have = c0 + me < n_all;
         const uint32_t blk = have ? ((fetched && c0 == 0) ? W.pre[sft * 64 + me] : list[c0 + me]) : 0u;
         const u64 zeros = __ballot(have && blk == 0);
-        if (zeros) { have = have && me < first_lane(zeros); n_all = 0; }        // a zero ends the list
+        if (zeros) { have = have && me < first_lane(zeros); n_all = 0; W.took(BLK_VS_ZERO_ENDED); }        // a zero ends the list
         // every hit counts for the block's total, and the totals' best-of list sees every one of them
         int total = 0, run_ahead = 0;                   // (the block's run score fetched in the same round trip: it is the one credited, mostly)
         if (have) {
@@ -728,6 +742,7 @@ __device__ __forceinline__ int vote_of_word(Wave& W, const Word& w, int d, int s
         // the run hash: snapshot, marks, commit the lanes below the first meeting
         u64 pend = __ballot(have);
         while (pend) {
+            if (!first_group) ++W.n_splits;                 // (uniform: a scalar register, written once per query)
             const bool mine = (pend >> me) & 1;
             Found a = {0, 0, false}, b = {0, 0, false};
             bool ask = false;
@@ -770,7 +785,7 @@ __device__ __forceinline__ int vote_of_word(Wave& W, const Word& w, int d, int s
             if (!done) {
                 // the lowest pending lane met a full table: its entry alone, with the table growing under it
                 const int l = first_lane(pend);
-                if (me == l) { RunHash T = H; SlowHash S = {&T, W.st}; credited = S.entry(blk, p, up); W.header[1] += 1; W.header[2] += (uint32_t) (T.level - H.level); W.st[ST_HH_LEVEL] = T.level; }
+                if (me == l) { RunHash T = H; SlowHash S = {&T, W.st}; credited = S.entry(blk, p, up); W.st[ST_PATHS + BLK_VS_LANE_ENTRIES] += 1; W.st[ST_PATHS + BLK_VS_HASH_GROWTHS] += T.level - H.level; W.st[ST_HH_LEVEL] = T.level; }
                 wave_sync();
                 const int lv = uni(W.st[ST_HH_LEVEL]);
                 if (lv != H.level) H.bind(lv);              // (every lane alike: the table's place and size stay uniform)
@@ -832,6 +847,7 @@ __device__ __forceinline__ int scan(Wave& W, const uint8_t* q, int q_len, int le
     const bool res_fits = q_len <= W.res_cap;
     if (res_fits) for (int i = me; i < q_len; i += 64) { const int c = q[i]; W.res[i] = c < X.convts ? X.convtab[c] : (uint8_t) 255; }
     lds_sync();
+    if (!res_fits) W.took(BLK_VS_HBM_QUERIES);
     Speller sp = {&X, q, q_len, right, res_fits ? W.res : nullptr};
     const bool is_short = qlen < X.shortquery;
     const int base = X.rscrtab[0];
@@ -850,6 +866,7 @@ __device__ __forceinline__ int scan(Wave& W, const uint8_t* q, int q_len, int le
             if (me < nshift) mine = sp.at(W.as[d * 32 + me], d);
             // ... and the head of every phase's posting list, all in flight together (one list: nothing to merge)
             const bool fetch = nshift <= SPDP_BLK_PRE_PHASES;
+            if (!fetch) W.took(BLK_VS_NO_PREFETCH);
             if (fetch) {
                 uint32_t head[SPDP_BLK_PRE_PHASES];
                 #pragma unroll
@@ -866,7 +883,7 @@ __device__ __forceinline__ int scan(Wave& W, const uint8_t* q, int q_len, int le
             for (int sft = 0; sft < nshift; ++sft) {
                 const int ms = is_short ? (up ? left : right) : W.as[e * 32 + sft];
                 int cscr = 0, more = 0, p = 0;
-                W.hh.new_phase();
+                if (W.hh.new_phase()) W.took(BLK_VS_WIPES);
                 bool first = true;
                 do {
                     const int ss = W.as[d * 32 + sft];
@@ -948,7 +965,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     W.qr_mem = (KV*) l; l += 2 * 4 * (size_t) W.qr_words;
     // ---- the wave's slab
     uint8_t* g = A.slabs + (size_t) blockIdx.x * A.slab_bytes;
-    W.header = (uint32_t*) g; g += 16;
+    W.header = (uint32_t*) g; W.stats = (u64*) (g + 8); g += SPDP_BLK_SLAB_HEADER;
     W.score = (Score*) g; g += sizeof(Score) * (4 * (size_t) X.nseg + 2);
     RunHash& H = W.hh;
     H.sizes = X.hh_sizes; H.step_mod = (uint32_t) X.hh_size2;
@@ -984,6 +1001,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
         const int64_t o = A.offs[qi];
         const int len = (int) (A.offs[qi + 1] - o);
         int calls = 0;
+        W.n_splits = 0;
         const int reached = scan(W, A.codes + o, len, A.left[qi], A.right[qi], A.stop_at ? A.stop_at[qi] : 0, calls);
         wave_sync();
         Record R = {A.out + (size_t) qi * A.out_cap, A.out_cap, 3, false};
@@ -994,6 +1012,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
             if (A.out_cap > 1) R.out[1] = calls;
             if (A.out_cap > 2) R.out[2] = (reached ? SPDP_BLK_REACHED : 0) | (R.cut ? SPDP_BLK_CUT : 0) | (W.st[ST_TROUBLE] & ~3) |
                                           (reached == 2 ? SPDP_BLK_FORCED : 0);
+            // which paths the query took, into the slab's header (spdp_blk_vote_stats sums the waves')
+            W.st[ST_PATHS + BLK_VS_QUERIES] = 1;
+            W.st[ST_PATHS + BLK_VS_SPLITS] = W.n_splits;
+            W.st[ST_PATHS + BLK_VS_TABLE] = (W.st[ST_TROUBLE] & SPDP_BLK_TABLE) ? 1 : 0;
+            for (int k = 0; k < SPDP_BLK_VOTE_STATS; ++k) W.stats[k] += (u64) (uint32_t) W.st[ST_PATHS + k];
         }
         wave_sync();
     }
@@ -1012,7 +1035,7 @@ extern "C" uint32_t spdp_blk_vote_lds_bytes(const BlkDev* ix, int hh_in_lds)
 }
 extern "C" size_t spdp_blk_vote_slab_bytes(const BlkDev* ix, int hh_in_lds)
 {
-    size_t b = 16 + sizeof(Score) * (4 * (size_t) ix->nseg + 2);
+    size_t b = SPDP_BLK_SLAB_HEADER + sizeof(Score) * (4 * (size_t) ix->nseg + 2);
     if (!hh_in_lds) b += sizeof(KV) * (size_t) ix->hh_sizes[0];
     b += sizeof(KV) * ((size_t) ix->hh_sizes[SPDP_BLK_HASH_LEVELS - 1] + (size_t) ix->hh_sizes[SPDP_BLK_HASH_LEVELS - 2]);
     b += sizeof(KV) * 4 * ((size_t) ix->hb_sizes[SPDP_BLK_HASH_LEVELS - 1] + ix->hb_sizes[SPDP_BLK_HASH_LEVELS - 2] +

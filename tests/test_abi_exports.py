@@ -29,7 +29,8 @@ def test_library_exports_all_declared_symbols():
     assert hasattr(engine.Engine, "signal_records_s") and hasattr(engine.Engine, "signal_records_h")
     # the HSP search's request path and the block search's counters (tests/test_hsp_cases.py, tests/test_gpu_hsp_cases.py)
     from spaln_amd import blocks
-    for name, wrapper in (("spdp_hsp_plan", "hsp_plan"), ("spdp_hsp_tasks", "hsp_tasks"), ("spdp_hsp_tasks_host", "hsp_tasks_host"), ("spdp_blk_find_stats", "find_stats")):
+    for name, wrapper in (("spdp_hsp_plan", "hsp_plan"), ("spdp_hsp_tasks", "hsp_tasks"), ("spdp_hsp_tasks_host", "hsp_tasks_host"), ("spdp_blk_find_stats", "find_stats"),
+                          ("spdp_blk_vote_stats", "vote_stats")):
         assert name in _declared() and name in engine.EXPORTS and hasattr(lib, name) and hasattr(blocks, wrapper)
 
 
@@ -38,6 +39,10 @@ def test_hsp_entries_refuse_null_arguments():
     lib = engine.load_library()
     assert lib.spdp_hsp_tasks(None, None, None, None, None, None, None) == -1
     assert lib.spdp_blk_find_stats(None, None, 0) == -1
+    assert lib.spdp_blk_vote_stats(None, None, None, 0) == -1
+    # the binding names as many fields as the header declares
+    n = int(re.search(r"#define SPDP_BLK_VOTE_STATS_N (\d+)", open(os.path.join(ROOT, "include", "spdp.h")).read()).group(1))
+    assert len(abi.BLK_VOTE_STATS) == n == len(set(abi.BLK_VOTE_STATS))
     err = C.create_string_buffer(128)
     assert lib.spdp_hsp_tasks_host(None, None, None, None, err, 128) == -1 and b"null argument" in err.value
     assert lib.spdp_hsp_plan(None, 1, 17, 17, 1, 1, None, err, 128) == -1 and b"null argument" in err.value
