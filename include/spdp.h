@@ -1075,6 +1075,35 @@ typedef struct SpdpBlkBuildParamsP {
 int spdp_blk_build_params_default_p(int64_t fasta_bytes, SpdpBlkBuildParamsP* p);
 SpdpBlkIndexHost* spdp_blk_index_build_p(SpdpContext* ctx, const SpdpGenome* genome, const SpdpBlkBuildParamsP* p,
                                          const SpdpBlkSearchOpts* opts, double* seconds);
+/* The amino-acid index of a protein database, `spaln -W -KA prot.faa` (<db>.bka: what spdp_blk_finds and spdp_map_align_b search):
+ * makeblock with PreScan::lenStat (src/blksrc.cc:766-820), MakeBlk::idxblk with Block::c2w (:448-464), blkscrtab(segn, blksz)
+ * (:944-997).  blklen is the longest sequence, so ONE BLOCK IS ONE SEQUENCE: the word state starts afresh at every sequence start and
+ * every flawless word counts.  db: the SpdpGenome spdp_map_align_b takes, sequence i = codes[chr_off[i] .. chr_off[i + 1]).  convtab
+ * gives a residue code its class (< nalpha), the ambiguous class (= nalpha: it ends the run of residues words are cut from) or marks
+ * it as a residue the program's scan skips (> nalpha): those are dropped from the copy that is uploaded -- they break no word and
+ * count neither in glen nor in a sequence's length.  The program's scan decides by the LETTER (ReducWord's a2r): X and U are ambiguous,
+ * J has the class of S, B / Z / O are skipped; its ConvTab gives the CODE 24 (Sec and Glx share it) the class nalpha + 1.  A caller
+ * that wants the program's file therefore passes U as the ambiguous code 2, J as Ser, and B / Z / O as 23 / 24 / 24.
+ * b.ktuple 3 .. 7, b.nbitpat = 1, b.bitpat of weight k (2^k - 1: contiguous), b.blklen: ignored, the build sets it.
+ * ContBlk::MaxBlk: the program only ever raises it, from what its heap held (ContBlk::ContBlk leaves it unset), and its files carry
+ * numbers beyond any list; the index built here carries the longest kept list.
+ * Refused by name: null arguments, k or nalpha out of range, nbitpat != 1, a pattern whose weight is not k, nshift outside 1 ..
+ * SPDP_BLK_MAX_SHIFT, a code at or beyond convts, offsets that do not start at 0 or decrease, more than 2^32 - 1 residues, a sequence
+ * with no counted residue (the program writes a ChrID entry without a block for it; the search takes block b to be sequence b), a word
+ * in more than 65 535 sequences, more postings than blkp can address. */
+typedef struct SpdpBlkBuildParamsA {
+    SpdpBlkBuildParams b;
+    int32_t nalpha;                  /* 6 .. 20                                                                              */
+    int32_t convts;                  /* entries of convtab (26 for the amino-acid codes)                                     */
+    uint8_t convtab[32];             /* residue code -> class (< nalpha) | nalpha: ambiguous | > nalpha: skipped by the scan  */
+} SpdpBlkBuildParamsA;
+/* what `spaln -W -KA` picks for a database of total_residues counted residues (k from 0.30 ln(total), 3 .. 6; Nshift = k; twenty
+ * classes; MaxGene from its square root) and the ConvTab it writes (the entries it never assigns -- 0, 1, 2, 23 -- as described
+ * above).  0, or -1. */
+int spdp_blk_build_params_default_a(int64_t total_residues, SpdpBlkBuildParamsA* p);
+/* opts NULL: the defaults with genomic_db = 0.  seconds as in spdp_blk_index_build ([1] includes the pass that drops residues). */
+SpdpBlkIndexHost* spdp_blk_index_build_a(SpdpContext* ctx, const SpdpGenome* db, const SpdpBlkBuildParamsA* p,
+                                         const SpdpBlkSearchOpts* opts, double* seconds);
 /* the index as the reference's file (format version 26; the five pointers of its header, which the reference writes as its
  * heap held them, as zeros; ConvTab entries the reference leaves unset as "ambiguous"): 0, or -1 */
 int spdp_blk_index_write(const SpdpBlkIndexHost* h, const char* path);

@@ -413,6 +413,72 @@ def build_index_p(eng, genome_codes, chr_off, prm: BlkBuildParamsP, write_to: st
     return out, list(sec)
 
 
+class BlkBuildParamsA(C.Structure):      # SpdpBlkBuildParamsA
+    _fields_ = [("b", BlkBuildParams), ("nalpha", C.c_int32), ("convts", C.c_int32), ("convtab", C.c_uint8 * 32)]
+
+
+def build_params_default_a(lib, total_residues: int) -> BlkBuildParamsA:
+    """what `spaln -W -KA` picks for a protein database of that many counted residues, and the ConvTab it writes
+    (spdp_blk_build_params_default_a)"""
+    p = BlkBuildParamsA()
+    lib.spdp_blk_build_params_default_a.argtypes = [C.c_int64, C.c_void_p]
+    if lib.spdp_blk_build_params_default_a(int(total_residues), C.byref(p)):
+        raise RuntimeError("spdp_blk_build_params_default_a: out of range")
+    return p
+
+
+def build_index_a(eng, codes, offs, prm: BlkBuildParamsA, write_to: str = None, max_out: int = 1, local: int = 0, cross_species: bool = True):
+    """spdp_blk_index_build_a (+ spdp_blk_index_write): the amino-acid index of a protein database (`spaln -W -KA`, <db>.bka) made on
+    the device; codes / offs: the database as map_align_b takes it.  Returns what read_protein_db_index returns of the program's file
+    (the arrays for BlockIndex, abi.BlkFindsParams -- None when the index has no average word score) and the seconds [device, host,
+    call]."""
+    from . import abi, defaults
+    lib = eng.lib
+    g = Genome()
+    gc = np.ascontiguousarray(codes, dtype=np.uint8)
+    go = np.ascontiguousarray(offs, dtype=np.int64)
+    g.codes, g.chr_off, g.n_chr = gc.ctypes.data, go.ctypes.data, len(go) - 1
+    o = SearchOpts()
+    lib.spdp_blk_search_opts_default(C.byref(o))
+    for k, v in defaults.search_opts_protein_db(max_out, local, cross_species).items():
+        setattr(o, k, v)
+    sec = (C.c_double * 3)()
+    lib.spdp_blk_index_build_a.restype = C.c_void_p
+    lib.spdp_blk_index_build_a.argtypes = [C.c_void_p] * 5
+    lib.spdp_blk_index_host_free.argtypes = [C.c_void_p]
+    lib.spdp_blk_finds_params_default.restype = C.c_int
+    lib.spdp_blk_finds_params_default.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    h = lib.spdp_blk_index_build_a(eng.ctx, C.byref(g), C.byref(prm), C.byref(o), sec)
+    if not h:
+        raise RuntimeError(lib.spdp_last_error(eng.ctx).decode())
+    try:
+        if write_to is not None:
+            lib.spdp_blk_index_write.argtypes = [C.c_void_p, C.c_char_p]
+            if lib.spdp_blk_index_write(h, write_to.encode()):
+                raise RuntimeError("spdp_blk_index_write: cannot write " + write_to)
+        fprm = abi.BlkFindsParams()
+        if lib.spdp_blk_finds_params_default(h, int(max_out), int(local), C.byref(fprm)):
+            fprm = None                                 # (no word kept its list -- a database of one sequence: nothing to search with)
+        out = _host_index_to_dict(lib, h)
+    finally:
+        lib.spdp_blk_index_host_free(h)
+    return out, fprm, list(sec)
+
+
+def bka_without_heap_bytes(raw: bytes) -> bytes:
+    """a <db>.bka with the bytes zeroed in which the program's files hold its heap, to compare a built file with the program's: the
+    five pointers of ContBlk, the padding behind ConvTS, ContBlk::MaxBlk (only ever raised, from what the heap held) and the ConvTab
+    entries ReducWord never assigns (0, 1, 2 and 23)"""
+    b = bytearray(raw)
+    convts = struct.unpack_from("<I", raw, 36)[0]
+    for lo, hi in ((36 + 48, 36 + 88), (40, 44), (36 + 42, 36 + 44)):
+        b[lo:hi] = bytes(hi - lo)
+    for i in (0, 1, 2, 23):
+        if i < convts:
+            b[len(b) - convts + i] = 0
+    return bytes(b)
+
+
 class BlkFindParams(C.Structure):        # SpdpBlkFindParams
     _fields_ = [("vthr", C.c_int32), ("drop_rate", C.c_float), ("max_out", C.c_int32), ("max_out2", C.c_int32),
                 ("min_agap", C.c_int32), ("phase1t", C.c_int32), ("a_exgl", C.c_int32), ("a_exgr", C.c_int32)]

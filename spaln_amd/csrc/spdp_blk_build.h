@@ -4,6 +4,7 @@
 #define SPDP_BLK_BUILD_H
 #include <stdint.h>
 #include <vector>
+#include "spdp_blk_build_a.h"
 
 struct SpdpContext;
 struct BlkBuildArgs {
@@ -29,7 +30,20 @@ struct BlkBuildArgsP {
     uint32_t* tcount;
     unsigned long long* keys; unsigned long long* n_keys; unsigned long long cap;
 };
+// the amino-acid index of a protein database (`spaln -W -KA`): one block per sequence, words of base R.nalpha
+struct BlkBuildArgsA {
+    const uint8_t* codes; const int64_t* seq_off;   // sequence s = codes[seq_off[s] .. seq_off[s + 1]), none empty; its block is s + 1
+    int n_seq;
+    int64_t G;
+    BlkRuleA R;
+    uint32_t tabsize;
+    const int64_t* tile_carry;                  // the last ambiguous residue before a tile (-1: none)
+    uint32_t* tcount;
+    unsigned long long* keys; unsigned long long* n_keys; unsigned long long cap;
+};
 struct BlkBuildDev;
+int spdp_blkidx_words_a(SpdpContext* ctx, const uint8_t* codes, const int64_t* seq_off, int n_seq, BlkBuildArgsA A, int key_bits,
+                        std::vector<uint32_t>& tcount, std::vector<uint32_t>& cnt, BlkBuildDev** out);
 int spdp_blkidx_words_p(SpdpContext* ctx, const uint8_t* codes, const int64_t* chr_off, const int32_t* chr_first, int n_chr,
                         BlkBuildArgsP A, int key_bits, std::vector<uint32_t>& tcount, std::vector<uint32_t>& cnt, BlkBuildDev** out);
 int spdp_blkidx_words(SpdpContext* ctx, const uint8_t* codes, const int64_t* chr_off, const int32_t* chr_first, int n_chr,

@@ -365,6 +365,93 @@ __global__ __launch_bounds__(TPB) void blkidx_words_p(BlkBuildArgsP A)
     }
 }
 
+// ---- the amino-acid index of a protein database (`spaln -W -KA`; spdp_blk_build_a.h has the per-residue rule) ------------------
+// blkidx_tile_last / blkidx_words with three things changed: a residue's class comes from a table, a word is a number of base
+// nalpha, and a block is a sequence -- the thread walks the sequence offsets along with its 16 residues, of which a dozen-residue
+// sequence covers only some.
+struct ClassTable { uint8_t c[32]; };
+
+__global__ __launch_bounds__(TPB) void blkidx_tile_last_a(const uint8_t* __restrict__ codes, int64_t G, ClassTable ct, int nalpha,
+                                                          int64_t* __restrict__ tile_last)
+{
+    __shared__ uint8_t s_cls[32];
+    __shared__ int64_t s[TPB / 64];
+    if (threadIdx.x < 32) s_cls[threadIdx.x] = ct.c[threadIdx.x];
+    __syncthreads();
+    const int64_t t0 = (int64_t) blockIdx.x * TILE;
+    int64_t last = -1;
+    for (int i = threadIdx.x; i < TILE; i += TPB) {
+        const int64_t g = t0 + i;
+        if (g < G && blka_class(s_cls, nalpha, codes[g]) == nalpha) last = g;
+    }
+    for (int o = 32; o; o >>= 1) { const int64_t v = __shfl_xor(last, o); last = v > last ? v : last; }
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < TPB / 64; ++w) last = s[w] > last ? s[w] : last;
+        tile_last[blockIdx.x] = last;
+    }
+}
+
+__global__ __launch_bounds__(TPB) void blkidx_words_a(BlkBuildArgsA A)
+{
+    __shared__ uint8_t s_x[HALO + TILE];                             // classes of residues t0 - HALO .. t0 + TILE
+    __shared__ uint8_t s_cls[32];
+    __shared__ int64_t s_wave[TPB / 64];
+    const int nalpha = A.R.nalpha;
+    if (threadIdx.x < 32) s_cls[threadIdx.x] = A.R.cls[threadIdx.x];
+    __syncthreads();
+    const int64_t t0 = (int64_t) blockIdx.x * TILE;
+    for (int i = threadIdx.x; i < HALO + TILE; i += TPB) {
+        const int64_t g = t0 - HALO + i;
+        s_x[i] = (g >= 0 && g < A.G) ? (uint8_t) blka_class(s_cls, nalpha, A.codes[g]) : (uint8_t) nalpha;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p0 = t0 + (int64_t) threadIdx.x * PER;
+    // the last ambiguous residue before my first one: tiles before mine, threads before me
+    int64_t mine = -1;
+    for (int i = 0; i < PER; ++i) if (s_x[HALO + threadIdx.x * PER + i] == nalpha && p0 + i < A.G) mine = p0 + i;
+    int64_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) { const int64_t v = __shfl_up(incl, o); if (lane >= o && v > incl) incl = v; }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int64_t last = A.tile_carry[blockIdx.x];
+    for (int w = 0; w < wave; ++w) last = s_wave[w] > last ? s_wave[w] : last;
+    { const int64_t prev = __shfl_up(incl, 1); if (lane > 0 && prev > last) last = prev; }
+
+    // my sequence: the last c with seq_off[c] <= p0 (no sequence is empty)
+    int c = 0;
+    {
+        int lo = 0, hi = A.n_seq;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.seq_off[mid] <= p0) lo = mid; else hi = mid; }
+        c = lo;
+    }
+    int64_t c_lo = A.seq_off[c], c_hi = A.seq_off[c + 1];
+    for (int i = 0; i < PER; ++i) {
+        const int64_t g = p0 + i;
+        const bool in = g < A.G;
+        if (in) while (g >= c_hi && c + 1 < A.n_seq) { ++c; c_lo = c_hi; c_hi = A.seq_off[c + 1]; }
+        const int xi = HALO + threadIdx.x * PER + i;
+        if (in && s_x[xi] == nalpha) last = g;
+        const BlkWordA o = blka_word(A.R, s_x + xi, g, c_lo, last);
+        if (in && o.flawless) atomicAdd(A.tcount + o.word, 1u);
+        const bool emit = in && o.emit;
+        // one counter bump per wave
+        const unsigned long long m = __ballot(emit);
+        if (m) {
+            unsigned long long base = 0;
+            const int leader = __ffsll((long long) m) - 1;
+            if (lane == leader) base = atomicAdd(A.n_keys, (unsigned long long) __popcll(m));
+            base = ((unsigned long long) (unsigned) __shfl((int) (base >> 32), leader) << 32) | (unsigned) __shfl((int) base, leader);
+            if (emit) {
+                const unsigned long long at = base + __popcll(m & ((1ull << lane) - 1));
+                if (at < A.cap) A.keys[at] = ((unsigned long long) o.word << 32) | (unsigned) (c + 1);
+            }
+        }
+    }
+}
+
 // flag[i] = key i opens a (word, block) entry; cnt[word] = entries of the word
 __global__ void blkidx_heads(const unsigned long long* __restrict__ keys, int64_t n, uint32_t* __restrict__ cnt, uint8_t* __restrict__ flag)
 {
@@ -543,6 +630,60 @@ int spdp_blkidx_words_p(SpdpContext* ctx, const uint8_t* codes, const int64_t* c
         HIPCHK(hipStreamSynchronize(st));
         if (n_keys <= cap) break;
         if (round) { ctx->err = "spdp_blk_index_build_p: key count changed between two passes"; return -1; }
+        cap = n_keys;
+    }
+    if (blkidx_finish_keys(ctx, d, n_keys, key_bits, tabsize, tcount, cnt)) return -1;
+    guard.keep = true;
+    *out = d;
+    return 0;
+}
+
+// pass 1 of the amino-acid index: as spdp_blkidx_words, a block being a sequence of the database
+int spdp_blkidx_words_a(SpdpContext* ctx, const uint8_t* codes, const int64_t* seq_off, int n_seq, BlkBuildArgsA A, int key_bits,
+                        std::vector<uint32_t>& tcount, std::vector<uint32_t>& cnt, BlkBuildDev** out)
+{
+    (void) hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    if (A.R.width > HALO || A.R.weight > BLKA_MAX_K) { ctx->err = "spdp_blk_index_build_a: a pattern beyond the kernel's halo"; return -1; }
+    BlkBuildDev* d = new BlkBuildDev;
+    struct Guard { BlkBuildDev*& d; bool keep = false; ~Guard() { if (!keep) { delete d; d = nullptr; } } } guard{d};
+    const int64_t G = A.G;
+    const int64_t n_tiles = (G + TILE - 1) / TILE;
+    const uint32_t tabsize = A.tabsize;
+    d->tabsize = tabsize;
+    HIPCHK(d->codes.get((size_t) G)); HIPCHK(d->chr_off.get(sizeof(int64_t) * ((size_t) n_seq + 1)));
+    HIPCHK(d->tile_last.get(sizeof(int64_t) * n_tiles)); HIPCHK(d->tcount.get(sizeof(uint32_t) * (size_t) tabsize));
+    HIPCHK(d->cnt.get(sizeof(uint32_t) * (size_t) tabsize)); HIPCHK(d->n_keys.get(sizeof(unsigned long long)));
+    HIPCHK(hipMemcpyAsync(d->codes.p, codes, (size_t) G, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->chr_off.p, seq_off, sizeof(int64_t) * ((size_t) n_seq + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d->tcount.p, 0, sizeof(uint32_t) * (size_t) tabsize, st));
+    HIPCHK(hipMemsetAsync(d->cnt.p, 0, sizeof(uint32_t) * (size_t) tabsize, st));
+    ClassTable ct;
+    memcpy(ct.c, A.R.cls, 32);
+    hipLaunchKernelGGL(blkidx_tile_last_a, dim3((unsigned) n_tiles), dim3(TPB), 0, st, d->codes.as<uint8_t>(), G, ct, A.R.nalpha, d->tile_last.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> tl((size_t) n_tiles);
+    HIPCHK(hipMemcpyAsync(tl.data(), d->tile_last.p, sizeof(int64_t) * n_tiles, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t run = -1;                                   // exclusive prefix maximum: what a tile inherits
+    for (int64_t t = 0; t < n_tiles; ++t) { const int64_t mine = tl[t]; tl[t] = run; if (mine > run) run = mine; }
+    HIPCHK(hipMemcpyAsync(d->tile_last.p, tl.data(), sizeof(int64_t) * n_tiles, hipMemcpyHostToDevice, st));
+    A.codes = d->codes.as<uint8_t>(); A.seq_off = d->chr_off.as<int64_t>(); A.n_seq = n_seq;
+    A.tile_carry = d->tile_last.as<int64_t>(); A.tcount = d->tcount.as<uint32_t>(); A.n_keys = d->n_keys.as<unsigned long long>();
+    // keys: one per Nshift residues of a run and one more per sequence; a run that needs more says so and is repeated with room for them
+    unsigned long long cap = (unsigned long long) ((double) G / A.R.nshift * 1.25) + (unsigned long long) n_seq + (1ull << 20);
+    unsigned long long n_keys = 0;
+    for (int round = 0; round < 2; ++round) {
+        HIPCHK(d->keys.get(sizeof(unsigned long long) * cap));
+        HIPCHK(hipMemsetAsync(d->n_keys.p, 0, sizeof(unsigned long long), st));
+        if (round) HIPCHK(hipMemsetAsync(d->tcount.p, 0, sizeof(uint32_t) * (size_t) tabsize, st));
+        A.keys = d->keys.as<unsigned long long>(); A.cap = cap;
+        hipLaunchKernelGGL(blkidx_words_a, dim3((unsigned) n_tiles), dim3(TPB), 0, st, A);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&n_keys, d->n_keys.p, sizeof n_keys, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (n_keys <= cap) break;
+        if (round) { ctx->err = "spdp_blk_index_build_a: key count changed between two passes"; return -1; }
         cap = n_keys;
     }
     if (blkidx_finish_keys(ctx, d, n_keys, key_bits, tabsize, tcount, cnt)) return -1;

@@ -240,6 +240,48 @@ uint32_t bp_compress(const char* sp, int* ones)
     return c;
 }
 double wall(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
+
+// blkscrtab(segn, blksz), src/blksrc.cc:944-997: the scores of the words from their counts (tcount) and from how many blocks hold
+// them (cnt; zeroed here for a word that loses its list), the kept words' lists laid out in h->blkp / nblk, h->blkb sized.  Returns
+// what is wrong, or nullptr
+struct BlkScores { double avr = 0.; uint64_t kept = 0, word_no = 0, max_blk = 0; };
+const char* blk_score_words(HostIndex* h, const std::vector<uint32_t>& tcount, std::vector<uint32_t>& cnt, uint32_t tabsize, uint32_t segn,
+                            uint32_t blksz, int afact, int nbit, BlkScores& out)
+{
+    try { h->nblk.assign(tabsize, 0); h->blkp.assign(tabsize, 0); h->wscr.assign(tabsize, 0); } catch (const std::bad_alloc&) { return "out of memory for the index tables"; }
+    const int nt = std::max(1, std::min(spdp_host_cpus(), (int) (tabsize >> 14)));
+    std::vector<uint64_t> part_m(nt, 0);
+    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) { uint64_t m = 0; for (uint32_t w = a; w < b; ++w) if (tcount[w]) ++m; part_m[t] = m; });
+    uint64_t m_seen = 0;
+    for (uint64_t x : part_m) m_seen += x;
+    if (!m_seen) return "no word in the genome";
+    const double basescr = log((double) segn);
+    short min_scr = (short) -(100 * log((double) afact * blksz / (uint32_t) m_seen));
+    if (min_scr < 0) min_scr = 0;
+    std::vector<double> part_avr(nt, 0.);
+    std::vector<uint64_t> part_kept(nt, 0), part_words(nt, 0), part_max(nt, 0), part_over(nt, 0);
+    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) {
+        double avr = 0.; uint64_t kept = 0, words = 0, mx = 0, over = 0;
+        for (uint32_t w = a; w < b; ++w) {
+            if (!cnt[w]) { h->wscr[w] = -1; continue; }
+            if (cnt[w] > 65535) ++over;
+            // a word that never counted in tcount (all its occurrences in a block's last margin residues): the reference takes
+            // (short) of +inf there -- cvttsd2si's 0x80000000, whose low half is 0
+            const short sc = tcount[w] ? (short) (100 * (basescr - log((double) tcount[w] / nbit))) : (short) 0;
+            if (sc > min_scr) { ++kept; words += cnt[w]; h->wscr[w] = sc; avr += sc; mx = std::max<uint64_t>(mx, cnt[w]); }
+            else { h->wscr[w] = min_scr; cnt[w] = 0; }
+        }
+        part_avr[t] = avr; part_kept[t] = kept; part_words[t] = words; part_max[t] = mx; part_over[t] = over;
+    });
+    uint64_t over = 0;
+    for (int t = 0; t < nt; ++t) { out.avr += part_avr[t]; out.kept += part_kept[t]; out.word_no += part_words[t]; out.max_blk = std::max(out.max_blk, part_max[t]); over += part_over[t]; }
+    if (over) return "a word lies in more than 65 535 blocks: the reference's 16-bit counters wrap there (use a longer k)";
+    if (out.word_no > (uint64_t) INT32_MAX) return "more postings than a 32-bit list offset (blkp) can address";
+    uint64_t at = 0;
+    for (uint32_t w = 0; w < tabsize; ++w) if (cnt[w]) { h->blkp[w] = (int32_t) (at + 1); h->nblk[w] = (uint16_t) cnt[w]; at += cnt[w]; }
+    try { h->blkb.assign((size_t) out.word_no, 0); } catch (const std::bad_alloc&) { return "out of memory for the posting lists"; }
+    return nullptr;
+}
 }   // namespace
 
 // setupbitpat(DNA, gnmsz) with no -X option but -XC (src/blksrc.cc:680-737; the defaults wcp_cf of :45)
@@ -341,38 +383,9 @@ static SpdpBlkIndexHost* blk_index_build(SpdpContext* ctx, const SpdpGenome* gen
     // ---- blkscrtab(segn, blksz), src/blksrc.cc:944-997
     const auto t_host = std::chrono::steady_clock::now();
     const uint32_t segn = (uint32_t) blocks, blksz = (uint32_t) G / segn;
-    try { h->nblk.assign(tabsize, 0); h->blkp.assign(tabsize, 0); h->wscr.assign(tabsize, 0); } catch (const std::bad_alloc&) { return fail("out of memory for the index tables"); }
-    const int nt = std::max(1, std::min(spdp_host_cpus(), (int) (tabsize >> 14)));
-    std::vector<uint64_t> part_m(nt, 0);
-    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) { uint64_t m = 0; for (uint32_t w = a; w < b; ++w) if (tcount[w]) ++m; part_m[t] = m; });
-    uint64_t m_seen = 0;
-    for (uint64_t x : part_m) m_seen += x;
-    if (!m_seen) { return fail("no word in the genome"); }
-    const double basescr = log((double) segn);
-    short min_scr = (short) -(100 * log((double) p->afact * blksz / (uint32_t) m_seen));
-    if (min_scr < 0) min_scr = 0;
-    std::vector<double> part_avr(nt, 0.);
-    std::vector<uint64_t> part_kept(nt, 0), part_words(nt, 0), part_max(nt, 0), part_over(nt, 0);
-    on_ranges(nt, tabsize, [&](int t, uint32_t a, uint32_t b) {
-        double avr = 0.; uint64_t kept = 0, words = 0, mx = 0, over = 0;
-        for (uint32_t w = a; w < b; ++w) {
-            if (!cnt[w]) { h->wscr[w] = -1; continue; }
-            if (cnt[w] > 65535) ++over;
-            // a word that never counted in tcount (all its occurrences in a block's last margin residues): the reference takes
-            // (short) of +inf there -- cvttsd2si's 0x80000000, whose low half is 0
-            const short sc = tcount[w] ? (short) (100 * (basescr - log((double) tcount[w] / nbit))) : (short) 0;
-            if (sc > min_scr) { ++kept; words += cnt[w]; h->wscr[w] = sc; avr += sc; mx = std::max<uint64_t>(mx, cnt[w]); }
-            else { h->wscr[w] = min_scr; cnt[w] = 0; }
-        }
-        part_avr[t] = avr; part_kept[t] = kept; part_words[t] = words; part_max[t] = mx; part_over[t] = over;
-    });
-    double avr = 0.; uint64_t kept = 0, word_no = 0, max_blk = 0, over = 0;
-    for (int t = 0; t < nt; ++t) { avr += part_avr[t]; kept += part_kept[t]; word_no += part_words[t]; max_blk = std::max(max_blk, part_max[t]); over += part_over[t]; }
-    if (over) { return fail("a word lies in more than 65 535 blocks: the reference's 16-bit counters wrap there (use a longer k)"); }
-    if (word_no > (uint64_t) INT32_MAX) { return fail("more postings than a 32-bit list offset (blkp) can address"); }
-    uint64_t at = 0;
-    for (uint32_t w = 0; w < tabsize; ++w) if (cnt[w]) { h->blkp[w] = (int32_t) (at + 1); h->nblk[w] = (uint16_t) cnt[w]; at += cnt[w]; }
-    try { h->blkb.assign((size_t) word_no, 0); } catch (const std::bad_alloc&) { return fail("out of memory for the posting lists"); }
+    BlkScores sc;
+    if (const char* why = blk_score_words(h, tcount, cnt, tabsize, segn, blksz, p->afact, nbit, sc)) return fail(why);
+    const double avr = sc.avr; const uint64_t kept = sc.kept, word_no = sc.word_no, max_blk = sc.max_blk;
     const double t_host1 = wall(t_host);
     const auto t_dev2 = std::chrono::steady_clock::now();
     if (spdp_blkidx_lists(ctx, dev, h->blkp.data(), (int64_t) word_no, h->blkb.data())) { return nullptr; }
@@ -600,6 +613,138 @@ extern "C" SpdpBlkIndexHost* spdp_blk_index_build_p(SpdpContext* ctx, const Spdp
 {
     try { return blk_index_build_p(ctx, genome, p, opts, seconds); }
     catch (const std::bad_alloc&) { if (ctx) ctx->err = "spdp_blk_index_build_p: out of host memory"; return nullptr; }
+}
+
+// ---- the amino-acid index of a protein database, `spaln -W -KA` (<db>.bka) -------------------------------------------------------
+// what setupbitpat picks for a protein database of that many counted residues (src/blksrc.cc:678-737 with wcp_af of :43; makeblock,
+// :795-806: the size is PreScan::lenStat's total, and blklen becomes the longest sequence -- the build sets it)
+extern "C" int spdp_blk_build_params_default_a(int64_t total_residues, SpdpBlkBuildParamsA* p)
+{
+    if (!p || total_residues < 1) return -1;
+    memset(p, 0, sizeof *p);
+    p->b.afact = 10; p->b.nbitpat = 1;
+    const double gs = (double) total_residues;
+    int k = (int) (log(gs) * 0.30);
+    if (k < 3) k = 3;
+    if (k > 6) k = 6;
+    p->b.ktuple = k; p->b.nshift = k; p->b.bitpat = (1u << k) - 1;
+    p->b.maxgene = (int) (38 * sqrt(gs) / 1024 + 1) * 1024;
+    if (p->b.maxgene < 16384) p->b.maxgene = 16384;
+    p->nalpha = 20;
+    // iConvTab of the twenty-letter alphabet over the amino-acid codes (ReducWord::ReducWord, src/bitpat.cc:61-90; the codes of
+    // src/seq.cc:47-49, 58): A .. V = 3 .. 22 in the code's own order; 24 (Sec and Glx share it) one past the ambiguous class; 25, the
+    // table's last entry, the ambiguous class.  The loop assigns nothing below the first amino acid (0, 1 and X = 2) and nothing to
+    // Asx (23), which is in no class: the program's files hold its heap there.  Here X is ambiguous, the others are skipped
+    p->convts = 26;
+    p->convtab[0] = p->convtab[1] = 21; p->convtab[2] = 20;
+    for (int c = 3; c <= 22; ++c) p->convtab[c] = (uint8_t) (c - 3);
+    p->convtab[23] = 21; p->convtab[24] = 21; p->convtab[25] = 20;
+    return 0;
+}
+
+static SpdpBlkIndexHost* blk_index_build_a(SpdpContext* ctx, const SpdpGenome* db, const SpdpBlkBuildParamsA* p,
+                                           const SpdpBlkSearchOpts* opts, double* seconds)
+{
+    if (!ctx) return nullptr;
+    auto fail = [&](const char* m) -> SpdpBlkIndexHost* { ctx->err = std::string("spdp_blk_index_build_a: ") + m; return nullptr; };
+    if (!db || !db->codes || !db->chr_off || db->n_chr < 1 || !p) return fail("null argument");
+    const int K = p->b.ktuple, na = p->nalpha, nshift = p->b.nshift;
+    if (K < 3 || K > BLKA_MAX_K || na < 6 || na > 20) return fail("parameters out of range (words of 3 .. 7 amino acids, 6 .. 20 classes)");
+    if (p->b.nbitpat != 1) return fail("one bit pattern only (the spaced pairs of -XC are not built)");
+    if (nshift < 1 || nshift > SPDP_BLK_MAX_SHIFT) return fail("nshift out of range");
+    if (p->b.afact < 1 || p->b.maxgene < 1 || p->convts < 1 || p->convts > 32) return fail("afact, maxgene or convts out of range");
+    uint64_t tab64 = 1;
+    for (int i = 0; i < K; ++i) tab64 *= (uint64_t) na;
+    if (tab64 > (uint64_t) INT32_MAX) return fail("nalpha ^ k beyond a 32-bit word table");
+    const uint32_t tabsize = (uint32_t) tab64;
+    BlkBuildArgsA A;
+    memset(&A, 0, sizeof A);
+    {   // Bitpat::Bitpat (src/bitpat.cc:109-143): the least significant bit is the leftmost position
+        int width = 0, weight = 0;
+        for (uint32_t x = p->b.bitpat; x; x >>= 1) { weight += x & 1; ++width; }
+        if (weight != K || width > 32 || !(p->b.bitpat & 1)) return fail("the bit pattern's weight is not k (or it is wider than 32)");
+        A.R.width = width; A.R.weight = weight; A.R.spaced = width > weight;
+        int wt = 0;
+        for (int w = 0; w < width; ++w) if (p->b.bitpat & (1u << w)) A.R.exam[wt++] = w;
+    }
+    A.R.nalpha = na; A.R.nshift = nshift;
+    for (int c = 0; c < 32; ++c) A.R.cls[c] = c < p->convts ? std::min<uint8_t>(p->convtab[c], (uint8_t) (na + 1)) : (uint8_t) (na + 1);
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int n_seq = db->n_chr;
+    if (db->chr_off[0] != 0) return fail("chr_off must start at 0");
+    for (int s = 0; s < n_seq; ++s) if (db->chr_off[s + 1] < db->chr_off[s]) return fail("chr_off decreases");
+    const int64_t G_in = db->chr_off[n_seq];
+    // the residues the program's scan skips (class > nalpha) leave the copy that is uploaded: they break no word and count nowhere
+    std::vector<uint8_t> codes;
+    std::vector<int64_t> off((size_t) n_seq + 1, 0);
+    codes.reserve((size_t) G_in);
+    int64_t longest = 0;
+    for (int s = 0; s < n_seq; ++s) {
+        for (int64_t j = db->chr_off[s]; j < db->chr_off[s + 1]; ++j) {
+            const uint8_t c = db->codes[j];
+            if (c >= p->convts) return fail("a residue code at or beyond convts");
+            if (A.R.cls[c] <= na) codes.push_back(c);
+        }
+        off[s + 1] = (int64_t) codes.size();
+        // the program writes a ChrID entry without a block for such a sequence; the search takes block b to be sequence b
+        if (off[s + 1] == off[s]) return fail("a sequence with no counted residue");
+        longest = std::max(longest, off[s + 1] - off[s]);
+    }
+    const int64_t G = (int64_t) codes.size();
+    if (G > (int64_t) UINT32_MAX) return fail("at most 2^32 - 1 residues (the reference's positions are 32-bit)");
+    A.G = G; A.tabsize = tabsize;
+    std::unique_ptr<HostIndex> hold(new HostIndex);         // (freed on every way out but the last)
+    HostIndex* h = hold.get();
+    h->chrid.resize((size_t) n_seq + 1);
+    for (int s = 0; s <= n_seq; ++s) h->chrid[s] = {(uint32_t) off[s], (uint32_t) (s + 1)};
+    int word_bits = 1;
+    while ((1ull << word_bits) < tab64) ++word_bits;
+    const double t_drop = wall(t_begin);
+    std::vector<uint32_t> tcount, cnt;
+    BlkBuildDev* dev = nullptr;
+    if (spdp_blkidx_words_a(ctx, codes.data(), off.data(), n_seq, A, 32 + word_bits, tcount, cnt, &dev)) { return nullptr; }
+    struct DevGuard { BlkBuildDev* d; ~DevGuard() { spdp_blkidx_free(d); } } dev_guard{dev};
+    const double t_dev1 = wall(t_begin) - t_drop;
+    // ---- blkscrtab(segn, spos / segn): every residue lies inside blklen, so every flawless word has counted in tcount
+    const auto t_host = std::chrono::steady_clock::now();
+    const uint32_t segn = (uint32_t) n_seq, blksz = (uint32_t) G / segn;
+    BlkScores sc;
+    if (const char* why = blk_score_words(h, tcount, cnt, tabsize, segn, blksz, p->b.afact, 1, sc)) return fail(why);
+    const double t_host1 = wall(t_host);
+    const auto t_dev2 = std::chrono::steady_clock::now();
+    if (spdp_blkidx_lists(ctx, dev, h->blkp.data(), (int64_t) sc.word_no, h->blkb.data())) { return nullptr; }
+    const double t_dev2s = wall(t_dev2);
+    // ---- the header (makeblock, MakeBlk::idxblk, writeBlkInfo, findChrBbound)
+    memset(&h->wcp, 0, sizeof h->wcp); memset(&h->wc, 0, sizeof h->wc);
+    h->wcp.Nalpha = (uint32_t) na; h->wcp.Ktuple = (uint32_t) K; h->wcp.Bitpat2 = p->b.bitpat2; h->wcp.TabSize = tabsize; h->wcp.BitPat = p->b.bitpat;
+    h->wcp.Nshift = (uint32_t) nshift; h->wcp.blklen = (uint32_t) longest; h->wcp.MaxGene = (uint32_t) p->b.maxgene;
+    h->wcp.Nbitpat = 1; h->wcp.afact = (uint16_t) p->b.afact;
+    h->convtab.assign(p->convtab, p->convtab + p->convts);
+    h->wc.ConvTS = (uint32_t) p->convts; h->wc.WordNo = sc.word_no; h->wc.ChrNo = (uint64_t) n_seq; h->wc.glen = (uint64_t) G;
+    h->wc.AvrScr = sc.kept ? (uint16_t) (sc.avr / (double) sc.kept) : 0;
+    // ContBlk::MaxBlk: blkscrtab raises it to the longest kept list, from whatever the heap held where MakeBlk was allocated (ContBlk's
+    // constructor leaves it unset) -- the program's files carry a larger number than any list.  Here: the longest kept list
+    h->wc.MaxBlk = (uint16_t) sc.max_blk;
+    h->wc.BytBlk = segn <= 65535 ? 2 : 4; h->wc.WordSz = h->wc.BytBlk == 2 ? sc.word_no : 2 * sc.word_no; h->wc.VerNo = 26;
+    const double B = (double) segn;
+    h->b2c[0] = h->b2c[1] = h->b2c[2] = 0.;
+    for (int k = 0; k <= n_seq; ++k) {
+        const double d = k * B - n_seq * (double) (h->chrid[k].segn - 1);
+        h->b2c[0] = std::min(h->b2c[0], d); h->b2c[1] = std::max(h->b2c[1], d);
+    }
+    h->b2c[0] /= B; h->b2c[1] /= B;
+    SpdpBlkSearchOpts o;
+    if (opts) o = *opts; else { spdp_blk_search_opts_default(&o); o.genomic_db = 0; }
+    std::string why;
+    if (!derive_search_params(h, o, why)) { ctx->err = "spdp_blk_index_build_a: " + why; return nullptr; }
+    if (seconds) { seconds[0] = t_dev1 + t_dev2s; seconds[1] = t_drop + t_host1; seconds[2] = wall(t_begin); }
+    return (SpdpBlkIndexHost*) hold.release();
+}
+extern "C" SpdpBlkIndexHost* spdp_blk_index_build_a(SpdpContext* ctx, const SpdpGenome* db, const SpdpBlkBuildParamsA* p,
+                                                    const SpdpBlkSearchOpts* opts, double* seconds)
+{
+    try { return blk_index_build_a(ctx, db, p, opts, seconds); }
+    catch (const std::bad_alloc&) { if (ctx) ctx->err = "spdp_blk_index_build_a: out of host memory"; return nullptr; }
 }
 
 // WriteBlkInfo / writeBlkInfo (src/blksrc.cc:598-622): the struct images of the reference's 64-bit build

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Protein queries against a protein database inside the library, against the reference's own program.
 
-    python tools/aa_search.py [--queries 300] [--sequences 580] [--threads 16] [--max-out N] [--all-out]
+    python tools/aa_search.py [--queries 300] [--sequences 580] [--threads 16] [--max-out N] [--all-out] [--library-index]
                                                                       (an MI355X box; oracle/_ref for the comparison)
 
 A synthetic protein database with paralog families and queries of eight classes (mutated at 15 / 35 / 50 %, fragments, every tenth
@@ -12,6 +12,11 @@ residue X, unrelated, tiny) is formatted by the compiled reference's own `spaln 
   * library:    prot.bka read by spdp_blk_index_read, the database's residue codes, and then ONE spdp_map_align_b call = the vote
                 of SrchBlk::finds on the device -> every candidate a pair -> spdp_align_b_seeded -> spdp_skl_rng_b -> the
                 threshold and the order of the printed hits.
+
+With --library-index the library does not read prot.bka: it builds the index itself from the database's residue codes
+(spdp_blk_index_build_a; its three `seconds` are printed beside the wall time of `spaln -W -KA`, whose protein path is serial whatever
+-t says), the hit lists are still held to the program's run on the program's file, and the two .bka files are compared outside the
+bytes that hold the program's heap (blocks.bka_without_heap_bytes).
 
 Compared per query: the ordered hit list (name, printed score, the corners as -O4 prints them, the aligned ranges).  One JSON line: reference
 aligned, library aligned, identical, seconds of both (the library's call warm: the median of --repeat calls after a first one),
@@ -119,6 +124,7 @@ def main() -> int:
     ap.add_argument("--all-out", action="store_true")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--no-reference", action="store_true", help="library only (a profiler run): nothing is compared")
+    ap.add_argument("--library-index", action="store_true", help="the library builds its own index of the database instead of reading prot.bka")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     db, queries = make_data(rng, args.sequences, args.queries)
@@ -157,14 +163,27 @@ def main() -> int:
             want_d = parse_o4(r.stdout) if r.returncode == 0 else None
             default_differs = None if want_d is None else sum(1 for name, _, _, _ in queries if want_d.get(name, []) != want.get(name, []))
         eng = engine.Engine(0)
+        seqs = [encode(s) for s in db]
+        db_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        db_off[1:] = np.cumsum([len(s) for s in seqs])
+        db_codes = np.concatenate(seqs)
+        build = None
         t0 = time.perf_counter()
-        arrays, fprm = blocks.read_protein_db_index(eng.lib, os.path.join(td, "prot.bka"), max_out=args.max_out)
+        if args.library_index:
+            prm = blocks.build_params_default_a(eng.lib, int(db_off[-1]))
+            blocks.build_index_a(eng, db_codes[:db_off[min(64, len(seqs))]], db_off[:min(64, len(seqs)) + 1], prm)      # first call: module load
+            t0 = time.perf_counter()
+            mine_bka = os.path.join(td, "library.bka")
+            arrays, fprm, build_sec = blocks.build_index_a(eng, db_codes, db_off, prm, write_to=mine_bka, max_out=args.max_out)
+            with open(mine_bka, "rb") as f, open(os.path.join(td, "prot.bka"), "rb") as g:
+                a, b = f.read(), g.read()
+            build = dict(seconds_device_host_call=[round(x, 4) for x in build_sec], ktuple=int(prm.b.ktuple), tabsize=int(arrays["tabsize"]),
+                         postings=int(arrays["blk_blkb"].size), files_equal_outside_heap_bytes=blocks.bka_without_heap_bytes(a) == blocks.bka_without_heap_bytes(b),
+                         library_maxblk=int(arrays["maxblk"]), program_maxblk=int.from_bytes(b[78:80], "little"))
+        else:
+            arrays, fprm = blocks.read_protein_db_index(eng.lib, os.path.join(td, "prot.bka"), max_out=args.max_out)
         dix = blocks.BlockIndex(eng, arrays)
         load_s = time.perf_counter() - t0
-    seqs = [encode(s) for s in db]
-    db_off = np.zeros(len(seqs) + 1, dtype=np.int64)
-    db_off[1:] = np.cumsum([len(s) for s in seqs])
-    db_codes = np.concatenate(seqs)
     sc, up, model = defaults.scoring_b(), abi.UnsplicedParams(1.0, 0), defaults.wilip_model_b()
     sp = defaults.seed_params_b(3, 15)
     sp.wilip = C.addressof(model)
@@ -200,12 +219,12 @@ def main() -> int:
         "identical": None if bad is None else len(queries) - len(bad), "of": len(queries), "first_differing": None if bad is None else bad[:5],
         "reference_threads": args.threads, "reference_s": None if ref_s is None else round(ref_s, 3),
         "reference_default_engine_s": None if ref_default_s is None else round(ref_default_s, 3), "queries_whose_records_differ_without_A0": default_differs, "library_s": round(lib_s, 4),
-        "library_s_all": [round(t, 4) for t in times], "index_load_s": round(load_s, 3), "format_s": round(format_s, 3),
+        "library_s_all": [round(t, 4) for t in times], "index_load_s": round(load_s, 3), "format_s": round(format_s, 3), "library_index": build,
         "library_over_reference": None if ref_s is None else round(ref_s / lib_s, 2),
         "split": st, "vote_kernel_ms": round(ms, 3), "vote_queries_per_s": round(len(queries) / (ms * 1e-3), 1) if ms > 0 else None,
         "candidates_per_query": round(st["candidates"] / max(st["searched"], 1), 3), "per_class": per_class, "device": eng.device_name()}))
     eng.close()
-    return 0 if not bad else 1
+    return 0 if not bad and (build is None or build["files_equal_outside_heap_bytes"]) else 1
 
 
 if __name__ == "__main__":
