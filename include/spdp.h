@@ -1220,7 +1220,8 @@ int spdp_polya_scan_resident(SpdpContext* ctx, uint8_t* d_codes, const int64_t* 
  * on the reverse leg of ori = 3 too, where the program copies tlen unchanged (Seq::copyseq, src/seq.cc:1123) and the bound thus
  * cuts the transcript's end; exon positions are those of the query AS GIVEN, as -O4 prints them (descending for a T-head query
  * aligned as normalised, ascending again when its reverse leg won).  q_rev keeps its meaning: the reverse leg of ori = 3 won.
- * polya_thr <= 0: the results of spdp_map_align_s / _multi with ori = q_mns.  The group twins take no preparation yet. */
+ * polya_thr <= 0: the results of spdp_map_align_s / _multi with ori = q_mns.  The group twins: spdp_group_map_align_s_prep /
+ * _multi_prep ("device groups, third part"). */
 int spdp_map_align_s_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                           const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
                           const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
@@ -1268,7 +1269,8 @@ int spdp_map_align_s_multi_prep(SpdpContext* ctx, const SpdpBlkIndex* ix, const 
  * narrowed in the coordinates of the query as given.  The program differs there as it does for -M N: after a locus aligned with
  * the query reverse-complemented it leaves the query in that state (src/fwd2s1.cc:2766-2777) and goes on -- further loci, cov and
  * the rests -- with ranges that belong to the other orientation; that state is not reproduced.  Not served either: a rest of a
- * rest (the program has no such recursion), Seq::sigII queries, the group twins. */
+ * rest (the program has no such recursion), Seq::sigII queries.  The group twins: spdp_group_map_align_s_dispersed /
+ * _h_dispersed ("device groups, third part"). */
 int spdp_dispersed_rests(const int32_t org[2], const int32_t cov[2], int32_t min_seg_len, int32_t rests[4]);
 int spdp_map_align_s_dispersed(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
@@ -1461,6 +1463,70 @@ int spdp_map_align_b(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkInde
 /* counters of the last spdp_map_align_b call on this context: queries [0] searched, [1] refused as too short; [2] candidates
  * aligned, [3] pairs dropped by the threshold; microseconds in [4] the vote kernel, [5] the alignment calls, [6] host work */
 int spdp_blk_finds_stats(const SpdpContext* ctx, int64_t* out, int n);
+
+/* ---- device groups, third part: the unspliced aligner, the protein-database search, the locus search, the _prep and _dispersed
+ * map + align entries ---------------------------------------------------------------------------------------------------------
+ * The rule of the other group calls: the queries (problems) are sharded over the members by the longest-processing-time rule,
+ * every member runs the single-context entry on its shard from its own host thread on its own device, nothing is exchanged, the
+ * results land in the caller's order, spdp_group_last_shards tells who served what.  Arguments are those of the single-context
+ * entry with the group in place of the context and, where an index is taken, ix[r] = the index created on spdp_group_context(g, r).
+ * The return value is the worst of the members' (1 = "some problem not computed"); a member's -1 makes the call return -1,
+ * spdp_group_last_error names the device and carries that member's message, and every malloc'ed output is freed and NULL.  A
+ * group of one member returns what the single-context entry returns; n <= 0 is answered by the first member.
+ * Costs: spdp_cells_b on the window spdp_stripe gives (the unspliced aligner), 1 + query length (all others).
+ * max_trace_bytes holds per member (each has its own device): a problem that alone exceeds it comes back "not computed".
+ * The HSP source of spdp_group_align_b_seeded is asked with the CALLER's pair numbers, from the members' worker threads;
+ * spdp_align_b_seeded_refusal is consulted once, for the call as a whole, before any member starts.
+ * Pooled outputs (*hits / *corners, *loci / *hsps, *genes / *exons / *part) are the members' lists concatenated in the caller's query
+ * order with corner_off / hsp_off / exon_off counted again and SpdpLocus.query in the caller's numbers: what one context writes for
+ * the same queries (spaln_amd/csrc/spdp_group_gather.h).  A query without hits, loci or genes keeps its empty slot.
+ * seconds: every phase is the maximum over the members (the call lasts as long as its slowest member); the entry a single-context
+ * call documents as "the call" (spdp_map_align_b: [3]) is the wall time of the group call.  kernel_ms: the largest of the members'.
+ * The per-context counters -- spdp_blk_finds_stats, spdp_seeded_stats_b, spdp_blk_find_stats -- stay per context: read them
+ * through spdp_group_context(g, r), member by member.
+ * Every member's host phases size themselves by the whole host: eight members on one host oversubscribe it. */
+int spdp_group_homscore_b(SpdpGroup* g, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
+                          const SpdpProblem* probs, int n_probs, int32_t* scores);
+int spdp_group_align_b(SpdpGroup* g, const SpdpScoring* sc, const SpdpUnsplicedParams* up,
+                       const SpdpProblem* probs, int n_probs, SpdpAlignment* out);
+int spdp_group_align_b_seeded(SpdpGroup* g, const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp,
+                              const SpdpProblem* probs, int n_probs, const SpdpJuxt* const* hsps, const int32_t* n_hsps,
+                              const int32_t* lowest_level, const SpdpHspSource* src, SpdpAlignment* out);
+int spdp_group_blk_finds(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpBlkFindsParams* prm,
+                         const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                         int32_t* out, int32_t out_cap, float* kernel_ms);
+int spdp_group_map_align_b(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* db,
+                           const SpdpScoring* sc, const SpdpUnsplicedParams* up, const SpdpSeedParams* sp, const SpdpBlkFindsParams* fprm,
+                           const uint8_t* codes, const int64_t* offs, int32_t n, int32_t all_out,
+                           int64_t* hit_off, SpdpMapHitB** hits, SpdpSkl** corners, double* seconds);
+/* nucleotide queries and, with model->dvsp = 1, protein queries on translated indexes; status[] in the caller's order */
+int spdp_group_blk_find(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                        const struct SpdpWilipModel* model, const SpdpScoring* sc, const SpdpBlkFindParams* prm,
+                        const uint8_t* codes, const int64_t* offs, const int32_t* left, const int32_t* right, int32_t n,
+                        SpdpLocus** loci, int32_t* n_loci, SpdpJuxt** hsps, int32_t* status);
+/* part is pooled like genes; covered and tails are per query */
+int spdp_group_map_align_s_prep(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep,
+                                SpdpMapGene* genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails);
+int spdp_group_map_align_s_multi_prep(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                      const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                      const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                      const uint8_t* codes, const int64_t* offs, int32_t n, const SpdpQueryPrep* prep, int32_t all_out,
+                                      int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, double* seconds, SpdpQueryTail* tails);
+int spdp_group_map_align_s_dispersed(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                     const SpdpScoring* sc, const SpdpSeedParams* sp, const SpdpSignalModel* sigmodel,
+                                     const SpdpBlkFindParams* fprm, const SpdpRescoreParams* rp,
+                                     const uint8_t* codes, const int64_t* offs, int32_t n, int32_t ori, const SpdpQueryPrep* prep,
+                                     int32_t min_seg_len, int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                                     int32_t* covered, double* seconds, SpdpQueryTail* tails);
+int spdp_group_map_align_h_dispersed(SpdpGroup* g, const SpdpBlkIndex* const* ix, const SpdpBlkIndexDesc* hix, const SpdpGenome* genome,
+                                     const struct SpdpScoringH* sc, const SpdpSeedParams* sp, const struct SpdpSignalModelH* sigmodel,
+                                     const SpdpBlkFindParams* fprm, const struct SpdpRescoreParamsH* rp,
+                                     const uint8_t* codes, const int64_t* offs, int32_t n, int32_t min_seg_len,
+                                     int64_t* gene_off, SpdpMapGene** genes, SpdpMapExon** exons, int32_t** part,
+                                     int32_t* covered, double* seconds);
 
 #ifdef __cplusplus
 }

@@ -230,13 +230,14 @@ def finds(index: "BlockIndex", prm, queries, ranges=None, out_cap: int = 64, res
     right = np.array([len(queries[i]) if ranges is None else ranges[i][1] for i in range(n)], dtype=np.int32)
     out = np.zeros((n, out_cap), dtype=np.int32)
     ms = C.c_float()
-    fn = lib.spdp_blk_finds_resident if resident else lib.spdp_blk_finds
+    name = "spdp_blk_finds_resident" if resident else _entry(index, "spdp_blk_finds")
+    fn = getattr(lib, name)
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     if not resident:
         rc = fn(eng.ctx, index.h, C.byref(index.desc), C.byref(prm), codes.ctypes.data, offs.ctypes.data, left.ctypes.data, right.ctypes.data, n,
                 out.ctypes.data, out_cap, C.byref(ms))
-        eng._check(rc, "spdp_blk_finds")
+        eng._check(rc, name)
         return out, ms.value
     hip = _hip_runtime()
     hosts = (codes, offs, left, right, out)
@@ -285,12 +286,14 @@ def map_align_b(index: "BlockIndex", db_codes, seq_off, sc, up, sp, fprm, querie
     hit_off = np.zeros(n + 1, dtype=np.int64)
     hits, corners = C.POINTER(abi.MapHitB)(), C.POINTER(C.c_int32)()
     sec = (C.c_double * 4)()
-    lib.spdp_map_align_b.restype = C.c_int
-    lib.spdp_map_align_b.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4
-    rc = lib.spdp_map_align_b(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(up), C.byref(sp), C.byref(fprm),
-                              codes.ctypes.data, offs.ctypes.data, n, int(bool(all_out)), hit_off.ctypes.data, C.byref(hits), C.byref(corners), sec)
+    name = _entry(index, "spdp_map_align_b")
+    fn = getattr(lib, name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4
+    rc = fn(eng.ctx, index.h, C.byref(index.desc), C.byref(g), C.byref(sc), C.byref(up), C.byref(sp), C.byref(fprm),
+            codes.ctypes.data, offs.ctypes.data, n, int(bool(all_out)), hit_off.ctypes.data, C.byref(hits), C.byref(corners), sec)
     if rc < 0:
-        eng._check(rc, "spdp_map_align_b")
+        eng._check(rc, name)
     out = []
     for i in range(n):
         lst = []
@@ -552,8 +555,10 @@ class _Call:
         self.g = Genome(self._gc.ctypes.data, self._go.ctypes.data, len(self._go) - 1)
         self.sec = (C.c_double * 4)()
         self._head = (C.c_void_p(index.eng.ctx), C.c_void_p(index.h), C.byref(index.desc), C.byref(self.g)) + models + (self.codes, self.offs)
+        self._index = index
 
     def run(self, fn: str, *rest) -> int:
+        fn = _entry(self._index, fn)
         args = [C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else a for a in self._head + rest]
         f = getattr(self.lib, fn)
         f.restype = C.c_int
@@ -605,7 +610,8 @@ def find(index: "BlockIndex", genome_codes, chr_off, model, sc, prm: BlkFindPara
     hsps = C.POINTER(C.c_int32)()
     nl = C.c_int32()
     status = np.zeros(n, dtype=np.int32)
-    call.eng._check(call.run("spdp_blk_find", left, right, n, C.byref(loci), C.byref(nl), C.byref(hsps), status), "spdp_blk_find")
+    name = _entry(index, "spdp_blk_find")
+    call.eng._check(call.run(name, left, right, n, C.byref(loci), C.byref(nl), C.byref(hsps), status), name)
     out = [[] for _ in range(n)]
     for k in range(nl.value):
         L = loci[k]
@@ -884,3 +890,94 @@ def map_align_h_dispersed(index: "BlockIndex", genome_codes, chr_off, sc, sp, si
     of the query in residues).  Returns (lists, covered, seconds, return code) as map_align_dispersed."""
     c = _map_call(index, genome_codes, chr_off, sc, sp, sigmodel, prm, rescore, queries)
     return _dispersed(c, "spdp_map_align_h_dispersed", int(min_seg_len))
+
+
+# ---- device groups (include/spdp.h "device groups, third part"): the entries above on an engine.Group --------------------------
+GROUP_TWINS = ("spdp_blk_finds", "spdp_map_align_b", "spdp_blk_find", "spdp_map_align_s_prep", "spdp_map_align_s_multi_prep",
+               "spdp_map_align_s_dispersed", "spdp_map_align_h_dispersed")
+
+
+class _GroupHandle:
+    """what a call needs of an engine when a group runs it: the handle the entry takes first, and the group's error text"""
+
+    def __init__(self, grp):
+        self.grp, self.lib, self.ctx = grp, grp.lib, grp.h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what}: {self.grp.last_error()}")
+
+
+class GroupIndex:
+    """One BlockIndex per member of an engine.Group, all made from the same arrays (a fixture, read_index_file /
+    read_protein_db_index of a file, or what build_index* returned), and the handle array the group entries take.  Where a
+    function of this module takes an index, a GroupIndex makes it run its group twin (group_finds, group_map_align_b, ...)."""
+
+    def __init__(self, grp, fx: dict):
+        self.grp, self.lib = grp, grp.lib
+        self.members = []
+        try:
+            for r in range(grp.size):
+                self.members.append(BlockIndex(grp.context(r), fx))
+        except Exception:
+            self.free()
+            raise
+        self._handles = (C.c_void_p * grp.size)(*[m.h for m in self.members])
+        self.h = C.addressof(self._handles)
+        self.desc = self.members[0].desc
+        self.eng = _GroupHandle(grp)
+
+    def free(self):
+        for m in self.members:
+            m.free()
+        self.members = []
+
+
+def _entry(index, name: str) -> str:
+    """the entry that serves this index: the single-context one, or its group twin for a GroupIndex"""
+    if not isinstance(index, GroupIndex) or name.startswith("spdp_group_"):
+        return name
+    if name not in GROUP_TWINS:
+        raise ValueError(f"{name} has no group form that goes through a GroupIndex")
+    return "spdp_group_" + name[len("spdp_"):]
+
+
+def _grouped(index) -> "GroupIndex":
+    if not isinstance(index, GroupIndex):
+        raise TypeError("a blocks.GroupIndex is needed (one index per member of the group)")
+    return index
+
+
+def group_finds(index: GroupIndex, prm, queries, ranges=None, out_cap: int = 64):
+    """spdp_group_blk_finds: finds() with the queries sharded over the group's members; kernel ms = the slowest member's"""
+    return finds(_grouped(index), prm, queries, ranges, out_cap)
+
+
+def group_map_align_b(index: GroupIndex, db_codes, seq_off, sc, up, sp, fprm, queries, all_out: bool = False):
+    """spdp_group_map_align_b: map_align_b() on a group; seconds [vote, alignment, host: each the slowest member's; the group call]"""
+    return map_align_b(_grouped(index), db_codes, seq_off, sc, up, sp, fprm, queries, all_out)
+
+
+def group_find(index: GroupIndex, genome_codes, chr_off, model, sc, prm: BlkFindParams, queries, ranges=None):
+    """spdp_group_blk_find: find() on a group (nucleotide queries, or protein queries on translated indexes)"""
+    return find(_grouped(index), genome_codes, chr_off, model, sc, prm, queries, ranges)
+
+
+def group_map_align_prep(index: GroupIndex, *args, **kw):
+    """spdp_group_map_align_s_prep: map_align_prep() on a group"""
+    return map_align_prep(_grouped(index), *args, **kw)
+
+
+def group_map_align_multi_prep(index: GroupIndex, *args, **kw):
+    """spdp_group_map_align_s_multi_prep: map_align_multi_prep() on a group"""
+    return map_align_multi_prep(_grouped(index), *args, **kw)
+
+
+def group_map_align_dispersed(index: GroupIndex, *args, **kw):
+    """spdp_group_map_align_s_dispersed: map_align_dispersed() on a group"""
+    return map_align_dispersed(_grouped(index), *args, **kw)
+
+
+def group_map_align_h_dispersed(index: GroupIndex, *args, **kw):
+    """spdp_group_map_align_h_dispersed: map_align_h_dispersed() on a group"""
+    return map_align_h_dispersed(_grouped(index), *args, **kw)

@@ -43,6 +43,9 @@ EXPORTS = [
     "spdp_blk_find_stats", "spdp_hsp_plan", "spdp_hsp_tasks", "spdp_hsp_tasks_host",
     "spdp_blk_finds", "spdp_blk_finds_resident", "spdp_blk_finds_params_default", "spdp_map_align_b", "spdp_blk_finds_stats",
     "spdp_blk_build_params_default_a", "spdp_blk_index_build_a",
+    "spdp_group_homscore_b", "spdp_group_align_b", "spdp_group_align_b_seeded", "spdp_group_blk_finds", "spdp_group_map_align_b",
+    "spdp_group_blk_find", "spdp_group_map_align_s_prep", "spdp_group_map_align_s_multi_prep", "spdp_group_map_align_s_dispersed",
+    "spdp_group_map_align_h_dispersed",
 ]
 
 
@@ -288,6 +291,77 @@ def _seeded_call(lib, handle, check, name, sc, sp, ps, hsps, lowest_levels, wili
     return res
 
 
+def _alignments_b(lib, arr, n):
+    """[(score, skl)] of an SpdpAlignment array of the unspliced aligner; releases the array's corner lists"""
+    res = []
+    for i in range(n):
+        k = arr[i].n_skl
+        skl = np.ctypeslib.as_array(C.cast(arr[i].skl, C.POINTER(C.c_int32)), shape=(k, 2)).copy() if k else np.zeros((0, 2), dtype=np.int32)
+        res.append((int(arr[i].score), skl))
+    lib.spdp_free_alignments(arr, n)
+    return res
+
+
+def _seeded_call_b(lib, handle, check, name, sc, up, sp, ps, model, hsps, lowest_levels, allow_partial, source):
+    """one spdp_align_b_seeded call on a context or a group handle: ([(score, skl)], seconds spent in the library)"""
+    import time
+    n = len(ps)
+    keep = []
+    jx = (C.c_void_p * n)()
+    nh = (C.c_int32 * n)()
+    lv = (C.c_int32 * n)(*[int(x) for x in (lowest_levels if lowest_levels is not None else [0] * n)])
+    for i, h in enumerate(hsps or []):
+        if h is None or len(h) < 2:
+            continue
+        a = np.ascontiguousarray(h, dtype=np.int32)
+        keep.append(a)
+        jx[i] = a.ctypes.data
+        nh[i] = a.shape[0] - 1
+    src = None
+    if source is not None:
+        def units(_user, query, level, span, flat, n_flat):
+            a = source(int(query), int(level), [int(span[k]) for k in range(8)])
+            if a is None:
+                return 1
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            keep.append(a)                               # (appends are atomic; the arrays live until the call returns)
+            flat[0] = a.ctypes.data_as(C.POINTER(C.c_int32))
+            n_flat[0] = a.size
+            return 0
+        src = abi.HspSource()
+        src.user = None
+        src.units = abi.HSP_UNITS_FN(units)
+        src.release = abi.HSP_RELEASE_FN(lambda _u, _q, _f: None)
+    arr = (abi.Alignment * n)()
+    probs = ps.array()
+    fn = getattr(lib, name)
+    fn.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
+    sp.wilip = C.addressof(model) if model is not None else None
+    t0 = time.perf_counter()
+    rc = fn(handle, C.byref(sc), C.byref(up), C.byref(sp), probs, n, jx, nh, lv, None if src is None else C.byref(src), arr)
+    seconds = time.perf_counter() - t0
+    sp.wilip = None
+    if not (allow_partial and rc == 1):
+        check(rc, name)
+    return _alignments_b(lib, arr, n), seconds
+
+
+class Member:
+    """The r-th context of a Group where an Engine is asked for (blocks.BlockIndex, the per-context counters): the group owns it"""
+
+    def __init__(self, lib, ctx):
+        self.lib, self.ctx = lib, ctx
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what}: {self.lib.spdp_last_error(self.ctx).decode()}")
+
+    def seeded_stats_b(self) -> dict:
+        """spdp_seeded_stats_b of this member: its share of the group's last align_b_seeded call"""
+        v = (C.c_int64 * len(Engine.SEEDED_STATS_B))()
+        self.lib.spdp_seeded_stats_b(self.ctx, v, len(Engine.SEEDED_STATS_B))
+        return dict(zip(Engine.SEEDED_STATS_B, (int(x) for x in v)))
+
 
 class Group:
     """Several GPUs behind one handle (spdp_group_*): the batched calls shard the query list over the members."""
@@ -298,11 +372,52 @@ class Group:
         self.h = self.lib.spdp_group_create(arr, len(devices))
         if not self.h:
             raise RuntimeError("spdp_group_create failed: no usable HIP device (there is no CPU path)")
+        self.size = len(devices)
+        self.lib.spdp_group_context.restype = C.c_void_p
+        self.lib.spdp_group_context.argtypes = [C.c_void_p, C.c_int]
 
     def close(self):
         if getattr(self, "h", None):
             self.lib.spdp_group_destroy(self.h)
             self.h = None
+
+    def context(self, r: int) -> Member:
+        """spdp_group_context: the r-th member's context, for the indexes made on it and the counters read from it"""
+        ctx = self.lib.spdp_group_context(self.h, int(r))
+        if not ctx:
+            raise IndexError(f"the group has no member {r}")
+        return Member(self.lib, ctx)
+
+    def last_error(self) -> str:
+        return self.lib.spdp_group_last_error(self.h).decode()
+
+    # ---- the unspliced aligner (include/spdp.h "device groups, third part"): results as the Engine's methods of the same name
+    def homscore_b(self, sc, up: abi.UnsplicedParams, ps) -> np.ndarray:
+        out = np.zeros(len(ps), dtype=np.int32)
+        self.lib.spdp_group_homscore_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        self._check(self.lib.spdp_group_homscore_b(self.h, C.byref(sc), C.byref(up), ps.array(), len(ps), out.ctypes.data_as(C.c_void_p)),
+                    "spdp_group_homscore_b")
+        return out
+
+    def align_b(self, sc, up: abi.UnsplicedParams, ps, allow_partial=False):
+        import time
+        n = len(ps)
+        arr = (abi.Alignment * n)()
+        probs = ps.array()
+        self.lib.spdp_group_align_b.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        t0 = time.perf_counter()
+        rc = self.lib.spdp_group_align_b(self.h, C.byref(sc), C.byref(up), probs, n, arr)
+        self.last_call_s = time.perf_counter() - t0
+        if not (allow_partial and rc == 1):
+            self._check(rc, "spdp_group_align_b")
+        return _alignments_b(self.lib, arr, n)
+
+    def align_b_seeded(self, sc, up: abi.UnsplicedParams, sp: abi.SeedParams, ps, model=None, hsps=None, lowest_levels=None,
+                       allow_partial=False, source=None):
+        """source is asked with the caller's pair numbers, from the members' worker threads"""
+        res, self.last_call_s = _seeded_call_b(self.lib, self.h, self._check, "spdp_group_align_b_seeded", sc, up, sp, ps, model, hsps, lowest_levels,
+                                               allow_partial, source)
+        return res
 
     def _check(self, rc, what):
         if rc != 0:
@@ -783,39 +898,14 @@ class Engine:
         return res, dict(zip(self.LSP_STATS_B, (int(x) for x in st)))
 
     def align_b_seeded(self, sc, up: abi.UnsplicedParams, sp: abi.SeedParams, ps, model=None, hsps=None, lowest_levels=None,
-                       allow_partial=False):
+                       allow_partial=False, source=None):
         """alignB_ng with seeding on (-Q1 .. -Q3, spdp_align_b_seeded): result as align_b; a pair the program prints no record
         for comes back with an empty skl.  model: an abi.WilipModel (defaults.wilip_model_b()), the library's own HSP search
         at every level; hsps[i]: (n_i + 1, 5) int32 array (b->jxt with its free slot) or None, lowest_levels[i] = b->wllvl.
-        last_call_s = seconds spent in the library."""
-        import time
-        n = len(ps)
-        keep = []
-        jx = (C.c_void_p * n)()
-        nh = (C.c_int32 * n)()
-        lv = (C.c_int32 * n)(*[int(x) for x in (lowest_levels if lowest_levels is not None else [0] * n)])
-        for i, h in enumerate(hsps or []):
-            if h is None or len(h) < 2:
-                continue
-            a = np.ascontiguousarray(h, dtype=np.int32)
-            keep.append(a)
-            jx[i] = a.ctypes.data
-            nh[i] = a.shape[0] - 1
-        arr = (abi.Alignment * n)()
-        probs = ps.array()
-        sp.wilip = C.addressof(model) if model is not None else None
-        t0 = time.perf_counter()
-        rc = self.lib.spdp_align_b_seeded(self.ctx, C.byref(sc), C.byref(up), C.byref(sp), probs, n, jx, nh, lv, None, arr)
-        self.last_call_s = time.perf_counter() - t0
-        sp.wilip = None
-        if not (allow_partial and rc == 1):
-            self._check(rc, "spdp_align_b_seeded")
-        res = []
-        for i in range(n):
-            k = arr[i].n_skl
-            skl = np.ctypeslib.as_array(C.cast(arr[i].skl, C.POINTER(C.c_int32)), shape=(k, 2)).copy() if k else np.zeros((0, 2), dtype=np.int32)
-            res.append((int(arr[i].score), skl))
-        self.lib.spdp_free_alignments(arr, n)
+        source: the caller's HSP search in place of the model, source(pair, level, span of 8 ints) -> the flat int32 record
+        SpdpHspSource::units hands over, or None.  last_call_s = seconds spent in the library."""
+        res, self.last_call_s = _seeded_call_b(self.lib, self.ctx, self._check, "spdp_align_b_seeded", sc, up, sp, ps, model, hsps, lowest_levels,
+                                               allow_partial, source)
         return res
 
     SEEDED_STATS_B = ("walks", "hsp_searches", "device_batches", "thin_requests", "wide_requests", "host_requests", "requests_le16_rows",

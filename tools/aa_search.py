@@ -20,7 +20,13 @@ bytes that hold the program's heap (blocks.bka_without_heap_bytes).
 
 Compared per query: the ordered hit list (name, printed score, the corners as -O4 prints them, the aligned ranges).  One JSON line: reference
 aligned, library aligned, identical, seconds of both (the library's call warm: the median of --repeat calls after a first one),
-the library's split from spdp_blk_finds_stats and the vote kernel's HIP-event time.  Reads nothing of the reference's sources."""
+the library's split from spdp_blk_finds_stats and the vote kernel's HIP-event time.  Reads nothing of the reference's sources.
+
+--members N puts N contexts ON DEVICE 0 behind one device group (--gpus a,b,..: one context on each of these devices), an index per
+member, and the call becomes ONE spdp_group_map_align_b call: the records compared with the program's are then the group's, the
+single-context call is still timed beside it, and "group" in the JSON line holds the group call's seconds and every member's load
+(queries, 1 + length summed: the cost the shards are balanced by).  Several members on one card share that card: the figures say
+what the fan-out and the gathering cost and that the records are the same, not how the call scales."""
 import argparse
 import ctypes as C
 import json
@@ -125,7 +131,10 @@ def main() -> int:
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--no-reference", action="store_true", help="library only (a profiler run): nothing is compared")
     ap.add_argument("--library-index", action="store_true", help="the library builds its own index of the database instead of reading prot.bka")
+    ap.add_argument("--members", type=int, default=0, help="N: the call goes through a device group of N contexts, all on device 0 (spdp_group_map_align_b)")
+    ap.add_argument("--gpus", default="", help="a,b,..: the same with one context on each of these devices")
     args = ap.parse_args()
+    devices = [int(x) for x in args.gpus.split(",")] if args.gpus else [0] * max(args.members, 0)
     rng = np.random.default_rng(args.seed)
     db, queries = make_data(rng, args.sequences, args.queries)
     with tempfile.TemporaryDirectory() as td:
@@ -184,6 +193,8 @@ def main() -> int:
             arrays, fprm = blocks.read_protein_db_index(eng.lib, os.path.join(td, "prot.bka"), max_out=args.max_out)
         dix = blocks.BlockIndex(eng, arrays)
         load_s = time.perf_counter() - t0
+        grp = engine.Group(devices) if devices else None
+        gix = blocks.GroupIndex(grp, arrays) if grp else None
     sc, up, model = defaults.scoring_b(), abi.UnsplicedParams(1.0, 0), defaults.wilip_model_b()
     sp = defaults.seed_params_b(3, 15)
     sp.wilip = C.addressof(model)
@@ -199,6 +210,26 @@ def main() -> int:
     lib_s, st = times[k], splits[k]
     _, ms = blocks.finds(dix, fprm, q_codes)             # the vote alone: HIP-event time
     dix.free()
+    group = None
+    if grp:                                             # the same call on the group: its records are the ones compared below
+        blocks.group_map_align_b(gix, db_codes, db_off, sc, up, sp, fprm, q_codes[:min(64 * len(devices), len(q_codes))], all_out=args.all_out)
+        g_times, g_secs = [], []
+        for _ in range(max(1, args.repeat)):
+            t0 = time.perf_counter()
+            got, sec = blocks.group_map_align_b(gix, db_codes, db_off, sc, up, sp, fprm, q_codes, all_out=args.all_out)
+            g_times.append(time.perf_counter() - t0)
+            g_secs.append(sec)
+        member = grp.shards(len(q_codes))
+        k = int(np.argsort(g_times)[len(g_times) // 2])
+        cost = np.array([1 + len(q) for q in q_codes], dtype=np.int64)
+        group = dict(devices=devices, library_s=round(g_times[k], 4), library_s_all=[round(t, 4) for t in g_times],
+                     seconds_vote_align_host_call=[round(x, 4) for x in g_secs[k]],
+                     queries_per_member=[int((member == r).sum()) for r in range(len(devices))],
+                     load_per_member=[int(cost[member == r].sum()) for r in range(len(devices))], largest_cost=int(cost.max()),
+                     split_per_member=[blocks.finds_stats(grp.context(r)) for r in range(len(devices))],
+                     over_one_context=round(g_times[k] / lib_s, 3))
+        gix.free()
+        grp.close()
     def spans(t):                                       # where the first triple begins and the last one ends
         return (t[0], t[-3] + t[-1] - 1, t[1], t[-2] + t[-1] - 1)
     want = None if want is None else {k: [(b, v, t, spans(t)) for b, v, t in recs] for k, recs in want.items()}
@@ -213,8 +244,9 @@ def main() -> int:
         c["aligned"] += bool(hits)
         c["source_first"] += bool(hits) and hits[0]["seq"] == src
     print(json.dumps({
-        "what": "every record `spaln -Q7 -A0 -O4%s%s -a<db>` prints against one spdp_map_align_b call" %
-                (f" -M{args.max_out}" if args.max_out > 1 else "", " -pw" if args.all_out else ""),
+        "what": "every record `spaln -Q7 -A0 -O4%s%s -a<db>` prints against one %s call" %
+                (f" -M{args.max_out}" if args.max_out > 1 else "", " -pw" if args.all_out else "", "spdp_group_map_align_b" if group else "spdp_map_align_b"),
+        "group": group,
         "sequences": len(db), "queries": len(queries), "reference_aligned": None if want is None else len(want), "library_aligned": len(mine),
         "identical": None if bad is None else len(queries) - len(bad), "of": len(queries), "first_differing": None if bad is None else bad[:5],
         "reference_threads": args.threads, "reference_s": None if ref_s is None else round(ref_s, 3),

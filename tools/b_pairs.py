@@ -146,16 +146,18 @@ def exg_of(lcl: int):
     return (1 if lcl & 4 else 0, 1 if lcl & 8 else 0, 1 if lcl & 1 else 0, 1 if lcl & 2 else 0)
 
 
-def library_records(eng, sc, up, pairs, lcl, seeded=None):
+def library_records(eng, sc, up, pairs, lcl, seeded=None, grp=None):
     """the library's record per pair: (corners 1-based after trimskl, stat dict, engine score); (None, None, score) where
-    there is no alignment.  seeded = (SeedParams, WilipModel): through spdp_align_b_seeded instead of spdp_align_b"""
+    there is no alignment.  seeded = (SeedParams, WilipModel): through spdp_align_b_seeded instead of spdp_align_b; grp: an
+    engine.Group that runs the call in place of the engine (spdp_group_align_b / _align_b_seeded)"""
     from spaln_amd import abi, synth
     ps = abi.ProblemSet()
     for a, b in pairs:
         ps.add(synth.encode_protein(np.frombuffer(a.encode(), dtype=np.uint8)), synth.encode_protein(np.frombuffer(b.encode(), dtype=np.uint8)),
                None, None, exg=exg_of(lcl))
-    alns = eng.align_b_seeded(sc, up, seeded[0], ps, model=seeded[1]) if seeded else eng.align_b(sc, up, ps)
-    dt = eng.last_call_s                   # the call alone: upload, walks, kernels, download, corner lists
+    who = grp or eng
+    alns = who.align_b_seeded(sc, up, seeded[0], ps, model=seeded[1]) if seeded else who.align_b(sc, up, ps)
+    dt = who.last_call_s                   # the call alone: upload, walks, kernels, download, corner lists
     stats = eng.skl_rng_b(sc, up, ps, [s for _, s in alns])
     out = []
     for (score, skl), st in zip(alns, stats):
@@ -194,6 +196,9 @@ def main() -> int:
     ap.add_argument("--no-reference", action="store_true", help="library only (a profiler run): nothing is compared")
     ap.add_argument("--qck", type=int, default=0, help="1 .. 3: the reference with -Q<n> against the seeded entry (spdp_align_b_seeded); 0: -Q0")
     ap.add_argument("--repeat", type=int, default=1, help="timed repetitions of the library call (after the warm-up call)")
+    ap.add_argument("--members", type=int, default=0, help="N: the call also goes through a device group of N contexts, all on device 0 (spdp_group_align_b / "
+                    "_align_b_seeded); the records compared are then the group's.  Members on one card share it: no scaling figure")
+    ap.add_argument("--gpus", default="", help="a,b,..: the same with one context on each of these devices")
     args = ap.parse_args()
     from spaln_amd import abi, defaults, engine
 
@@ -224,11 +229,26 @@ def main() -> int:
         times.append(lib_s)
     lib_s = float(np.median(times))
     extra = {}
+    devices = [int(x) for x in args.gpus.split(",")] if args.gpus else [0] * max(args.members, 0)
+    if devices:                                         # the same call on the group: its records are the ones compared below
+        grp = engine.Group(devices)
+        library_records(eng, sc, up, pairs[:min(len(pairs), 64 * len(devices))], args.lcl, seeded, grp)
+        g_times = []
+        for _ in range(max(1, args.repeat)):
+            got, g_s, ps = library_records(eng, sc, up, pairs, args.lcl, seeded, grp)
+            g_times.append(g_s)
+        member = grp.shards(len(pairs))
+        cost = np.array([eng.cells_b(p, sc.sh) for p in ps.items], dtype=np.int64)
+        extra["group"] = dict(devices=devices, library_align_s=round(float(np.median(g_times)), 4), library_align_s_all=[round(t, 4) for t in g_times],
+                              pairs_per_member=[int((member == r).sum()) for r in range(len(devices))],
+                              cells_per_member=[int(cost[member == r].sum()) for r in range(len(devices))], largest_cost=int(cost.max()),
+                              over_one_context=round(float(np.median(g_times)) / lib_s, 3))
+        grp.close()
     if seeded:
         st = eng.seeded_stats_b()
         dp = st["thin_requests"] + st["wide_requests"] + st["requests_not_computed"]
-        extra = {"seeded_stats": st, "share_requests_le16_rows": round(st["requests_le16_rows"] / max(dp, 1), 4),
-                 "share_cells_le16_rows": round(st["cells_le16_rows"] / max(st["cells"], 1), 4)}
+        extra.update({"seeded_stats": st, "share_requests_le16_rows": round(st["requests_le16_rows"] / max(dp, 1), 4),
+                      "share_cells_le16_rows": round(st["cells_le16_rows"] / max(st["cells"], 1), 4)})
         eng.align_b(sc, up, ps)                                                    # (warm) the full DP on the same pairs
         eng.align_b(sc, up, ps)
         extra["library_full_dp_align_s"] = round(eng.last_call_s, 4)
@@ -241,7 +261,8 @@ def main() -> int:
     bad = [] if want1 is None else [i for i in range(len(pairs))
            if not same_record(got[i], want1[i][0] if want1[i] else None, want1[i][1] if want1[i] else 0.0, want0[i], defaults.B_SCALE)]
     print(json.dumps({
-        "what": "every record `spaln -Q0 -A0 -ip -pw %s` prints against %s + spdp_skl_rng_b" % (" ".join(opts), "spdp_align_b_seeded" if seeded else "spdp_align_b"),
+        "what": "every record `spaln -Q0 -A0 -ip -pw %s` prints against %s%s + spdp_skl_rng_b" % (" ".join(opts), "spdp_group_" if devices else "spdp_",
+                                                                                               "align_b_seeded" if seeded else "align_b"),
         "pairs": len(pairs), "identical": None if want1 is None else len(pairs) - len(bad), "first_differing": bad[:5], "cells": cells,
         "library_align_s": round(lib_s, 4), "library_pairs_per_s": round(len(pairs) / lib_s, 1), "library_gcups": round(cells / lib_s / 1e9, 3),
         "library_homscore_s": round(score_s, 4),
