@@ -922,7 +922,15 @@ int spdp_blk_finds_params_default(const SpdpBlkIndexHost* h, int32_t max_out, in
  * or rose), n_cand = min(max_out, sigm) and the candidate sequences in the order finds fills sqs[1..] (findChrNo of each block;
  * -1 - c for a sequence met before, whose slot keeps what it held: the shash rule, :3353-3354).  sigm = 0: finds returns ERROR.
  * Refused by name: a null argument, a nucleotide index, an index read for a genomic database, Ncand != max_out + 10, a database
- * of more than 2^24 blocks (what holds rscr: DESIGN.md 5b), out_cap < 6, a bad range.  kernel_ms (may be NULL): HIP-event time.
+ * of more than 2^24 blocks when the scores are held in the slab (below), out_cap < 6, a bad range.  kernel_ms (may be NULL):
+ * HIP-event time, summed over the call's launches.
+ * What holds rscr: a wave keeps the scores of its query either in a SLAB of nseg + 1 slots (8 bytes a block per
+ * resident wave; at most 2^24 blocks) or in an open-addressed TABLE of S slots keyed by block, whose size does not depend on the
+ * database.  A query that scores more than S blocks ends at once and is run again by the call on tables of 4 S slots, and so on: no
+ * record of such a run reaches the caller, and a table of nseg + 1 slots cannot fill (when not even one wave's table can be
+ * allocated the call is refused by name).  SPDP_FINDS_RSCR=slab|hash in the environment when an index is first searched
+ * chooses (unset: the slab up to 2^24 blocks, the table beyond; any other word is refused), SPDP_FINDS_RSCR_SLOTS=<n> the first S
+ * (rounded up to a power of two, at least 64; default 2^15).  The records do not depend on either (tests/test_gpu_finds_store.py).
  * The run hash of a wave lives in LDS when its reference-sized table takes at most 24 KB, else in the wave's slab of HBM;
  * SPDP_FINDS_HH_LDS=0 in the environment when an index is first searched puts it in the slab whatever its size (the records do
  * not depend on it: tests/test_gpu_finds_cases.py). */
@@ -934,6 +942,11 @@ int spdp_blk_finds(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexD
 int spdp_blk_finds_resident(SpdpContext* ctx, const SpdpBlkIndex* ix, const SpdpBlkIndexDesc* hix, const SpdpBlkFindsParams* prm,
                             const uint8_t* d_codes, const int64_t* d_offs, const int32_t* d_left, const int32_t* d_right, int32_t n,
                             int32_t* d_out, int32_t out_cap, float* kernel_ms);
+/* what held the scores in the last spdp_blk_finds[_resident] call of this context: [0] the form (0 slab, 1 table), [1] the waves
+ * launched first, [2] the bytes of one wave's area, [3] the first S, [4] the last S (both 0 for the slab), [5] launches, [6] queries
+ * run again after a full table, [7] the most distinct blocks one query scored (table form; 0 for the slab) */
+#define SPDP_BLK_FINDS_STORE_STATS_N 8
+int spdp_blk_finds_store_stats(const SpdpContext* ctx, int64_t* out, int n);
 
 /* ---- block search, third slice (round 5): from the vote to candidate loci ------------------------------------------------
  * What SrchBlk::findblock returns to its caller: TestOutput's second half (src/blksrc.cc:2677-2692: the candidate block pairs

@@ -564,5 +564,8 @@ class MapHitB(C.Structure):              # SpdpMapHitB
 
 
 # spdp_blk_vote_stats (include/spdp.h): the path counters of the block vote, in the order the library writes them
+# spdp_blk_finds_store_stats (SPDP_BLK_FINDS_STORE_STATS_N): what held the scores of the last spdp_blk_finds call
+BLK_FINDS_STORE_STATS = ("form", "waves", "area_bytes", "first_slots", "last_slots", "launches", "rerun_queries", "most_blocks")
+
 BLK_VOTE_STATS = ("queries", "zero_ended", "lds_merges", "lane_merges", "splits", "lane_entries",
                   "hash_growths", "hits_growths", "runs_growths", "wipes", "hbm_queries", "no_prefetch", "table")

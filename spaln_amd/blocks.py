@@ -270,6 +270,19 @@ def finds_stats(eng) -> dict:
     return dict(zip(FINDS_STATS, (int(x) for x in v)))
 
 
+def finds_store_stats(eng) -> dict:
+    """spdp_blk_finds_store_stats: what held the scores in the last finds() call on this engine -- form (0 slab, 1 table), waves,
+    area_bytes of one wave, first_slots / last_slots of a table, launches, rerun_queries after a full table, most_blocks a query
+    scored (table form)"""
+    from . import abi
+    v = (C.c_int64 * len(abi.BLK_FINDS_STORE_STATS))()
+    eng.lib.spdp_blk_finds_store_stats.restype = C.c_int
+    eng.lib.spdp_blk_finds_store_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    if eng.lib.spdp_blk_finds_store_stats(eng.ctx, v, len(v)):
+        raise RuntimeError("spdp_blk_finds_store_stats: null argument")
+    return dict(zip(abi.BLK_FINDS_STORE_STATS, (int(x) for x in v)))
+
+
 def map_align_b(index: "BlockIndex", db_codes, seq_off, sc, up, sp, fprm, queries, all_out: bool = False):
     """spdp_map_align_b: what `spaln -Q4 .. -Q7 -a<db> [-M N] [-pw]` prints of protein queries against a protein database -- the
     vote of finds, every candidate aligned (spdp_align_b_seeded with sp.qck = 1 .. 3, spdp_align_b with 0), the threshold sp.vthr

@@ -13,8 +13,9 @@
 // run hash keeps the reference's slot geometry (Dhash<INT,int>(2 MaxBlk, 0): home key % size1, stride size2 - key % size2, a
 // block that fails to continue is written EMPTY, which cuts the probe chains that ran over it -- results depend on it), its 64
 // updates of a chunk decided on a snapshot and committed up to the first lane whose probe path meets a lower lane's write; the
-// scores rscr[block] are {query tag, value} slots of the wave's slab, never cleared; the Ncand heap sits in LDS, offers are
-// decided in parallel and applied lowest lane first.
+// scores rscr[block] are {query tag, value} slots, never cleared, in one of two stores (FindsWave::store): the wave's slab of
+// nseg + 1 slots, a block's slot at its number, or an open-addressed table of tb_n slots keyed by block ("score slots" below);
+// the Ncand heap sits in LDS, offers are decided in parallel and applied lowest lane first.
 #ifndef SPDP_BLK_FINDS_H_
 #define SPDP_BLK_FINDS_H_
 #include <stdint.h>
@@ -37,6 +38,11 @@ FD int finds_uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 // slots other lanes of the wave write: read and written past the L1, as the findblock vote does
 FD uint64_t finds_ld(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 FD void finds_st(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// a slot several lanes may want at once: *p becomes `now` if it still holds `was` (-> 1), else it is left alone (-> 0)
+FD int finds_cas(uint64_t* p, uint64_t was, uint64_t now)
+{
+    return __hip_atomic_compare_exchange_strong(p, &was, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 FD int finds_first(uint64_t m) { return __ffsll((long long) m) - 1; }
 FD int finds_popc(uint64_t m) { return __popcll(m); }
 #else
@@ -49,13 +55,15 @@ inline void finds_own_min(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
 inline int finds_uni(int x) { return x; }
 inline uint64_t finds_ld(const uint64_t* p) { return *p; }
 inline void finds_st(uint64_t* p, uint64_t v) { *p = v; }
+inline int finds_cas(uint64_t* p, uint64_t was, uint64_t now) { if (*p != was) return 0; *p = now; return 1; }      // (one lane after the other: a plain compare and store)
 inline int finds_first(uint64_t m) { return __builtin_ffsll((long long) m) - 1; }
 inline int finds_popc(uint64_t m) { return __builtin_popcountll(m); }
 #endif
 
-enum { FST_FRONT = 0, FST_TROUBLE = 1, FST_TW0 = 2, FST_TW1 = 3, FST_STAGED = 4, FST_WORDS = 8 };
+enum { FST_FRONT = 0, FST_TROUBLE = 1, FST_TW0 = 2, FST_TW1 = 3, FST_STAGED = 4, FST_FULL = 5, FST_WORDS = 8 };
 
-// what a wave works with.  LDS: st, as, own, heap (and hh when it fits); the slab in HBM: rscr, stage (and hh when it does not)
+// what a wave works with.  LDS: st, as, own, heap (and hh when it fits); the wave's area of HBM: rscr or tb, stage (and hh when
+// it does not)
 struct FindsWave {
     const BlkDev* X;
     const int32_t* lenadj;              // per block Randbs::lencor(SegLen[blk]) (setSegLen :1966-1983), nseg + 1 of them
@@ -66,6 +74,10 @@ struct FindsWave {
     uint64_t* hh; uint32_t hh_n, hh_step, epoch;        // the run hash: key << 32 | epoch << 16 | count
     uint64_t* rscr; uint32_t tag;       // tag << 32 | value
     uint32_t* stage;                    // two posting lists merged (2 maxlist + 2)
+    int store = 0;                      // what holds the scores: 0 the slab rscr, 1 the table tb
+    uint64_t* tb = nullptr;             // tb_n slots of two words: block << 32 | tag, tag << 32 | value
+    uint32_t tb_n = 0, tb_shift = 0;    // a power of two, and 32 - its logarithm
+    int n_scored = 0;                   // the distinct blocks the query has scored so far (counted in the table form only)
 };
 
 FD uint32_t finds_no_lane() { return 0xffffffffu; }
@@ -163,13 +175,38 @@ FD FindsWord finds_word(const FindsWave& W, const uint8_t* q, int q_len, int rig
     return w;
 }
 
-// ---- score slots
-FD int finds_rscr_get(const FindsWave& W, uint32_t blk)
+// ---- score slots.  A value is {query tag, value}: a slot of an earlier query reads as 0 and nothing is cleared between queries.
+// The slab: the slot of a block is at its number.  The table: a slot is two words, {block, tag} and {tag, value}; a block's slot is
+// the first of its probe sequence (home = the block's multiplicative hash, then the next slot, round the table) that holds the
+// block under this query's tag, or the first that holds no block of this query, which the lane claims with finds_cas -- the lanes
+// of a chunk insert at the same time and may want the same free slot; the loser reads the slot again, finds this query's tag in it
+// and walks on.  UNLIKE THE RUN HASH, NO RESULT DEPENDS ON THE SLOT GEOMETRY: a block's value is only read, increased and written
+// back, nothing is ever emptied, so any table size and any probe that visits every slot give the same records.  A block twice in
+// one chunk (a malformed index): both lanes end on one slot, each adds to what it read, one store stays -- as in the slab.
+// get -> the value, `at`: where put writes it, finds_no_lane() when the probe went round a table full of this query's blocks;
+// fresh: the block had no slot in this query yet and this lane made it one
+FD int finds_rscr_value(const FindsWave& W, uint64_t x) { return (uint32_t) (x >> 32) == W.tag ? (int) (uint32_t) x : 0; }
+FD int finds_rscr_get(const FindsWave& W, uint32_t blk, uint32_t& at, int& fresh)
 {
-    const uint64_t x = finds_ld(W.rscr + blk);
-    return (uint32_t) (x >> 32) == W.tag ? (int) (uint32_t) x : 0;
+    fresh = 0;
+    if (!W.store) { at = blk; return finds_rscr_value(W, finds_ld(W.rscr + blk)); }
+    const uint64_t mine = ((uint64_t) blk << 32) | W.tag;
+    uint32_t s = (blk * 0x9e3779b1u) >> W.tb_shift;
+    for (uint32_t seen = 0; seen < W.tb_n; ) {
+        uint64_t* slot = W.tb + 2 * (size_t) s;
+        const uint64_t k = finds_ld(slot);
+        if (k == mine) { at = s; return finds_rscr_value(W, finds_ld(slot + 1)); }
+        if ((uint32_t) k == W.tag) { s = (s + 1) & (W.tb_n - 1); ++seen; continue; }    // another block of this query
+        if (finds_cas(slot, k, mine)) { at = s; fresh = 1; return 0; }                  // (its value word is an earlier query's: 0)
+        // lost to another lane: the slot now carries this query's tag and is not free again, so it is read once more, not for ever
+    }
+    at = finds_no_lane();
+    return 0;
 }
-FD void finds_rscr_put(const FindsWave& W, uint32_t blk, int v) { finds_st(W.rscr + blk, ((uint64_t) W.tag << 32) | (uint32_t) v); }
+FD void finds_rscr_put(const FindsWave& W, uint32_t at, int v)
+{
+    finds_st(W.store ? W.tb + 2 * (size_t) at + 1 : W.rscr + at, ((uint64_t) W.tag << 32) | (uint32_t) v);
+}
 
 // ---- the run hash
 FD uint32_t finds_hh_key(uint64_t s) { return (uint32_t) (s >> 32); }
@@ -319,7 +356,7 @@ FD int finds_vote(FindsWave& W, const FindsWord& w, int p, int threshold)
         }
         uint64_t pend = finds_ballot(have);
         while (pend) {
-            PerLane<uint32_t> slot; PerLane<int> cur, ok, writes, meets, sig, run;
+            PerLane<uint32_t> slot; PerLane<int> cur, ok, writes, meets, sig, run, fresh;
             EACH_LANE(l) {
                 slot[l] = 0; cur[l] = 0; ok[l] = 0; writes[l] = 0;
                 if ((pend >> l) & 1) {
@@ -340,18 +377,26 @@ FD int finds_vote(FindsWave& W, const FindsWord& w, int p, int threshold)
             EACH_LANE(l) if (writes[l]) W.own[slot[l] & (SPDP_FINDS_OWN - 1)] = finds_no_lane();
             const uint64_t go = pend & (met ? ((1ull << finds_first(met)) - 1) : ~0ull);
             EACH_LANE(l) {
-                sig[l] = 0; run[l] = 0;
+                sig[l] = 0; run[l] = 0; fresh[l] = 0;
                 if ((go >> l) & 1) {
                     if (ok[l]) {
                         finds_hh_put(W, slot[l], blk[l], p);
-                        run[l] = finds_rscr_get(W, blk[l]) + w.score;
-                        finds_rscr_put(W, blk[l], run[l]);
-                        sig[l] = run[l] >= threshold + W.lenadj[blk[l]];
+                        uint32_t at;
+                        run[l] = finds_rscr_get(W, blk[l], at, fresh[l]) + w.score;
+                        if (at == finds_no_lane()) W.st[FST_FULL] = 1;
+                        else {
+                            finds_rscr_put(W, at, run[l]);
+                            sig[l] = run[l] >= threshold + W.lenadj[blk[l]];
+                        }
                     } else if (cur[l] > 0) finds_hh_put(W, slot[l], blk[l], 0);
                 } else ok[l] = 0;
             }
             finds_sync();
             went_on += finds_popc(finds_ballot(ok));
+            if (W.store) {
+                W.n_scored += finds_popc(finds_ballot(fresh));
+                if (finds_uni(W.st[FST_FULL])) return went_on;              // the table is full: the query is over (finds_query)
+            }
             const uint64_t sigm = finds_ballot(sig);
             if (sigm) finds_offer_in_order(W, sigm, blk, run);
             pend &= ~go;                                // (the lowest pending lane meets nobody: every turn commits at least one)
@@ -360,19 +405,21 @@ FD int finds_vote(FindsWave& W, const FindsWord& w, int p, int threshold)
     return went_on;
 }
 
-// SrchBlk::finds for one query.  The record: [0] ints used, [1] nmmc the scan ended in, [2] flags (SPDP_BLK_REACHED: searched;
+// SrchBlk::finds for one query.  -> 1: the score table ran full; the query ended there, NOTHING was written to out and the caller
+// runs it again on a larger table (0 otherwise, and always with the slab).  The record: [0] ints used, [1] nmmc the scan ended in, [2] flags (SPDP_BLK_REACHED: searched;
 // SPDP_BLK_SHORT: refused, nothing follows; SPDP_BLK_CUT; SPDP_BLK_TABLE), [3] [4] testword, [5] sigm, (block, score) x sigm in
 // hsort order, n_cand, the candidate sequences (-1 - c for a sequence seen before: its slot keeps what it held)
-FD void finds_query(FindsWave& W, const uint8_t* q, int q_len, int left, int right, int32_t* out, int out_cap)
+FD int finds_query(FindsWave& W, const uint8_t* q, int q_len, int left, int right, int32_t* out, int out_cap)
 {
     const BlkDev& X = *W.X;
     const int nshift = X.nshift, width0 = X.bitpat[X.pat_off[0] + 1];
     const int qlen = right - left;
     EACH_LANE(l) if (l < FST_WORDS) W.st[l] = 0;
+    W.n_scored = 0;
     finds_sync();
     if (qlen - (nshift + width0) < 1 || nshift > SPDP_BLK_MAX_SHIFT || qlen > SPDP_FINDS_MAX_QUERY) {
         EACH_LANE(l) if (l == 0) { if (out_cap > 0) out[0] = out_cap < 3 ? out_cap : 3; if (out_cap > 1) out[1] = 0; if (out_cap > 2) out[2] = SPDP_FINDS_SHORT; }
-        return;
+        return 0;
     }
     // init2: Nshift consecutive start points at the left end, the last Nshift whole words at the right end, the phase of a
     // right-end point chosen so that the two ends of a phase are a multiple of Nshift apart
@@ -385,12 +432,12 @@ FD void finds_query(FindsWave& W, const uint8_t* q, int q_len, int left, int rig
     const int c = qlen / (2 * nshift) - 1;
     const int rms = right - nshift * (c < W.ptpl ? c : W.ptpl);
     const int base = X.rscrtab[0];
-    int meet = 0;
+    int meet = 0, full = 0;
     uint32_t nmmc = 0;
-    for ( ; nmmc < (uint32_t) W.maxmmc && !meet; ++nmmc) {
+    for ( ; nmmc < (uint32_t) W.maxmmc && !meet && !full; ++nmmc) {
         const int threshold = finds_randbs(X, nmmc);
-        for (int d = 0; d < 2; ++d) {
-            for (int s = 0; s < nshift; ++s) {
+        for (int d = 0; d < 2 && !full; ++d) {
+            for (int s = 0; s < nshift && !full; ++s) {
                 int ms = finds_uni(W.as[32 * (1 - d) + s]);
                 if (ms > rms) ms = rms;
                 int cscr = 0, p = 0, more = 0;
@@ -407,11 +454,13 @@ FD void finds_query(FindsWave& W, const uint8_t* q, int q_len, int left, int rig
                     if (w.score == 0) { more = 1; continue; }           // ubiquitous
                     ++p; cscr += w.score;
                     more = finds_vote(W, w, p, threshold);
-                } while (more && cscr < base);
+                    if (W.store) full = finds_uni(W.st[FST_FULL]);
+                } while (more && cscr < base && !full);
             }
         }
     }
     finds_sync();
+    if (full) return 1;
     // hsort, the first min(MaxOut, sigm) blocks, findChrNo on each (one lane)
     EACH_LANE(l) if (l == 0) {
         const int sigm = W.st[FST_FRONT];
@@ -438,5 +487,6 @@ FD void finds_query(FindsWave& W, const uint8_t* q, int q_len, int left, int rig
         if (out_cap > 5) out[5] = sigm;
     }
     finds_sync();
+    return 0;
 }
 #endif

@@ -4,16 +4,27 @@
 #define SPDP_BLK_FINDS_DEV_H_
 #include "spdp_blk_dev.h"
 
-// WHAT HOLDS rscr.  The reference keeps rscr[nseg] per thread and clears it per query.  Here a wave owns a slab of nseg + 1
-// {query tag, value} slots in HBM (8 bytes a block): nothing is cleared between queries, and a posting entry costs one load and
-// one store at an address its block number gives.  The other form -- a per-wave hash keyed by block, sized by the blocks a query
-// touches -- would bound the memory by the query instead of the database; nobody has measured which of the two is faster, the
-// slab was chosen because the genome vote has it and a probe sequence per posting entry is what the run hash already costs.
-// Its limit: a launch wants at least SPDP_FINDS_MIN_WAVES slabs inside SPDP_FINDS_SLAB_BUDGET, so a database of more than
-// SPDP_FINDS_MAX_BLOCKS blocks (one block per sequence in a -KA index) is refused by name.
+// WHAT HOLDS rscr.  The reference keeps rscr[nseg] per thread and clears it per query.  Here a wave owns an area of HBM, in one of
+// two forms, and in both a score is a {query tag, value} word that an earlier query's tag makes read as 0, so nothing is cleared
+// between queries (the tags come round after 2^32 - 1 queries of a wave; the wave then wipes its scores once):
+//   * THE SLAB: nseg + 1 slots, a block's slot at its number -- one load and one store per posting entry, 8 bytes a block per wave.
+//     A launch wants at least SPDP_FINDS_MIN_WAVES areas inside SPDP_FINDS_SLAB_BUDGET, so the slab serves a database of at most
+//     SPDP_FINDS_MAX_BLOCKS blocks (one block per sequence in a -KA index) and is refused by name beyond;
+//   * THE TABLE: S slots (a power of two) of 16 bytes, {block, tag} and {tag, value}, open-addressed and keyed by block
+//     (spdp_blk_finds.h, "score slots") -- a probe and a compare-and-swap for a block's first entry, a probe, a load and a store for
+//     the later ones.  The area is a header, the table, the staging list and the run hash when LDS has no room for it: NOTHING IN IT
+//     GROWS WITH nseg (lenadj stays one array for all waves).  A query whose blocks fill the table ends at once, writes no record
+//     and puts its number on the launch's list (BlkFindsArgs::over, counted in next[1]); the host reads the counter and the word beside it, the
+//     most blocks a query scored -- 8 bytes, all there is to read when nothing overflowed --, runs the listed queries again on tables of 4 S slots (BlkFindsArgs::which), and so on until the list
+//     is empty.  A table of at least nseg + 1 slots cannot fill (the probe visits every slot, a block number is below nseg).
+// SPDP_FINDS_RSCR=slab|hash in the environment when an index is first searched chooses; unset: the slab up to
+// SPDP_FINDS_MAX_BLOCKS blocks, the table beyond.  SPDP_FINDS_RSCR_SLOTS=<n> sets the first S (rounded up to a power of two, at
+// least 64; default SPDP_FINDS_TABLE_SLOTS).  Both forms measured side by side: MEASUREMENTS.md, "Protein database search".
 #define SPDP_FINDS_SLAB_BUDGET ((size_t) 8 << 30)
 #define SPDP_FINDS_MIN_WAVES 64
 #define SPDP_FINDS_MAX_BLOCKS (1 << 24)
+#define SPDP_FINDS_TABLE_SLOTS (1u << 15)
+#define SPDP_FINDS_TABLE_MIN_SLOTS 64u
 #define SPDP_FINDS_HH_LDS_BYTES (24u << 10)     // the run hash lives in LDS up to this size (six waves a CU), in the slab beyond
 
 struct BlkFindsArgs {
@@ -22,15 +33,19 @@ struct BlkFindsArgs {
     int32_t max_out, ptpl, maxmmc;
     const uint8_t* codes; const int64_t* offs; const int32_t* left; const int32_t* right;
     int32_t* out; int out_cap, n;
-    uint8_t* slabs; size_t slab_bytes;          // one per wave of the launch; zero when allocated, kept between launches
-    uint32_t* next;                             // the launch's query counter
+    uint8_t* slabs; size_t slab_bytes;          // one area per wave of the launch; zero when allocated, kept between launches
+    uint32_t* next;                             // four words the launch clears: [0] its query counter, [1] the queries on `over`,
+                                                // [2] the most distinct blocks one query scored (table form)
+    uint32_t tb_n;                              // 0: the slab form; else the slots of a wave's table, a power of two
+    const int32_t* which;                       // null: queries 0 .. n - 1; else the n queries to run
+    int32_t* over;                              // table form: room for n query numbers
     int n_waves, hh_n, hh_step, hh_in_lds;
     uint32_t lds_bytes;
 };
 #ifdef __HIPCC__
 extern "C" hipError_t spdp_blk_finds_launch(const BlkFindsArgs* a, hipStream_t s);
 #endif
-extern "C" size_t spdp_blk_finds_slab_bytes(const BlkDev* ix, int hh_n, int hh_in_lds);
+extern "C" size_t spdp_blk_finds_area_bytes(const BlkDev* ix, int hh_n, int hh_in_lds, uint32_t tb_n);      // tb_n = 0: the slab form
 extern "C" uint32_t spdp_blk_finds_lds_bytes(const BlkDev* ix, int hh_n, int hh_in_lds);
 
 // the resident index as the finds entries see it (spdp_blk_api.cpp): its context, the index as the kernels read it (host view and

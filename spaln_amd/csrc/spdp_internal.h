@@ -360,6 +360,7 @@ struct SpdpContext {
     int64_t seed_stats[12] = {0};      // spdp_seeded_stats
     int64_t seed_stats_b[16] = {0};    // spdp_seeded_stats_b
     int64_t finds_stats[8] = {0};      // spdp_blk_finds_stats: the last spdp_map_align_b call (spdp_map_b_api.cpp)
+    int64_t finds_store[8] = {0};      // spdp_blk_finds_store_stats: the last spdp_blk_finds[_resident] call (spdp_blk_finds_api.cpp)
     int64_t hsp_stats[8] = {0};        // spdp_blk_find_stats: the HSP searches of the last block search (spdp_blk_api.cpp, HspBatch::run)
     // Seq::tlen of the problems of the seeded calls made while it is set (spdp_map_align_s_prep; problem i of spdp_align_s_seeded,
     // forward problems then reverse ones of _ori3): the walks' own HSP searches end their forward extension there.  Null: a_len

@@ -42,6 +42,7 @@ EXPORTS = [
     "spdp_signal_records_s", "spdp_signal_records_h",
     "spdp_blk_find_stats", "spdp_hsp_plan", "spdp_hsp_tasks", "spdp_hsp_tasks_host",
     "spdp_blk_finds", "spdp_blk_finds_resident", "spdp_blk_finds_params_default", "spdp_map_align_b", "spdp_blk_finds_stats",
+    "spdp_blk_finds_store_stats",
     "spdp_blk_build_params_default_a", "spdp_blk_index_build_a",
     "spdp_group_homscore_b", "spdp_group_align_b", "spdp_group_align_b_seeded", "spdp_group_blk_finds", "spdp_group_map_align_b",
     "spdp_group_blk_find", "spdp_group_map_align_s_prep", "spdp_group_map_align_s_multi_prep", "spdp_group_map_align_s_dispersed",

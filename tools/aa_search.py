@@ -2,6 +2,7 @@
 """Protein queries against a protein database inside the library, against the reference's own program.
 
     python tools/aa_search.py [--queries 300] [--sequences 580] [--threads 16] [--max-out N] [--all-out] [--library-index]
+                              [--rscr slab|hash[,..]]
                                                                       (an MI355X box; oracle/_ref for the comparison)
 
 A synthetic protein database with paralog families and queries of eight classes (mutated at 15 / 35 / 50 %, fragments, every tenth
@@ -21,6 +22,13 @@ bytes that hold the program's heap (blocks.bka_without_heap_bytes).
 Compared per query: the ordered hit list (name, printed score, the corners as -O4 prints them, the aligned ranges).  One JSON line: reference
 aligned, library aligned, identical, seconds of both (the library's call warm: the median of --repeat calls after a first one),
 the library's split from spdp_blk_finds_stats and the vote kernel's HIP-event time.  Reads nothing of the reference's sources.
+
+--rscr slab|hash chooses what holds the scores of the vote (SPDP_FINDS_RSCR) for every index the run searches, and
+adds "rscr" to the JSON line: for the form (for each, when several are given with a comma; the first one serves the rest of the run)
+a FRESH index and on it the vote alone -- the first call (wall and kernel ms: the waves' areas are allocated and cleared in it),
+--repeat warm calls (kernel ms each), and spdp_blk_finds_store_stats of the last: waves, bytes of a wave's area, bytes of all,
+launches, queries run again, the most blocks a query scored.  "baseline" instead of a form leaves the variable alone (and asks no
+stats of a library that has no such entry: the parent's build through SPDP_LIB).
 
 --members N puts N contexts ON DEVICE 0 behind one device group (--gpus a,b,..: one context on each of these devices), an index per
 member, and the call becomes ONE spdp_group_map_align_b call: the records compared with the program's are then the group's, the
@@ -133,7 +141,13 @@ def main() -> int:
     ap.add_argument("--library-index", action="store_true", help="the library builds its own index of the database instead of reading prot.bka")
     ap.add_argument("--members", type=int, default=0, help="N: the call goes through a device group of N contexts, all on device 0 (spdp_group_map_align_b)")
     ap.add_argument("--gpus", default="", help="a,b,..: the same with one context on each of these devices")
+    ap.add_argument("--rscr", default="", help="slab|hash[,..]: what holds the vote's scores (SPDP_FINDS_RSCR); measures the vote alone on a fresh index per form")
     args = ap.parse_args()
+    forms = [f for f in args.rscr.split(",") if f]
+    if any(f not in ("slab", "hash", "baseline") for f in forms):
+        ap.error("--rscr: slab, hash or baseline")
+    if forms and forms[0] != "baseline":
+        os.environ["SPDP_FINDS_RSCR"] = forms[0]
     devices = [int(x) for x in args.gpus.split(",")] if args.gpus else [0] * max(args.members, 0)
     rng = np.random.default_rng(args.seed)
     db, queries = make_data(rng, args.sequences, args.queries)
@@ -210,6 +224,28 @@ def main() -> int:
     lib_s, st = times[k], splits[k]
     _, ms = blocks.finds(dix, fprm, q_codes)             # the vote alone: HIP-event time
     dix.free()
+    rscr = {}
+    for form in forms:                                  # the vote alone on a fresh index: what its first call costs, what a warm one
+        if form != "baseline":
+            os.environ["SPDP_FINDS_RSCR"] = form
+        vix = blocks.BlockIndex(eng, arrays)
+        t0 = time.perf_counter()
+        first, first_ms = blocks.finds(vix, fprm, q_codes)
+        first_s = time.perf_counter() - t0
+        warm, walls = [], []
+        for _ in range(max(1, args.repeat)):
+            t0 = time.perf_counter()
+            again, w_ms = blocks.finds(vix, fprm, q_codes)
+            walls.append(time.perf_counter() - t0)
+            warm.append(w_ms)
+        sst = blocks.finds_store_stats(eng) if hasattr(eng.lib, "spdp_blk_finds_store_stats") else None
+        vix.free()
+        rscr[form] = dict(first_call_s=round(first_s, 4), first_kernel_ms=round(first_ms, 3), warm_kernel_ms=[round(x, 3) for x in warm],
+                          warm_call_s=[round(x, 4) for x in walls], stats=sst, allocated_bytes=None if sst is None else sst["waves"] * sst["area_bytes"],
+                          records_crc=int(np.bitwise_xor.reduce(again.view(np.uint32).reshape(-1) * np.arange(1, again.size + 1, dtype=np.uint32))),
+                          same_as_first_call=bool(np.array_equal(first, again)))
+    if forms and forms[0] != "baseline":
+        os.environ["SPDP_FINDS_RSCR"] = forms[0]
     group = None
     if grp:                                             # the same call on the group: its records are the ones compared below
         blocks.group_map_align_b(gix, db_codes, db_off, sc, up, sp, fprm, q_codes[:min(64 * len(devices), len(q_codes))], all_out=args.all_out)
@@ -246,7 +282,7 @@ def main() -> int:
     print(json.dumps({
         "what": "every record `spaln -Q7 -A0 -O4%s%s -a<db>` prints against one %s call" %
                 (f" -M{args.max_out}" if args.max_out > 1 else "", " -pw" if args.all_out else "", "spdp_group_map_align_b" if group else "spdp_map_align_b"),
-        "group": group,
+        "group": group, "rscr": rscr or None,
         "sequences": len(db), "queries": len(queries), "reference_aligned": None if want is None else len(want), "library_aligned": len(mine),
         "identical": None if bad is None else len(queries) - len(bad), "of": len(queries), "first_differing": None if bad is None else bad[:5],
         "reference_threads": args.threads, "reference_s": None if ref_s is None else round(ref_s, 3),
