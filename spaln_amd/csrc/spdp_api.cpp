@@ -135,8 +135,11 @@ void DevPool::release()
 
 thread_local bool t_lane_copies = false;         // spdp_internal.h, spdp_copy_sync
 
-// lane i of a context: lane 0 is the context itself, the others are contexts of their own (streams, events, pools)
-// on the same device, created on first use and owned by the parent
+// lane i of a context: lane 0 is the context itself, the others are contexts of their own (stream, side stream, events,
+// pools, signal words, staging) on the same device, created on first use and owned by the parent.  Two lanes therefore
+// never touch one pool slot, and a lane's runs are waited for before a slot is taken again (DevRun::sync / release).
+// DevPool::get still frees and allocates when a slot has to grow, which waits for the whole device: the first call after
+// a change of plan stalls there behind the other lane's sweep, later calls do not.
 SpdpContext* spdp_lane(SpdpContext* ctx, int i)
 {
     if (i <= 0) return ctx;

@@ -194,9 +194,11 @@ struct ChunkGate {
     int wait() { std::unique_lock<std::mutex> g(m); cv.wait(g, [&] { return state != GATE_SHUT; }); return state; }
 };
 
-// the default plan of a big batch (align_on_store): chosen from the grid in profiles/chunk_handover_c2.txt
+// the default plan of a big batch (align_on_store): chosen from the grid in profiles/chunk_lanes_c2.txt.  With the lanes'
+// copies waiting for their own stream only, what follows the last sweep is the last chunk's post-work alone, so that chunk
+// is the smaller one; a third chunk still loses (a lane's next sweep waits for the post-work of its chunk before)
 constexpr int    kDefaultChunks = 2;
-constexpr double kDefaultChunkRatio = 1.0;
+constexpr double kDefaultChunkRatio = 0.55;
 
 struct Aligner {
     SpdpContext* ctx;                           // the lane this chunk runs on
@@ -633,11 +635,19 @@ static int align_on_store(SpdpContext* ctx, const DevStore* st, const SpdpProble
             cells[i] = spdp_cells(&probs[i], &w);
         }
         n_chunks = spdp_chunk_plan_of(cells.data(), n, max_chunks, ratio, min_chunk, bounds.data());
+        if (const char* e = getenv("SPDP_CHUNK_TEST_LAST"))     // test hook: the last chunk keeps its last <k> problems only
+            if (n_chunks > 1) bounds[n_chunks - 1] = std::max(bounds[n_chunks - 1], n - std::max(1, atoi(e)));
         if (getenv("SPDP_TIMING"))
             fprintf(stderr, "[spdp timing] %-28s %8.2f ms  (%d chunks)\n", "chunk plan (cells + bounds)",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_chunks);
     }
     const int n_lanes = std::min(n_chunks, 2);  // lane L runs chunks L, L + 2, .. one after the other; the gates chain c -> c + 1
+    // a plan of shrinking chunks (ratio < 1) comes with blocking copies that wait for the lane's own stream only
+    // (spdp_internal.h, at spdp_copy_sync): a chunk's post-work runs beside the next chunk's sweep, and only the last,
+    // smaller chunk's is left behind the last sweep.  Equal chunks keep the null-stream copies: the same post-work under
+    // a sweep measured 2.5 ms slower there (MEASUREMENTS).  SPDP_CHUNK_LANE_COPIES=1 / =0 sets the copies for any plan
+    const char* lane_env = getenv("SPDP_CHUNK_LANE_COPIES");
+    const bool own_copies = t_lane_copies || (n_chunks > 1 && (lane_env ? atoi(lane_env) != 0 : ratio > 0. && ratio < 1.));
     std::vector<Aligner> al(n_chunks);
     std::vector<ChunkGate> gates(n_chunks);
     std::vector<int> rc(n_chunks, 0);
@@ -671,8 +681,8 @@ static int align_on_store(SpdpContext* ctx, const DevStore* st, const SpdpProble
     };
     std::vector<std::thread> workers;
     for (int l = 1; l < n_lanes; ++l)
-        workers.emplace_back([&, l, lane_copies = t_lane_copies]() { (void) hipSetDevice(ctx->device); t_lane_copies = lane_copies; run_lane(l); });
-    run_lane(0);
+        workers.emplace_back([&, l]() { (void) hipSetDevice(ctx->device); LaneCopies own_stream(own_copies); run_lane(l); });
+    { LaneCopies own_stream(own_copies); run_lane(0); }
     for (std::thread& t : workers) t.join();
     ctx->chunk_stats[0] += 1; ctx->chunk_stats[1] += n_chunks;
     for (int c = 0; c + 1 < n_chunks; ++c) {

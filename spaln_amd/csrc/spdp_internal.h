@@ -255,16 +255,19 @@ enum { POOL_PROBS = 0, POOL_BND, POOL_TB, POOL_IMD, POOL_RES, POOL_SKL, POOL_NSK
 // an on / off knob of the environment: unset or non-zero = on.  Read on every call (the tests flip knobs between calls)
 static inline bool spdp_knob_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }
 
-// a blocking copy.  hipMemcpy goes through the null stream, which first waits for every blocking stream of the process.  For the
-// request batches of the seeded path -- several dispatcher lanes at work, a 16-byte read-back of the short class would wait
-// for the long class's multi-millisecond sweep -- the copy waits for its OWN stream only (t_lane_copies, set by
-// spdp_run_requests / spdh_run_requests for the duration of the call).  Everywhere else the null-stream form stays: in the
-// chunked ladder of spdp_align_s it keeps one chunk's slab sweeps from starting under the other chunk's linear-space sweep,
-// which changed nothing end to end when it was tried (290 ms a step either way, round 3) and is how the kernels of the headline
-// step were profiled.  It is also why more than two chunks lose there (profiles/chunk_handover_c2.txt): a chunk's post-work
-// waits for the sweep after it, and the lane's next sweep for that post-work.
+// a blocking copy.  hipMemcpy goes through the null stream, which first waits for every blocking stream of the process.
+// With t_lane_copies set the copy waits for its OWN stream only: in the request batches of the seeded path
+// (spdp_run_requests / spdh_run_requests) and on the chunk lanes of align_on_store (spdp_host.cpp; SPDP_CHUNK_LANE_COPIES).
+// What then orders a lane's copies: a copy goes through DevRun::strm(), the stream of the run's uploads and launches,
+// and every fetch follows DevRun::sync(), a host wait for that stream (side runs: side.sync()).  Lanes share no buffer
+// (spdp_lane); the one dependency between them is the gate's (ChunkGate: an event or the start signal).  An async copy
+// to or from a pageable vector is waited for before the vector is used or freed.  Everywhere else: the null-stream form.
 extern thread_local bool t_lane_copies;
-struct LaneCopies { bool was; LaneCopies() : was(t_lane_copies) { t_lane_copies = true; } ~LaneCopies() { t_lane_copies = was; } };
+struct LaneCopies {
+    bool was;
+    explicit LaneCopies(bool on = true) : was(t_lane_copies) { t_lane_copies = was || on; }
+    ~LaneCopies() { t_lane_copies = was; }
+};
 static inline hipError_t spdp_copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s)
 {
     if (!t_lane_copies) return hipMemcpy(dst, src, n, kind);
